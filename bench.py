@@ -17,12 +17,18 @@ two side streams of the pipeline over three buffer sets (call k + 1's record ker
 shapes one launch per call (step_kernel: records of call k + chains of call k + 1).  --pipeline-depth / --side-streams select the form.
   --advice: the prover-consumable witness as the product (h2r_pipeline_modpow_public_key_advice; roofline on cells_kernel).
 
+A plain run sets up, warms up, times the K steps and prints the line; nothing else.  --full adds what the headline does not need:
+the post-run checks of what was timed (results against pow(), the in-place audit, the advice MockProver ...), the CPU baseline, the
+live PMC traffic passes, the scale anchor and the sub-runs.  --dump-outputs DIR writes what the last timed step computed as
+DIR/<name>.npy (float32 / float64, every value exact; a fixed seeded sample where the output is large), for output-for-output
+comparisons of two builds: with the same arguments the inputs are the same in every run.
+
 Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
   roofline     -- the dominant kernel (trace_kernel / step_kernel / cells_kernel, HBM-write bound): algorithmic bytes per launch /
                   average launch time -- for launches that overlap on two side streams their PERIOD (timed wall time / launches;
                   avg_launch_ms_in_flight carries a launch's own duration from HIP events stamped by the dispatch), for the one-launch
                   steps the distance of two HIP events on the launch stream / launches, with --per-launch-timing per-launch HIP events.
-  cpu_baseline -- the CPU oracle ("port" of the reference's path, oracle/h2r_oracle.c) timed on this
+  cpu_baseline -- (--full) the CPU oracle ("port" of the reference's path, oracle/h2r_oracle.c) timed on this
                   host's cores on a bounded sample of the same workload (rank 0, N = 1 only).
 """
 import argparse
@@ -51,6 +57,7 @@ sys.path.insert(0, ROOT)
 
 import halo2_rsa_amd as H  # noqa: E402
 from halo2_rsa_amd import _lib  # noqa: E402
+from halo2_rsa_amd.big_integer import InFieldTrace  # noqa: E402
 from halo2_rsa_amd.dist import DistEnv, shard_range  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
@@ -87,6 +94,51 @@ WORKLOADS = {
 
 
 GLOBAL_SEED = 0x68327273
+
+DUMP_BUDGET = 48 << 20     # --dump-outputs: bytes of .npy data per run (the contract allows 64 MB)
+
+
+def exact_float(a):
+    """An integer array as float32 / float64 that holds every value exactly: 8- and 16-bit values as float32, 32-bit as float64,
+    64-bit values split into their two 32-bit halves (low half first) as float64."""
+    a = np.ascontiguousarray(a)
+    if a.dtype.itemsize == 8:
+        return a.view(np.uint32).astype(np.float64)
+    return a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+
+
+def byte_words(b):
+    """Raw bytes (uint8, last axis) as little-endian 16-bit words: half as many float32 values as bytes in the dump."""
+    b = np.ascontiguousarray(b, dtype=np.uint8)
+    if b.shape[-1] % 2:
+        b = np.concatenate([b, np.zeros(b.shape[:-1] + (1,), dtype=np.uint8)], axis=-1)
+    return b.view("<u2")
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (name -> integer ndarray) as path/<name>.npy, exact in float32 / float64."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        f = exact_float(a)
+        total += f.nbytes
+        assert total <= 64 * 10 ** 6, "--dump-outputs: more than 64 MB (%s)" % name
+        np.save(os.path.join(path, name + ".npy"), f)
+
+
+def sample_index(n, k, salt=0):
+    """A fixed, seeded, sorted sample of k of n indices (all of them when k >= n)."""
+    if k >= n:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(GLOBAL_SEED + salt).choice(n, size=k, replace=False))
+
+
+def sample_rows(t, row_bytes, budget=DUMP_BUDGET // 2, salt=0):
+    """A seeded sample of the rows of a large device byte tensor viewed as [-1, row_bytes], `budget` bytes of it in the dump
+    (a byte takes two there): (row indices, 16-bit words [k, row_bytes / 2])."""
+    rows = t.reshape(-1, row_bytes)
+    idx = sample_index(rows.shape[0], max(1, budget // (2 * row_bytes)), salt)
+    return idx, byte_words(rows[torch.from_numpy(idx).to(rows.device)].cpu().numpy())
 
 
 def synth_element(w, bits, g, golden):
@@ -243,15 +295,16 @@ def measured_pmc_traffic(argv_workload, kernel_prefix, timeout_s=150):
 
 
 def relaunch_under_torchrun(n):
-    """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run, one rank per GPU (the driver's
-    own multi-GPU command line does exactly this; WORLD_SIZE is then set and this is skipped)."""
+    """`python bench.py --gpus N` without a launcher: run again under torch.distributed.run, one rank per GPU, in a child process
+    whose exit status this one takes (the driver's own multi-GPU command line does exactly this; WORLD_SIZE is then set and this is skipped)."""
     import socket
+    import subprocess
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    sys.exit(subprocess.call(cmd))
 
 
 def check_gathered(gathered, audit_all, world, shard, total, w, bits, e, sample=True, strict=True, expect=None):
@@ -540,62 +593,73 @@ def advice_bench(args):
     chain_ms = _lib.profile_read(_lib.KERNEL_CHAIN)
     emit_ms = _lib.profile_read(_lib.KERNEL_EMIT)
     _lib.profile_enable(0)
-    # what was timed is the real thing: results against pow(), and the timed image against the image of a call WITH records
-    assert int(sts[last].max().item()) == 0 or (w, bits) != (64, 2048)
-    got = H.AssignedInteger(outs[last].contiguous(), w).to_big_uint()
-    for i in (0, 1, 2, chunk - 1):
-        if i < chunk and xs[i] < ns[i]:
-            assert got[i] == pow(xs[i], e, ns[i]), "GPU result differs from pow(x, e, n)"
-    sample = min(chunk, 8)
-    if whole:   # the record-based whole element (h2r_verify_pkcs1v15_batch + h2r_verify_emit_advice) of the first signatures
-        rsa = H.RSAChip(bits, 5, device=env.local_rank, columns=args.columns, montgomery=args.montgomery, col_stride=col_stride) if (args.columns or args.montgomery) \
-            else H.RSAChip(bits, 5, device=env.local_rank)
-        pk = H.RSAPublicKey(H.AssignedInteger(n_dev.limbs_dev[:sample].contiguous(), w), H.Fix(e))
-        ref = rsa.verify_pkcs1v15_signature(pk, hashed_dev[:sample].contiguous(), H.RSASignature(H.AssignedInteger(x_dev.limbs_dev[:sample].contiguous(), w)))
-        ref_img = ref.emit_advice()
-        assert torch.equal(ref.is_valid, valids[last][:sample]), "is_valid of the timed call differs from the record-based call's"
-    else:
-        ref = chip.pow_mod_fixed_exp(H.AssignedInteger(x_dev.limbs_dev[:sample].contiguous(), w), e, H.AssignedInteger(n_dev.limbs_dev[:sample].contiguous(), w),
-                                     check_in_field=True)
-        ref_img = ref.emit_modpow_advice(direct=False)
-    torch.cuda.synchronize()
-    timed = images[last].view(chunk, elem_bytes)[:sample]
-    if args.columns:   # (the columns are longer than the element's rows: compare what the image covers)
-        timed = timed.view(sample, 5, col_stride)[:, :, :rows * 32].reshape(sample, -1)
-        ref_img = ref_img.view(sample, 5, col_stride)[:, :, :rows * 32].reshape(sample, -1)
-    ok = ref.status.cpu().numpy() == 0
-    assert torch.equal(timed[torch.from_numpy(ok).to(timed.device)], ref_img[torch.from_numpy(ok).to(ref_img.device)]), \
-        "the timed advice image differs from the image of the records"
-    # ... and the WHOLE last timed image through the device-side MockProver (h2r_advice_check): the main-gate equation of every row, the
-    # range-check table of every lookup-enabled cell, every copy pair of the pow rows -- 1,024 x 77,021 rows where they lie
-    import numpy as np
-    if whole:
-        kinds_all = np.zeros(rows, dtype=np.uint8)
-        _lib.check(L.h2r_verify_row_kinds(chip._ctx, ctypes.byref(vl), kinds_all.ctypes.data), "h2r_verify_row_kinds")
-    else:
-        k_if = chip.fresh_op_row_kinds(_lib.FRESH_OPS.index("is_in_field"), assert_one=True)
-        k_pow = np.zeros(pow_rows, dtype=np.uint8)
-        _lib.check(L.h2r_pow_row_kinds(chip._ctx, ctypes.byref(pl), k_pow.ctypes.data), "h2r_pow_row_kinds")
-        kinds_all = np.concatenate([k_if, k_pow])
-    t_chk = time.perf_counter()
-    bad, first = chip.advice_check(kinds_all, images[last].view(chunk, elem_bytes), chunk, status=sts[last],
-                                   copies=chip.pow_copy_map(pl, e, row_offset=pow_off), src_a=x_dev, src_n=n_dev,
-                                   lookup=H.LookupArgument(chip, rsa_chip=whole))
-    n_bad = int((bad != 0).sum().item())
-    assert n_bad == 0, "h2r_advice_check: %d elements of the timed image violate a gate / lookup / copy (first: %#x)" % (n_bad, int(first[bad != 0][0].item()))
-    audit_s = time.perf_counter() - t_chk
-    # ... and the lookup multiplicities counted from the timed image (h2r_lookup_hist_advice: what the lookup argument needs of a witness that has
-    # no records) against those of the first signatures' records
-    la = H.LookupArgument(chip, rsa_chip=whole)
-    if whole:
-        want_h = la.hist_verify(ref, la.new_hist(sample))
-    else:
-        want_h = la.hist_records(ref.trace, la.new_hist(sample), status=ref.status)
-        la.hist_fresh_op("is_in_field", ref.in_field.buf, ref.in_field.elem_stride, sample, want_h)
-    got_h = la.hist_advice(kinds_all, images[last].view(chunk, elem_bytes)[:sample], sample, la.new_hist(sample), status=sts[last][:sample].contiguous())
-    torch.cuda.synchronize()
-    okh = torch.from_numpy(ok).to(got_h.device)
-    assert torch.equal(got_h[okh], want_h[okh]), "the lookup multiplicities of the timed image differ from those of the records"
+    if args.full:   # what was timed is the real thing: results against pow(), and the timed image against the image of a call WITH records
+        assert int(sts[last].max().item()) == 0 or (w, bits) != (64, 2048)
+        got = H.AssignedInteger(outs[last].contiguous(), w).to_big_uint()
+        for i in (0, 1, 2, chunk - 1):
+            if i < chunk and xs[i] < ns[i]:
+                assert got[i] == pow(xs[i], e, ns[i]), "GPU result differs from pow(x, e, n)"
+        sample = min(chunk, 8)
+        if whole:   # the record-based whole element (h2r_verify_pkcs1v15_batch + h2r_verify_emit_advice) of the first signatures
+            rsa = H.RSAChip(bits, 5, device=env.local_rank, columns=args.columns, montgomery=args.montgomery, col_stride=col_stride) if (args.columns or args.montgomery) \
+                else H.RSAChip(bits, 5, device=env.local_rank)
+            pk = H.RSAPublicKey(H.AssignedInteger(n_dev.limbs_dev[:sample].contiguous(), w), H.Fix(e))
+            ref = rsa.verify_pkcs1v15_signature(pk, hashed_dev[:sample].contiguous(), H.RSASignature(H.AssignedInteger(x_dev.limbs_dev[:sample].contiguous(), w)))
+            ref_img = ref.emit_advice()
+            assert torch.equal(ref.is_valid, valids[last][:sample]), "is_valid of the timed call differs from the record-based call's"
+        else:
+            ref = chip.pow_mod_fixed_exp(H.AssignedInteger(x_dev.limbs_dev[:sample].contiguous(), w), e, H.AssignedInteger(n_dev.limbs_dev[:sample].contiguous(), w),
+                                         check_in_field=True)
+            ref_img = ref.emit_modpow_advice(direct=False)
+        torch.cuda.synchronize()
+        timed = images[last].view(chunk, elem_bytes)[:sample]
+        if args.columns:   # (the columns are longer than the element's rows: compare what the image covers)
+            timed = timed.view(sample, 5, col_stride)[:, :, :rows * 32].reshape(sample, -1)
+            ref_img = ref_img.view(sample, 5, col_stride)[:, :, :rows * 32].reshape(sample, -1)
+        ok = ref.status.cpu().numpy() == 0
+        assert torch.equal(timed[torch.from_numpy(ok).to(timed.device)], ref_img[torch.from_numpy(ok).to(ref_img.device)]), \
+            "the timed advice image differs from the image of the records"
+        # ... and the WHOLE last timed image through the device-side MockProver (h2r_advice_check): the main-gate equation of every row, the
+        # range-check table of every lookup-enabled cell, every copy pair of the pow rows -- 1,024 x 77,021 rows where they lie
+        if whole:
+            kinds_all = np.zeros(rows, dtype=np.uint8)
+            _lib.check(L.h2r_verify_row_kinds(chip._ctx, ctypes.byref(vl), kinds_all.ctypes.data), "h2r_verify_row_kinds")
+        else:
+            k_if = chip.fresh_op_row_kinds(_lib.FRESH_OPS.index("is_in_field"), assert_one=True)
+            k_pow = np.zeros(pow_rows, dtype=np.uint8)
+            _lib.check(L.h2r_pow_row_kinds(chip._ctx, ctypes.byref(pl), k_pow.ctypes.data), "h2r_pow_row_kinds")
+            kinds_all = np.concatenate([k_if, k_pow])
+        t_chk = time.perf_counter()
+        bad, first = chip.advice_check(kinds_all, images[last].view(chunk, elem_bytes), chunk, status=sts[last],
+                                       copies=chip.pow_copy_map(pl, e, row_offset=pow_off), src_a=x_dev, src_n=n_dev,
+                                       lookup=H.LookupArgument(chip, rsa_chip=whole))
+        n_bad = int((bad != 0).sum().item())
+        assert n_bad == 0, "h2r_advice_check: %d elements of the timed image violate a gate / lookup / copy (first: %#x)" % (n_bad, int(first[bad != 0][0].item()))
+        audit_s = time.perf_counter() - t_chk
+        # ... and the lookup multiplicities counted from the timed image (h2r_lookup_hist_advice: what the lookup argument needs of a witness that has
+        # no records) against those of the first signatures' records
+        la = H.LookupArgument(chip, rsa_chip=whole)
+        if whole:
+            want_h = la.hist_verify(ref, la.new_hist(sample))
+        else:
+            want_h = la.hist_records(ref.trace, la.new_hist(sample), status=ref.status)
+            la.hist_fresh_op("is_in_field", ref.in_field.buf, ref.in_field.elem_stride, sample, want_h)
+        got_h = la.hist_advice(kinds_all, images[last].view(chunk, elem_bytes)[:sample], sample, la.new_hist(sample), status=sts[last][:sample].contiguous())
+        torch.cuda.synchronize()
+        okh = torch.from_numpy(ok).to(got_h.device)
+        assert torch.equal(got_h[okh], want_h[okh]), "the lookup multiplicities of the timed image differ from those of the records"
+    if args.dump_outputs and env.rank == 0:
+        # what the last timed call handed back: results, status (+ is_valid), and a seeded sample of the rows of its advice image (element * rows
+        # + row; the five 32-byte cells of a row, planar columns included)
+        dump = {"result_limbs": outs[last].cpu().numpy(), "status": sts[last].cpu().numpy()}
+        if whole:
+            dump["is_valid"] = valids[last].cpu().numpy()
+        idx = sample_index(chunk * rows, (DUMP_BUDGET // 2) // (2 * 160), salt=1)
+        ie, ir = (torch.from_numpy(v).to(dev) for v in (idx // rows, idx % rows))
+        img = images[last].view(chunk, 5, col_stride // 32, 32)[ie, :, ir, :] if args.columns else images[last].view(chunk, rows, 160)[ie, ir]
+        dump["image_row_index"] = idx.astype(np.uint64)
+        dump["image_row_words"] = byte_words(img.reshape(len(idx), 160).cpu().numpy())
+        dump_outputs(args.dump_outputs, dump)
     if env.rank == 0:
         algo = chunk * pow_rows * 160
         stamped_s = (sum(cells_ms) / len(cells_ms)) / 1e3 if cells_ms else float("nan")
@@ -626,8 +690,9 @@ def advice_bench(args):
                                     "pipeline's side stream (2 workspaces, 2 images)") if pipe is not None else
                                    "chain kernels of call k+1 on a second stream next to cells_kernel of call k (2 workspaces, 2 images), stream-ordered exports + events (H2R_BENCH_ADV=%s)" % adv_mode,
                        "untimed_clock_warmup_calls": ramp, "warmup_calls_total": 1 + ramp + warmup, "buffer_placement": placement,
-                       "post_run_audit": "h2r_advice_check on the last timed image: %d elements x %d rows, gate + lookup + %s copy pairs per element, 0 violations (%.2f s incl. the copy map); "
-                                         "h2r_lookup_hist_advice of its first %d elements = the multiplicities of their records" % (chunk, rows, "pow-row", audit_s, sample)},
+                       "post_run_audit": ("h2r_advice_check on the last timed image: %d elements x %d rows, gate + lookup + %s copy pairs per element, 0 violations (%.2f s incl. the copy map); "
+                                          "h2r_lookup_hist_advice of its first %d elements = the multiplicities of their records" % (chunk, rows, "pow-row", audit_s, sample))
+                                         if args.full else "none (bench.py --full runs it)"},
             "roofline": {"bound": "hbm", "achieved": round(achieved, 1) if achieved else None, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": round(achieved / HBM_PEAK_GBS, 4) if achieved else None, "traffic": None,
                          "traffic_source": "not measured", "kernel": "cells_kernel<%d%s>" % (w, ", Montgomery" if args.montgomery else ""), "launches_timed": len(cells_ms),
@@ -746,11 +811,17 @@ def lookup_bench(args):
     dt = time.perf_counter() - t0
     fill = _lib.profile_read(_lib.KERNEL_LOOKUP)
     _lib.profile_enable(0)
-    assert not status.cpu().numpy().any()
-    # what was timed is the real thing: every column sorted, and a multiset-preserving permutation of (inputs, table) for sampled circuits
-    av = a_perm[0, 0].view(torch.int64).view(usable, 4)
-    assert bool((av[1:, 3] >= av[:-1, 3]).all().item()) or args.montgomery, "A' is not sorted"
-    del av, a_perm, s_perm, out          # (views of the arena's mapped memory: gone before the arena unmaps it)
+    if args.full:
+        assert not status.cpu().numpy().any()
+        # what was timed is the real thing: every column sorted, and a multiset-preserving permutation of (inputs, table) for sampled circuits
+        av = a_perm[0, 0].view(torch.int64).view(usable, 4)
+        assert bool((av[1:, 3] >= av[:-1, 3]).all().item()) or args.montgomery, "A' is not sorted"
+        del av
+    if args.dump_outputs:   # the last call's status and the same seeded sample of the 32-byte cells of A' and of S'
+        ia, wa = sample_rows(a_perm, 32, budget=DUMP_BUDGET // 3, salt=1)
+        _, ws_ = sample_rows(s_perm, 32, budget=DUMP_BUDGET // 3, salt=1)
+        dump_outputs(args.dump_outputs, {"status": status.cpu().numpy(), "cell_index": ia.astype(np.uint64), "a_perm_words": wa, "s_perm_words": ws_})
+    del a_perm, s_perm, out          # (views of the arena's mapped memory: gone before the arena unmaps it)
     torch.cuda.synchronize()
     if arena is not None:
         arena.close()
@@ -865,21 +936,30 @@ def flow_bench(args):
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     a_perm, s_perm, status = state["out"]
-    assert not status.cpu().numpy().any()
-    # what was timed is the real thing: results against pow(), the multiplicities of the first circuits against the record-based call's
-    last = sets[(k0 + steps - 2) & 1]
-    got = H.AssignedInteger(last["powed"].contiguous(), w).to_big_uint()
-    for i in (0, 1, B - 1):
-        if xs[i] < ns[i]:
-            assert got[i] == pow(xs[i], e, ns[i]), "GPU result differs from pow(x, e, n)"
-    sample = min(B, 4)
-    ref = rsa.verify_pkcs1v15_signature(H.RSAPublicKey(H.AssignedInteger(n.limbs_dev[:sample].contiguous(), w), H.Fix(e)), hashed[:sample].contiguous(),
-                                        H.RSASignature(H.AssignedInteger(sig.limbs_dev[:sample].contiguous(), w)))
-    want = la.hist_verify(ref, la.new_hist(sample))
-    la.hist_values(sig.limbs_dev[:sample].contiguous(), 64, 8, want)
-    la.hist_values(n.limbs_dev[:sample].contiguous(), 64, 8, want)
-    torch.cuda.synchronize()
-    assert torch.equal(last["hist"][:sample], want), "multiplicities counted from the image differ from the records'"
+    last = sets[(k0 + steps - 2) & 1]   # (the batch whose multiplicities and columns the last step made)
+    if args.full:
+        assert not status.cpu().numpy().any()
+        # what was timed is the real thing: results against pow(), the multiplicities of the first circuits against the record-based call's
+        got = H.AssignedInteger(last["powed"].contiguous(), w).to_big_uint()
+        for i in (0, 1, B - 1):
+            if xs[i] < ns[i]:
+                assert got[i] == pow(xs[i], e, ns[i]), "GPU result differs from pow(x, e, n)"
+        sample = min(B, 4)
+        ref = rsa.verify_pkcs1v15_signature(H.RSAPublicKey(H.AssignedInteger(n.limbs_dev[:sample].contiguous(), w), H.Fix(e)), hashed[:sample].contiguous(),
+                                            H.RSASignature(H.AssignedInteger(sig.limbs_dev[:sample].contiguous(), w)))
+        want = la.hist_verify(ref, la.new_hist(sample))
+        la.hist_values(sig.limbs_dev[:sample].contiguous(), 64, 8, want)
+        la.hist_values(n.limbs_dev[:sample].contiguous(), 64, 8, want)
+        torch.cuda.synchronize()
+        assert torch.equal(last["hist"][:sample], want), "multiplicities counted from the image differ from the records'"
+    if args.dump_outputs:
+        # that batch's results, is_valid, status and multiplicities, and a seeded sample of the 32-byte cells of its A' and S'
+        dump = {k_: last[k_].cpu().numpy() for k_ in ("powed", "valid", "st", "hist")}
+        budget = (DUMP_BUDGET - sum(exact_float(v).nbytes for v in dump.values())) // 3
+        ia, dump["a_perm_words"] = sample_rows(a_perm, 32, budget=budget, salt=1)
+        _, dump["s_perm_words"] = sample_rows(s_perm, 32, budget=budget, salt=1)
+        dump["cell_index"] = ia.astype(np.uint64)
+        dump_outputs(args.dump_outputs, dump)
     img_b, col_b = B * rows * 160, 2 * B * 5 * usable * 32
     line = {"metric": "records-free prover inputs: circuits/sec (verify element image + lookup multiplicities + A', S')", "value": round(B / dt, 1), "unit": "circuits/s",
             "n_gpus": 1, "steps": steps, "warmup": max(2, args.warmup), "ms_per_step": round(1e3 * dt, 4), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
@@ -893,9 +973,9 @@ def flow_bench(args):
 
 
 def sub_run(extra, timeout=200):
-    """`bench.py <extra>` in a fresh process (same steps cap, no CPU baseline, no counters, no nested sub-runs): the parsed line."""
+    """`bench.py --full <extra>` in a fresh process (same steps cap, post-run checks, no CPU baseline, no counters, no nested sub-runs): the parsed line."""
     import subprocess
-    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--pmc-traffic", "off", "--scale-anchor", "off", "--sub-runs", "off"] + extra
+    cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--pmc-traffic", "off", "--scale-anchor", "off", "--sub-runs", "off"] + extra
     t0 = time.perf_counter()
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, check=True).stdout.strip().splitlines()[-1]
@@ -982,7 +1062,7 @@ def main():
     ap.add_argument("--records-free-flow", action="store_true",
                     help="the whole records-free flow per batch of one-signature circuits: verify element image + multiplicities from the image + A', S'")
     ap.add_argument("--sub-runs", choices=["auto", "off"], default="auto",
-                    help="auto: the default N = 1 line also carries plain_allocations, advice, advice_columns_montgomery, other_configs (C4, C5, RSA-1024) and lookup, "
+                    help="auto (with --full): the default N = 1 line also carries plain_allocations, advice, advice_columns_montgomery, other_configs (C4, C5, RSA-1024) and lookup, "
                          "each measured in a fresh process of this script")
     ap.add_argument("--columns", action="store_true", help="--advice: planar column vectors instead of 160-byte rows (H2R_ADVICE_COLUMNS)")
     ap.add_argument("--montgomery", action="store_true", help="--advice: cells in Montgomery form, x * 2^256 mod p (H2R_ADVICE_MONTGOMERY)")
@@ -1011,15 +1091,23 @@ def main():
                     help="N > 1: the broadcast / result all-gather / timing barrier go through libh2r's RCCL exports (h2r_dist_*, default) "
                          "or through torch.distributed")
     ap.add_argument("--scale-anchor", choices=["auto", "off"], default="auto",
-                    help="N = 1, default workload: also run the N > 1 per-GPU workload (8,192 signatures per step as four calls of 2,048) on this "
+                    help="N = 1, default workload, with --full: also run the N > 1 per-GPU workload (8,192 signatures per step as four calls of 2,048) on this "
                          "GPU and report it as `scale_anchor`: the like-for-like origin of a 1 -> 8 scaling curve")
     ap.add_argument("--pmc-traffic", choices=["auto", "off"], default="auto",
-                    help="roofline.traffic: auto = measure it now with two rocprofv3 --pmc passes of a short run of the same workload "
+                    help="roofline.traffic: auto (with --full) = measure it now with two rocprofv3 --pmc passes of a short run of the same workload "
                          "(N = 1, rank 0; falls back to the committed profiles/pmc_traffic.json when rocprofv3 is unavailable); off = committed file only")
     ap.add_argument("--dry-run-dist", action="store_true",
                     help="the N > 1 plumbing without the GPU (gloo on CPU): see dist_dry_run; tests/test_dist_cpu.py runs it at N = 8")
     ap.add_argument("--dry-total", type=int, default=0, help="--dry-run-dist: the global batch (need not be a multiple of N)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything the headline figure does not need: the post-run checks of what was timed, the CPU baseline, the live PMC "
+                         "traffic passes, the scale anchor and the sub-runs (each as its option says; without --full they are all off)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (rank 0's part) as DIR/<name>.npy, float32 / float64, "
+                         "at most 64 MB: a fixed seeded sample where the output is larger")
     args = ap.parse_args()
+    if not args.full:
+        args.no_cpu_baseline, args.pmc_traffic, args.scale_anchor, args.sub_runs = True, "off", "off", "off"
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         relaunch_under_torchrun(args.gpus)
     if args.dry_run_dist:
@@ -1103,10 +1191,11 @@ def main():
         eb = e.to_bytes((e.bit_length() + 7) // 8, "little")
         _lib.check(_lib.lib().h2r_verify_layout_fixed(chip._ctx, eb, len(eb), ctypes.byref(vl)), "h2r_verify_layout_fixed")
         elem_stride = vl.elem_stride
-        hashed_dev = torch.randint(-2**62, 2**62, (shard, 4), dtype=torch.int64, device=dev)
-        valid = torch.zeros(shard, dtype=torch.uint8, device=dev)
+        gen = torch.Generator(device=dev).manual_seed(GLOBAL_SEED + 41 + env.rank)   # (the same inputs in every run)
+        hashed_dev = torch.randint(-2**62, 2**62, (shard, 4), dtype=torch.int64, device=dev, generator=gen)
+        valid = torch.zeros((nbuf if chunks == 1 else chunks) * chunk, dtype=torch.uint8, device=dev)   # (indexed like the results: by region)
         if args.messages:   # the caller's step: message bytes -> SHA-256 -> hashed-message limbs, per call, on the device
-            msgs_dev = torch.randint(0, 256, (shard, args.messages), dtype=torch.uint8, device=dev)
+            msgs_dev = torch.randint(0, 256, (shard, args.messages), dtype=torch.uint8, device=dev, generator=gen)
             digest_dev = torch.zeros((shard, 32), dtype=torch.uint8, device=dev)
             hm_dev = torch.zeros((shard, _lib.H2R_HASHED_MSG_STREAM_BYTES), dtype=torch.uint8, device=dev)
     # The shard's traces stay resident on the GPU that produced them: with one call per step the calls
@@ -1138,7 +1227,7 @@ def main():
     else:
         trace_buf = torch.zeros(regions * chunk * elem_stride, dtype=torch.uint8, device=dev)
         trace_regions = [trace_buf[r * chunk * elem_stride:(r + 1) * chunk * elem_stride] for r in range(regions)]
-    ifs = chip.in_field_layout()[0]
+    ifs, ifs_sb = chip.in_field_layout()
     in_field_buf = torch.zeros(regions * chunk * ifs, dtype=torch.uint8, device=dev)   # assert_in_field witness (src/chip.rs:106)
     out = torch.zeros((regions * chunk, chip.num_limbs), dtype=chip.torch_dtype, device=dev)
     status = torch.zeros(regions * chunk, dtype=torch.uint8, device=dev)
@@ -1277,57 +1366,99 @@ def main():
         step_ms = _lib.profile_read(_lib.KERNEL_STEP)
         _lib.profile_enable(0)
 
-    # post-run: correctness of what was timed + the result gather (rank 0 receives every shard's x^e mod n)
-    assert int(status.max().item()) == 0 or (w, bits) != (64, 2048), "unexpected per-element status"
-    c_last = chunks - 1                                    # shard chunk the last call processed
-    res = out[last * chunk:(last + 1) * chunk]
-    got = H.AssignedInteger(res.contiguous(), w).to_big_uint()
-    base = c_last * chunk
-    # the trace that was timed is the real thing: first element of the last call, byte-exact vs pow() through q*n+r
-    tr = H.Trace(chip, trace_regions[last], chunk, pl)
-    tr.elem_stride = elem_stride
-    q0 = int.from_bytes(tr.plane(0, 0, "Q").tobytes(), "little")
-    r0 = int.from_bytes(tr.plane(0, 0, "R").tobytes(), "little")
-    assert xs[base] * xs[base] == q0 * ns[base] + r0, "first mul_mod record of the timed trace is wrong"
-    for i in (0, 1, 2, chunk - 1):
-        if i < chunk:
-            assert got[i] == pow(xs[base + i], e, ns[base + i]), "GPU result differs from pow(x, e, n)"
-    # one FULL call per shard audited in place on the device (h2r_pow_trace_check: every record of every element of the LAST call
-    # against SURVEY Appendix C's relations, independently of the producing kernels); the verdict bytes travel with the results
-    import ctypes as _ct
-    bad = torch.zeros(chunk, dtype=torch.int32, device=dev)
-    first_bad = torch.zeros(chunk, dtype=torch.int32, device=dev)
-    eb_ = e.to_bytes((e.bit_length() + 7) // 8, "little")
-    st_last = status[last * chunk:(last + 1) * chunk]
-    _lib.check(_lib.lib().h2r_pow_trace_check(chip._ctx, _ct.byref(vl.pow if verify else pl), xc[c_last].data_ptr(), nc[c_last].data_ptr(), eb_, len(eb_),
-                                              chip._flags(nc[c_last], chunk), trace_regions[last].data_ptr(), elem_stride,
-                                              workspaces[(counter[0] - 1) % nbuf].data_ptr(), chunk, st_last.data_ptr(), bad.data_ptr(),
-                                              first_bad.data_ptr(), chip._stream()), "h2r_pow_trace_check")
-    torch.cuda.synchronize()
-    audit = status[:shard].clone() if chunks > 1 else st_last.clone()
-    aud_last = ((bad != 0) | (st_last != 0)).to(torch.uint8)
-    if chunks > 1:
-        audit[last * chunk:(last + 1) * chunk] = aud_last
-    else:
-        audit = aud_last
-    shard_out = out[:shard].contiguous() if chunks > 1 else res.contiguous()
-    gathered, audit_all = env.gather_to_rank0(shard_out, audit.contiguous())
-    # every rank judges its own shard, rank 0 also the gathered results; the verdict is then AGREED (halo2_rsa_amd.dist.finish_with_verdict):
-    # a failed audit anywhere makes every rank exit non-zero with one line, and no result line is printed
-    verdict_ok, verdict_msg = True, ""
-    try:
-        n_mine = int((audit != 0).sum().item())
-        assert n_mine == 0 or (w, bits) != (64, 2048) or args.shared_modulus, "%d elements of this rank's shard with a status or a violated witness relation" % n_mine
-        if env.rank == 0:
-            verdict_ok, verdict_msg = check_gathered(gathered, audit_all, env.world, shard, shard * env.world, w, bits, e,
-                                                     sample=(chunks > 1 or env.world > 1 or shard > 1024) and not args.shared_modulus,
-                                                     strict=(w, bits) == (64, 2048) and not args.shared_modulus)
-    except AssertionError as ex:
-        verdict_ok, verdict_msg = False, str(ex)
-    if env.world > 1:
-        from halo2_rsa_amd.dist import finish_with_verdict
-        finish_with_verdict(env, verdict_ok, verdict_msg)
-    assert verdict_ok, verdict_msg
+    # post-run (--full): correctness of what was timed + the result gather (rank 0 receives every shard's x^e mod n)
+    if args.full:
+        assert int(status.max().item()) == 0 or (w, bits) != (64, 2048), "unexpected per-element status"
+        c_last = chunks - 1                                    # shard chunk the last call processed
+        res = out[last * chunk:(last + 1) * chunk]
+        got = H.AssignedInteger(res.contiguous(), w).to_big_uint()
+        base = c_last * chunk
+        # the trace that was timed is the real thing: first element of the last call, byte-exact vs pow() through q*n+r
+        tr = H.Trace(chip, trace_regions[last], chunk, pl)
+        tr.elem_stride = elem_stride
+        q0 = int.from_bytes(tr.plane(0, 0, "Q").tobytes(), "little")
+        r0 = int.from_bytes(tr.plane(0, 0, "R").tobytes(), "little")
+        assert xs[base] * xs[base] == q0 * ns[base] + r0, "first mul_mod record of the timed trace is wrong"
+        for i in (0, 1, 2, chunk - 1):
+            if i < chunk:
+                assert got[i] == pow(xs[base + i], e, ns[base + i]), "GPU result differs from pow(x, e, n)"
+        # one FULL call per shard audited in place on the device (h2r_pow_trace_check: every record of every element of the LAST call
+        # against SURVEY Appendix C's relations, independently of the producing kernels); the verdict bytes travel with the results
+        import ctypes as _ct
+        bad = torch.zeros(chunk, dtype=torch.int32, device=dev)
+        first_bad = torch.zeros(chunk, dtype=torch.int32, device=dev)
+        eb_ = e.to_bytes((e.bit_length() + 7) // 8, "little")
+        st_last = status[last * chunk:(last + 1) * chunk]
+        _lib.check(_lib.lib().h2r_pow_trace_check(chip._ctx, _ct.byref(vl.pow if verify else pl), xc[c_last].data_ptr(), nc[c_last].data_ptr(), eb_, len(eb_),
+                                                  chip._flags(nc[c_last], chunk), trace_regions[last].data_ptr(), elem_stride,
+                                                  workspaces[(counter[0] - 1) % nbuf].data_ptr(), chunk, st_last.data_ptr(), bad.data_ptr(),
+                                                  first_bad.data_ptr(), chip._stream()), "h2r_pow_trace_check")
+        torch.cuda.synchronize()
+        audit = status[:shard].clone() if chunks > 1 else st_last.clone()
+        aud_last = ((bad != 0) | (st_last != 0)).to(torch.uint8)
+        if chunks > 1:
+            audit[last * chunk:(last + 1) * chunk] = aud_last
+        else:
+            audit = aud_last
+        shard_out = out[:shard].contiguous() if chunks > 1 else res.contiguous()
+        gathered, audit_all = env.gather_to_rank0(shard_out, audit.contiguous())
+        # every rank judges its own shard, rank 0 also the gathered results; the verdict is then AGREED (halo2_rsa_amd.dist.finish_with_verdict):
+        # a failed audit anywhere makes every rank exit non-zero with one line, and no result line is printed
+        verdict_ok, verdict_msg = True, ""
+        try:
+            n_mine = int((audit != 0).sum().item())
+            assert n_mine == 0 or (w, bits) != (64, 2048) or args.shared_modulus, "%d elements of this rank's shard with a status or a violated witness relation" % n_mine
+            if env.rank == 0:
+                verdict_ok, verdict_msg = check_gathered(gathered, audit_all, env.world, shard, shard * env.world, w, bits, e,
+                                                         sample=(chunks > 1 or env.world > 1 or shard > 1024) and not args.shared_modulus,
+                                                         strict=(w, bits) == (64, 2048) and not args.shared_modulus)
+        except AssertionError as ex:
+            verdict_ok, verdict_msg = False, str(ex)
+        if env.world > 1:
+            from halo2_rsa_amd.dist import finish_with_verdict
+            finish_with_verdict(env, verdict_ok, verdict_msg)
+        assert verdict_ok, verdict_msg
+
+    if args.dump_outputs and env.rank == 0:
+        # what the calls of the last timed step handed back: results, status (+ is_valid, the message digests), and the witness of a seeded
+        # sample of the last call's elements as a flat stream in the reference's assignment order (in-field, then pow; the whole element with --verify)
+        regs = [last] if chunks == 1 else list(range(chunks))
+        rows_ = torch.cat([torch.arange(r * chunk, (r + 1) * chunk) for r in regs]).to(dev)
+        dump = {"result_limbs": out[rows_].cpu().numpy(), "status": status[rows_].cpu().numpy()}
+        if verify:
+            dump["is_valid"] = valid[rows_].cpu().numpy()
+            if args.messages:
+                cs = slice((chunks - 1) * chunk, chunks * chunk)
+                dump["last_call_hashed_msg_limbs"] = hashed_dev[cs].cpu().numpy()
+                dump["last_call_digests"] = digest_dev[cs].cpu().numpy()
+        import ctypes as _ct
+        sb = vl.stream_bytes if verify else pl.stream_bytes + (0 if args.no_in_field else ifs_sb)
+        k = min(chunk, 8, max(1, (DUMP_BUDGET // 2) // (2 * sb)))
+        elems = sample_index(chunk, k, salt=1)
+        tb = trace_regions[last]
+        streams = []
+        for i in elems:
+            i = int(i)
+            if verify:
+                host = np.ascontiguousarray(tb[i * elem_stride:(i + 1) * elem_stride].cpu().numpy())
+                st_ = np.zeros(vl.stream_bytes, dtype=np.uint8)
+                _lib.check(_lib.lib().h2r_verify_trace_flatten(chip._ctx, _ct.byref(vl), host.ctypes.data, st_.ctypes.data), "h2r_verify_trace_flatten")
+            else:
+                tr = H.Trace(chip, tb, chunk, pl)
+                tr.elem_stride = elem_stride
+                st_ = tr.flatten(i)
+                if not args.no_in_field:
+                    inf = InFieldTrace(chip, in_field_buf[last * chunk * ifs:(last + 1) * chunk * ifs], chunk, ifs, ifs_sb)
+                    st_ = np.concatenate([inf.flatten(i), st_])
+            streams.append(byte_words(st_))
+        words = np.stack(streams)
+        if words.nbytes * 2 > DUMP_BUDGET // 2:   # (a long exponent: a seeded sample of the stream's 16-bit words)
+            cols = sample_index(words.shape[1], (DUMP_BUDGET // 2) // (4 * k), salt=2)
+            words = words[:, cols]
+            dump["witness_word_index"] = cols.astype(np.uint32)
+        dump["witness_elements"] = elems.astype(np.uint32)
+        dump["witness_words"] = words
+        dump_outputs(args.dump_outputs, dump)
 
     if env.rank == 0:
         # written (pow stream + the assert_in_field stream of modpow_public_key) + inputs read
@@ -1373,7 +1504,8 @@ def main():
                        "mul_mods_per_assign": pl.num_mul_mods, "parallelism": "signature-sharded x%d" % env.world,
                        "ranks": env.describe()["ranks"], "rccl_version": env.describe()["rccl_version"], "communicator": env.describe()["communicator"],
                        "collective_backend": (env.backend + (" (RCCL)" if env.backend == "nccl" else "")) if env.initialised else "none (single process)",
-                       "post_run_check": "results of every shard vs pow(); last call of every shard audited in place (all %d elements, every record), verdict bytes gathered with the results" % chunk,
+                       "post_run_check": ("results of every shard vs pow(); last call of every shard audited in place (all %d elements, every record), verdict bytes gathered with the results" % chunk)
+                                         if args.full else "none (bench.py --full runs it)",
                        "pipeline": ((("one launch per step: records of call k + chains of call k+1 (step_kernel), %d buffer sets" % args.pipeline_depth)
                                      if step_ms else
                                      ("chain k+1 || trace k, %d buffer sets, %d record stream(s)" % (args.pipeline_depth, args.side_streams))) +
@@ -1436,7 +1568,7 @@ def scale_anchor_line(args):
     """`bench.py --gpus 1 --batch 2048 --chunks 4` (the per-GPU workload of every N > 1 run) in a fresh process, same steps / warm-up."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--batch", "2048", "--chunks", "4", "--steps", str(args.steps), "--warmup", str(args.warmup),
-           "--no-cpu-baseline", "--pmc-traffic", "off", "--scale-anchor", "off"]
+           "--full", "--no-cpu-baseline", "--pmc-traffic", "off", "--scale-anchor", "off"]
     try:
         out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, check=True).stdout.strip().splitlines()[-1]
         d = json.loads(out)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A table over default bench.py lines (one JSON line per file, each from a fresh box): headline, plain allocations and the sub-runs.
-usage: tools/multi_box_table.py gpurun_out/mb_*.json > profiles/r06_multi_box.txt"""
+"""A table over default `bench.py --full` lines (one JSON line per file, each from a fresh box): headline, plain allocations and the sub-runs.
+usage: tools/multi_box_table.py LINE.json ... > profiles/r06_multi_box.txt"""
 import json, sys
 
 rows = []

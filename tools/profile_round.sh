@@ -17,8 +17,8 @@ python tools/pmc_to_json.py $O 1024 > $O/pmc_traffic.json
 python tools/timeline.py $O/kt > $O/timeline_pipeline.txt
 python tools/timed_region_stats.py $O/kt 20 > $O/kernel_stats_pipeline_timed.csv
 python tools/timed_region_stats.py $O/kt_serial 20 > $O/kernel_stats_serial_timed.csv
-timeout 600 python bench.py --steps 40 --warmup 4 > $O/bench_pipeline.json 2> $O/bench_pipeline.err
-timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_pipeline_driver_args.json 2>/dev/null
+timeout 600 python bench.py --full --steps 40 --warmup 4 > $O/bench_pipeline.json 2> $O/bench_pipeline.err
+timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_pipeline_driver_args.json 2>/dev/null
 timeout 300 python bench.py --steps 40 --warmup 4 --no-pipeline --no-cpu-baseline --pmc-traffic off > $O/bench_serial.json 2>/dev/null
 # the same box with plain allocations (no placement-aware arena): what the arena is worth
 timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --pmc-traffic off --placement-candidates 0 > $O/bench_pipeline_driver_args_plain_allocations.json 2>/dev/null
@@ -62,7 +62,7 @@ python tools/sha256_timing.py > $O/sha256_timing.txt 2>&1
 python tools/fresh_advice_timing.py > $O/fresh_advice_timing.txt 2>&1
 # [round 4] the advice image as the product: kernel stats under rocprofv3, the bench line, the cells kernel alone by shape
 (cd /tmp; timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_advice -o r -- python $R/bench.py --advice --steps 10 --warmup 2 --no-cpu-baseline --pmc-traffic off > $O/kt_advice.log 2>&1)
-timeout 600 python bench.py --advice --steps 20 --warmup 5 > $O/bench_advice.json 2> $O/bench_advice.err
+timeout 600 python bench.py --full --advice --steps 20 --warmup 5 > $O/bench_advice.json 2> $O/bench_advice.err
 if [ -x tools/_bin/cells_bench ]; then
   { LD_LIBRARY_PATH=$R/halo2_rsa_amd/lib timeout 300 tools/_bin/cells_bench 64 2048 1024; LD_LIBRARY_PATH=$R/halo2_rsa_amd/lib timeout 300 tools/_bin/cells_bench 32 4096 431; } > $O/cells_kernel.txt 2>&1
 fi

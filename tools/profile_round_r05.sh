@@ -36,12 +36,12 @@ out["_units"] = "rocprofv3 --pmc, separate passes; KB per dispatch (calibration 
 print(json.dumps(out, indent=1))
 PY
 for t in advice advice_cm lookup; do f=$(ls $O/kt_$t/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $O/kernel_stats_$t.csv; done
-timeout -s KILL 400 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default_driver_args.json 2> $O/bench_default.err
-timeout -s KILL 200 python bench.py --advice --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_advice.json 2>/dev/null
+timeout -s KILL 400 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_default_driver_args.json 2> $O/bench_default.err
+timeout -s KILL 200 python bench.py --full --advice --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_advice.json 2>/dev/null
 timeout -s KILL 200 python bench.py --advice --columns --steps 20 --warmup 5 --no-cpu-baseline --pmc-traffic off > $O/bench_advice_columns.json 2>/dev/null
 timeout -s KILL 200 python bench.py --advice --montgomery --steps 20 --warmup 5 --no-cpu-baseline --pmc-traffic off > $O/bench_advice_montgomery.json 2>/dev/null
-timeout -s KILL 200 python bench.py --advice --columns --montgomery --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_advice_columns_montgomery.json 2>/dev/null
-timeout -s KILL 200 python bench.py --lookup --steps 8 --warmup 2 > $O/bench_lookup.json 2>/dev/null
+timeout -s KILL 200 python bench.py --full --advice --columns --montgomery --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_advice_columns_montgomery.json 2>/dev/null
+timeout -s KILL 200 python bench.py --full --lookup --steps 8 --warmup 2 > $O/bench_lookup.json 2>/dev/null
 timeout -s KILL 200 python bench.py --lookup --steps 8 --warmup 2 --placement-candidates 0 --pmc-traffic off > $O/bench_lookup_plain_allocations.json 2>/dev/null
 rm -rf $O/kt_* $O/pmc_*_w $O/pmc_*_r
 ls -la $O

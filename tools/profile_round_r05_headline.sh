@@ -15,7 +15,7 @@ python tools/timeline.py $O/kt > $O/timeline_pipeline.txt 2>/dev/null
 python tools/timed_region_stats.py $O/kt 20 > $O/kernel_stats_pipeline_timed.csv 2>/dev/null
 python tools/timed_region_stats.py $O/kt_serial 20 > $O/kernel_stats_serial_timed.csv 2>/dev/null
 cp $O/kt/r_kernel_stats.csv $O/kernel_stats_pipeline.csv; cp $O/kt_serial/r_kernel_stats.csv $O/kernel_stats_serial.csv
-$T 300 python bench.py --steps 40 --warmup 4 --sub-runs off > $O/bench_pipeline.json 2> $O/bench_pipeline.err
+$T 300 python bench.py --full --steps 40 --warmup 4 --sub-runs off > $O/bench_pipeline.json 2> $O/bench_pipeline.err
 $T 200 python bench.py --steps 40 --warmup 4 --no-pipeline --no-cpu-baseline --pmc-traffic off --sub-runs off > $O/bench_serial.json 2>/dev/null
 $T 200 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --pmc-traffic off --placement-candidates 0 > $O/bench_pipeline_driver_args_plain_allocations.json 2>/dev/null
 $T 200 python bench.py --steps 40 --warmup 4 --verify --no-cpu-baseline --pmc-traffic off --sub-runs off > $O/bench_verify.json 2>/dev/null
