@@ -137,7 +137,7 @@ def _adversarial_cases(bits, rng):
 @pytest.mark.parametrize("w,L", [(64, 32), (32, 128), (64, 16), (64, 64), (64, 48), (64, 24), (32, 96), (64, 40)])
 def test_mul_mod_adversarial_operands(H, w, L):
     """The chain kernel's ballot carries, DPP neighbour exchange and correction loop on adversarial digits: results
-    against Python integers for every triple, full traces against the oracle for a sample.  330 elements keep the
+    against Python integers for every triple, every element's full trace against the oracle.  330 elements keep the
     batch in the latency build's range (<= 512) for RSA-2048; a second, padded batch of 1,100 runs the throughput build."""
     bits = w * L
     chip = H.BigIntChip(w, bits)
@@ -152,18 +152,26 @@ def test_mul_mod_adversarial_operands(H, w, L):
         r = res.value.to_big_uint()
         bad = [i for i in range(len(A)) if r[i] != (A[i] * B[i]) % N[i]]
         assert not bad, (w, L, reps, bad[:5])
-        for i in rng.sample(range(len(A)), 12):
+        for i in range(len(A)):   # every element's trace, not a sample
             rc, rr, ost = o.mul_mod(o.limbs(A[i]), o.limbs(B[i]), o.limbs(N[i]))
-            assert rc == 0 and np.array_equal(ost, res.trace.flatten(i)), (w, L, i)
-    # the same moduli through a long square-and-multiply chain (errors would compound)
+            st = res.trace.flatten(i)
+            assert rc == 0 and np.array_equal(ost, st), (w, L, reps, i, "first mismatch at byte %d" % int(np.nonzero(ost != st)[0][0]))
+    # the same moduli through a long square-and-multiply chain (errors would compound): every record audited in place, every
+    # element's stream against the oracle
     e = (1 << 17) - 1
     n_list = sorted({c[2] for c in cases})
     X = [n - 2 for n in n_list]
-    pres = chip.pow_mod_fixed_exp(chip.assign_integer(X), e, chip.assign_integer(n_list), want_trace=False)
+    pres = chip.pow_mod_fixed_exp(chip.assign_integer(X), e, chip.assign_integer(n_list))
+    bad, _first = pres.audit()
     torch.cuda.synchronize()
     assert not pres.status.cpu().numpy().any()
+    assert not bad.cpu().numpy().any()
     got = pres.value.to_big_uint()
     assert all(got[i] == pow(X[i], e, n_list[i]) for i in range(len(X)))
+    for i in range(len(X)):
+        rc, _oo, ost = o.pow_mod_fixed_exp(o.limbs(X[i]), o.limbs(n_list[i]), e)
+        st = pres.trace.flatten(i)
+        assert rc == 0 and np.array_equal(ost, st), (w, L, "pow", i, "first mismatch at byte %d" % int(np.nonzero(ost != st)[0][0]))
 
 
 def test_mul_mod_golden_identities(H, golden):
@@ -1829,6 +1837,57 @@ def test_fresh_integer_family(H, w, L):
             assert fl == [int(A[i] < B[i]) for i in range(10)]
         if name == "is_greater_than_or_equal":
             assert fl == [int(A[i] >= B[i]) for i in range(10)]
+
+
+@pytest.mark.parametrize("w,L", [(64, 32), (64, 16), (64, 64), (32, 128)])
+def test_fresh_family_carry_and_borrow_runs(H, w, L):
+    """The Fresh family's ballot carries, borrows and comparisons (aux_* helpers: propagate masks ab_lo == MASK, ai == bi) on inputs
+    made of propagate runs, which random limbs almost never produce: a carry through every limb into limb L, borrow runs of 1 / 63 / 64 /
+    L-1 limbs, operands equal but for limb 0 / 63 / 64 / L-1, a + b == n with every limb sum == MASK, sub_mod with a < b.  (32, 128)
+    crosses the 64- and 128-limb blocks.  Stream, flag, value and status of every op in FRESH_OPS against the oracle."""
+    from oracle_lib import FRESH_OPS, fresh_op
+    import edge_cases as E
+    chip = H.BigIntChip(w, w * L)
+    o = Oracle(w, L)
+    cases = E.fresh_carry_cases(w, L)
+    A = [c[1] for c in cases]; B = [c[2] for c in cases]; N = [c[3] for c in cases]
+    a_dev, b_dev, n_dev = chip.assign_integer(A), chip.assign_integer(B), chip.assign_integer(N)
+    for name in FRESH_OPS:
+        fn = getattr(chip, name)
+        if name in ("add_mod", "sub_mod"):
+            res = fn(a_dev, b_dev, n_dev)
+        elif name == "is_zero":
+            res = fn(a_dev)
+        else:
+            res = fn(a_dev, b_dev)
+        torch.cuda.synchronize()
+        st = res.status.cpu().tolist()
+        fl = res.flag.cpu().tolist()
+        vals = res.value.to_big_uint() if res.value is not None else None
+        for i, (tag, a, b, n) in enumerate(cases):
+            rc, ov, of, ost = fresh_op(o, name, o.limbs(a), o.limbs(b), o.limbs(n))
+            if rc != 0:
+                assert st[i] != 0, (name, tag)
+                continue
+            assert st[i] == 0, (name, tag, st[i])
+            got = res.flatten(i)
+            assert np.array_equal(got, ost), (name, tag, "first mismatch at byte %d" % int(np.nonzero(got != ost)[0][0]))
+            if vals is not None:
+                assert vals[i] == o.to_int(ov), (name, tag)
+            if of >= 0:
+                assert fl[i] == of, (name, tag)
+        if name == "add":
+            assert vals == [a + b for _t, a, b, _n in cases]
+        if name == "sub":
+            assert all(vals[i] == a - b for i, (_t, a, b, _n) in enumerate(cases) if st[i] == 0 and a >= b)
+        if name == "is_less_than":
+            assert fl == [int(a < b) for _t, a, b, _n in cases]
+        if name == "is_greater_than_or_equal":
+            assert fl == [int(a >= b) for _t, a, b, _n in cases]
+        if name == "is_equal_fresh":
+            assert fl == [int(a == b) for _t, a, b, _n in cases]
+        if name == "is_in_field":
+            assert fl == [int(a < b) for _t, a, b, _n in cases]
 
 
 def test_fresh_ops_with_one_shared_comparand(H):
