@@ -110,7 +110,14 @@ inline u64 odd_stride_256(u64 bytes) {
 
 // The event a pipeline waits on for one call's record kernel.  With the profiler armed it is the profiler's own
 // stop event (borrowed; alive while g_prof_gen == gen), so that no extra marker packet sits between kernels.
-struct DoneRef { hipEvent_t ev = nullptr; u32 gen = 0; bool borrowed = false; };
+struct DoneRef {
+    hipEvent_t ev = nullptr; u32 gen = 0; bool borrowed = false;
+    bool alive() const {   // (h2r_profile_enable destroys the profiler's events and bumps the generation)
+        if (!borrowed) return true;
+        std::lock_guard<std::mutex> lk(g_prof_mu);
+        return gen == g_prof_gen;
+    }
+};
 
 struct Workspace {  // carve-up of the scratch of one batch call (relative to the 256-byte aligned base)
     u64 off_pre;   // the shared modulus' Barrett constants (recip_kernel), behind the operands
@@ -228,60 +235,140 @@ void fill_trace_args(const h2r_ctx *c, TraceArgs &ta) {
     if (knobs().trace_prio >= 0) ta.prio = (u32)knobs().trace_prio;
 }
 
+int32_t exp_to_bits(const uint8_t *e_le, size_t e_len, ExpBits *eb, u32 *T) {
+    if (!e_le && e_len) return H2R_E_NULL;
+    std::memset(eb, 0, sizeof *eb);
+    eb->nbits = exp_num_bits(e_le, e_len);
+    if (eb->nbits > 8 * sizeof eb->bytes) return H2R_E_UNSUPPORTED;
+    std::memcpy(eb->bytes, e_le, (eb->nbits + 7) / 8);
+    u32 t = 0;
+    for (u32 i = 0; i < eb->nbits; ++i) t += 1 + exp_bit(e_le, i);  // one square per bit, one mul per set bit
+    *T = t;
+    return H2R_OK;
+}
+
+inline bool shared(u32 flags) { return (flags & H2R_F_SHARED_MODULUS) != 0; }
+
+// The exponent of a pow call: one fixed exponent for the whole call (RSAPubE::Fix, BigIntChip::pow_mod_fixed_exp) or per-element
+// limbs (RSAPubE::Var, BigIntChip::pow_mod, chip.rs:664-696).
+struct Exponent {
+    ExpBits bits;            // fixed: e.to_bytes_le() (all zero for per-element limbs)
+    u32 T = 0;               // fixed: one squaring per bit, one multiply per set bit
+    int32_t rc = H2R_OK;     // fixed: what exp_to_bits said.  Reported where a call's checks reach the exponent (pow_layout),
+                             // so that every export keeps the order of its error codes
+    bool per_elem = false;   // per element: [batch][num_limbs] limbs of limb_bits bits each (limbs == nullptr: a shape only, for the layouts)
+    const void *limbs = nullptr; u32 num_limbs = 0, limb_bits = 0;
+    Exponent() { std::memset(&bits, 0, sizeof bits); }
+    static Exponent fixed(const uint8_t *e_le, size_t e_len) { Exponent e; e.rc = exp_to_bits(e_le, e_len, &e.bits, &e.T); return e; }
+    static Exponent per_element(const void *l, u32 nl, u32 lb) { Exponent e; e.per_elem = true; e.limbs = l; e.num_limbs = nl; e.limb_bits = lb; return e; }
+    bool var() const { return per_elem; }
+    u32 nbits() const { return var() ? num_limbs * limb_bits : bits.nbits; }
+    u32 chain_mode() const { return var() ? CHAIN_POW_VAR : CHAIN_POW_FIXED; }
+    Exponent at(u64 off, u32 limb_bytes) const {   // the exponent(s) of the elements from `off` on
+        Exponent e = *this;
+        if (limbs) e.limbs = static_cast<const u8 *>(limbs) + off * num_limbs * limb_bytes;
+        return e;
+    }
+};
+
 // run_path(..., args_only): fill the two kernels' arguments in and launch nothing (the pipeline issues them itself)
 struct PathArgs { ChainArgs ca; TraceArgs ta; bool has_trace = false; };
 // A long exponent walked as segments of its bits (ChainArgs::state): bits [bit_lo, bit_hi) = the mul_mods [t_lo, t_lo + t_cnt) of every element
 struct ExpSegment { u32 bit_lo, bit_hi, t_lo, t_cnt; };
+
+// WHAT one chain + record call computes.  The default is one mul_mod per element; pow() makes it a pow element of a layout.
+struct PowCall {
+    u32 mode = CHAIN_MULMOD, T = 1;       // T: mul_mods per element
+    const void *a = nullptr, *b = nullptr, *n = nullptr;
+    Exponent e;
+    u32 check_in_field = 0, flags = 0;
+    u64 batch = 0;
+    void *trace = nullptr;                // nullable: no witness
+    u64 elem_stride = 0, off_records = 0; // off_records = UINT64_MAX: a witness-only element (h2r_pow_layout_compact) -- the chain kernel leaves what it
+                                          // writes into a trace (a Var element's exponent bits and selected operands, the result), no record kernel follows
+    const h2r_pow_layout *pl = nullptr;
+    void *out = nullptr; uint8_t *status = nullptr;
+    void *workspace = nullptr;            // nullable in a plain stream-ordered call: stream-ordered scratch
+    // where the shared modulus' Barrett constants / the elements' moduli go when `workspace` is a slice of a larger call's plan (slice())
+    void *shared_pre = nullptr, *n_copy_at = nullptr;
+
+    // x ^ exponent, an element of layout `pl_` every `stride` bytes of the trace (the pow element itself, or one inside a verify element)
+    void pow(const Exponent &e_, const h2r_pow_layout &pl_, u64 stride) {
+        mode = e_.chain_mode(); e = e_; T = pl_.num_mul_mods; pl = &pl_; elem_stride = stride; off_records = pl_.off_records;
+    }
+    // The elements [off, off + nb) as a call of their own: slices of the caller's buffers and -- `whole`: the plan of the whole call, when
+    // it is walked as more than one sub-batch -- of the call's workspace ([batch * T][4][L], element-major), so audits and emitters see one call.
+    PowCall slice(const h2r_ctx *c, u64 off, u64 nb, const Workspace *whole) const {
+        const u64 in_bytes = (u64)c->K * 4;
+        PowCall s = *this;
+        s.batch = nb;
+        s.a = static_cast<const u8 *>(a) + off * in_bytes;
+        s.n = static_cast<const u8 *>(n) + (shared(flags) ? 0 : off * in_bytes);
+        s.e = e.at(off, c->layout.limb_bytes);
+        s.trace = static_cast<u8 *>(trace) + off * elem_stride;
+        s.out = out ? static_cast<u8 *>(out) + off * in_bytes : nullptr;
+        s.status = status + off;
+        if (whole) {
+            u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+            s.workspace = ws + off * ((u64)(T ? T : 1) * 4 * c->L * c->layout.limb_bytes);
+            s.shared_pre = ws + whole->off_pre;
+            s.n_copy_at = ws + whole->off_n + off * in_bytes;
+        }
+        return s;
+    }
+};
+
+// HOW it is issued.  Default-constructed (+ st): a plain stream-ordered call, both kernels on `st`.
+struct PowIssue {
+    hipStream_t st = nullptr;
+    hipStream_t trace_st = nullptr;       // pipeline mode: the record-writing kernel runs on trace_st after `chain_done`
+    hipEvent_t chain_done = nullptr, trace_done = nullptr;
+    DoneRef *done_ref = nullptr;          // out: what marks the end of the record kernel
+    PathArgs *args_only = nullptr; const ExpSegment *seg = nullptr;
+    static PowIssue on(hipStream_t st) { PowIssue i; i.st = st; return i; }
+};
+
 // Common driver: chain kernel (q, r of every mul_mod) then trace kernel (the witness records).
-int32_t run_path(const h2r_ctx *c, u32 mode, const void *a, const void *b, const void *n, const void *e_limbs,
-                 u32 e_num_limbs, u32 exp_limb_bits, const ExpBits *eb, u32 check_in_field, u64 batch, u32 flags,
-                 u32 T, void *trace, u64 elem_stride, u64 off_records, const h2r_pow_layout *pl, void *out,
-                 uint8_t *status, void *workspace, hipStream_t st, hipStream_t trace_st = nullptr,
-                 hipEvent_t chain_done = nullptr, hipEvent_t trace_done = nullptr, DoneRef *done_ref = nullptr,
-                 void *shared_pre = nullptr, PathArgs *args_only = nullptr, void *n_copy_at = nullptr, const ExpSegment *seg = nullptr) {
-    // shared_pre / n_copy_at: where the shared modulus' Barrett constants / the elements' moduli go when `workspace` is a
-    // slice of a larger call's plan
-    // trace_st != nullptr (pipeline mode): the record-writing kernel runs on trace_st after `chain_done`
-    if (!c || !n || !a || !status) return H2R_E_NULL;
-    if (trace_st && !workspace) return H2R_E_NULL;
+int32_t run_path(const h2r_ctx *c, const PowCall &call, const PowIssue &how) {
+    const u64 batch = call.batch; const u32 flags = call.flags, T = call.T;
+    void *trace = call.trace; uint8_t *status = call.status;
+    hipStream_t st = how.st, trace_st = how.trace_st;
+    if (!c || !call.n || !call.a || !status) return H2R_E_NULL;
+    if (trace_st && !call.workspace) return H2R_E_NULL;
     if (c->params.device < 0) return H2R_E_UNSUPPORTED;  // host-only context
     if (batch == 0) return H2R_OK;
     if (batch * (u64)(T ? T : 1) >= (1ull << 32)) return H2R_E_UNSUPPORTED;  // item index is 32-bit in the kernels
-    if (T == 0) {  // e == 0: no mul_mod at all; result is the constant 1 (chip.rs:729)
-        // handled by the chain kernel (loop of zero bits); still need a dummy ops buffer
-    }
+    // (T == 0, e == 0: no mul_mod at all; the result is the constant 1, chip.rs:729 -- the chain kernel's loop of zero bits)
     H2R_ON_DEVICE(c->params.device);
     const h2r_layout &lo = c->layout;
     const Workspace wp = workspace_plan(lo.limb_bytes, c->L, batch, T ? T : 1);
     ScratchGuard sg; sg.st = st;
-    u8 *ws = static_cast<u8 *>(workspace);
+    u8 *ws = static_cast<u8 *>(call.workspace);
     if (!ws) {
         HIP_TRY(hipMallocAsync(&sg.p, wp.total, st));
         sg.owned = true; ws = static_cast<u8 *>(sg.p);
     }
     ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(ws), 256));
-    // off_records = UINT64_MAX: a witness-only element (h2r_pow_layout_compact) -- the chain kernel leaves what it writes into a trace
-    // (a Var element's exponent bits and selected operands, the result), no record kernel follows
-    const bool records = trace && T && off_records != UINT64_MAX;
+    const bool records = trace && T && call.off_records != UINT64_MAX;
     ChainArgs ca;
     std::memset(&ca, 0, sizeof ca);
-    ca.a = static_cast<const u32 *>(a); ca.b = static_cast<const u32 *>(b); ca.n = static_cast<const u32 *>(n);
-    ca.e_limbs = static_cast<const u32 *>(e_limbs);
-    ca.n_stride = (flags & H2R_F_SHARED_MODULUS) ? 0 : c->K;
-    ca.batch = batch; ca.kreal = c->K; ca.mode = mode; ca.T = T ? T : 1;
-    ca.e_num_limbs = e_num_limbs; ca.exp_limb_bits = exp_limb_bits; ca.digits_per_limb = lo.limb_width / 32;
-    ca.check_in_field = check_in_field;
+    ca.a = static_cast<const u32 *>(call.a); ca.b = static_cast<const u32 *>(call.b); ca.n = static_cast<const u32 *>(call.n);
+    ca.e_limbs = static_cast<const u32 *>(call.e.limbs);
+    ca.n_stride = shared(flags) ? 0 : c->K;
+    ca.batch = batch; ca.kreal = c->K; ca.mode = call.mode; ca.T = T ? T : 1;
+    ca.e_num_limbs = call.e.num_limbs; ca.exp_limb_bits = call.e.limb_bits; ca.digits_per_limb = lo.limb_width / 32;
+    ca.check_in_field = call.check_in_field;
     ca.ops = reinterpret_cast<u32 *>(ws);
-    ca.out = static_cast<u32 *>(out); ca.status = status;
-    if (pl && trace) {
-        ca.trace = static_cast<u8 *>(trace); ca.elem_stride = elem_stride;
-        ca.off_e_bits = pl->off_e_bits; ca.off_selected = pl->off_selected; ca.selected_stride = pl->selected_stride;
-        ca.off_result = pl->off_result; ca.write_result_to_trace = 1;
-        if (mode != CHAIN_POW_VAR) { ca.off_e_bits = 0; ca.off_selected = 0; }
+    ca.out = static_cast<u32 *>(call.out); ca.status = status;
+    if (call.pl && trace) {
+        ca.trace = static_cast<u8 *>(trace); ca.elem_stride = call.elem_stride;
+        ca.off_e_bits = call.pl->off_e_bits; ca.off_selected = call.pl->off_selected; ca.selected_stride = call.pl->selected_stride;
+        ca.off_result = call.pl->off_result; ca.write_result_to_trace = 1;
+        if (call.mode != CHAIN_POW_VAR) { ca.off_e_bits = 0; ca.off_selected = 0; }
     }
-    if (eb) ca.e = *eb;
-    if (seg) { ca.state = reinterpret_cast<u32 *>(ws + wp.off_state); ca.bit_lo = seg->bit_lo; ca.bit_hi = seg->bit_hi; ca.t_base = seg->t_lo; }
-    u8 *n_copy = records ? (n_copy_at ? static_cast<u8 *>(n_copy_at) : ws + wp.off_n) : nullptr;
+    ca.e = call.e.bits;
+    if (how.seg) { ca.state = reinterpret_cast<u32 *>(ws + wp.off_state); ca.bit_lo = how.seg->bit_lo; ca.bit_hi = how.seg->bit_hi; ca.t_base = how.seg->t_lo; }
+    u8 *n_copy = records ? (call.n_copy_at ? static_cast<u8 *>(call.n_copy_at) : ws + wp.off_n) : nullptr;
     ca.n_copy = reinterpret_cast<u32 *>(n_copy);
     // 128-digit chains (RSA-4096 at 64-bit limbs) are the longer leg next to their record kernel: their waves get issue
     // priority there (1.00 -> 1.05 M assigns/s; no effect measured for the shorter chains)
@@ -292,25 +379,25 @@ int32_t run_path(const h2r_ctx *c, u32 mode, const void *a, const void *b, const
     if (knobs().chain_prio >= 0) ca.prio = (u32)knobs().chain_prio;
     // one key, many elements: the Barrett constants of the shared modulus are computed once (recip_kernel) instead of by
     // every element's workgroup (big_integer/chip.rs:562-567 divides by the same n every time)
-    // ... except in pipeline mode for the shapes whose chain kernel hides behind the record kernel anyway: the one-workgroup
+    // ... except in pipeline call.mode for the shapes whose chain kernel hides behind the record kernel anyway: the one-workgroup
     // recip_kernel in front of the chain kernel makes the chain kernel start 17 us AFTER the record kernel it shares the CUs
     // with instead of together with it, and the record kernel -- the longer leg -- then runs 0.195 -> 0.209 ms (same-box A/B,
     // bench.py --shared-modulus: 4.49 -> 4.8 M assigns/s without the precomputation).
     const bool chain_hidden = trace_st && records && (lo.limb_width == 32 || c->L <= 32);
-    if ((flags & H2R_F_SHARED_MODULUS) && batch > 1 && !chain_hidden)
-        ca.pre = reinterpret_cast<const u32 *>(shared_pre ? static_cast<u8 *>(shared_pre) : ws + wp.off_pre);
-    // Pipeline mode: the record stream must wait for this chain kernel.  The event it waits on is the dispatch's own
-    // stop event (the profiler's when armed, else chain_done) -- no separate marker packet.
+    if (shared(flags) && batch > 1 && !chain_hidden)
+        ca.pre = reinterpret_cast<const u32 *>(call.shared_pre ? static_cast<u8 *>(call.shared_pre) : ws + wp.off_pre);
+    // Pipeline call.mode: the record stream must wait for this chain kernel.  The event it waits on is the dispatch's own
+    // stop event (the profiler's when armed, else how.chain_done) -- no separate marker packet.
     hipEvent_t chain_wait = nullptr;
 #ifdef H2R_CHAIN_TIMING   // developer build (tools/chain_timing.py): dump block 0's s_memtime stamps
     static u64 *dbg_buf = nullptr;
     if (knobs().chain_timing) { if (!dbg_buf) (void)hipMalloc(&dbg_buf, 4096 * 8); (void)hipMemsetAsync(dbg_buf, 0, 4096 * 8, st); ca.dbg_time = dbg_buf; }
 #endif
-    if (args_only) args_only->ca = ca;
+    if (how.args_only) how.args_only->ca = ca;
     else {
         ProfScope ps(H2R_KERNEL_CHAIN, st, true);
         const bool piped = trace_st && records;
-        chain_wait = ps.on ? ps.b : (piped ? chain_done : nullptr);
+        chain_wait = ps.on ? ps.b : (piped ? how.chain_done : nullptr);
         if (c->K > 128) return H2R_E_UNSUPPORTED;
         HIP_TRY(launch_chain(c, ca, trace_st != nullptr, st, ps.a, chain_wait));
     }
@@ -329,9 +416,9 @@ int32_t run_path(const h2r_ctx *c, u32 mode, const void *a, const void *b, const
         ta.opA = ws; ta.opB = ws + c->L * lb; ta.opQ = ws + 2 * c->L * lb; ta.opR = ws + 3 * c->L * lb; ta.op_stride = 4ull * c->L;
         ta.n = n_copy; ta.n_stride = c->L;   // the chain kernel's copy: the caller's n is read inside the call only
         ta.status = status; ta.n_items = batch * T; ta.T = T;
-        if (seg) { ta.n_items = batch * seg->t_cnt; ta.T = seg->t_cnt; ta.t_lo = seg->t_lo; ta.T_ops = T; }   // this segment's mul_mods of every element
-        ta.trace = static_cast<u8 *>(trace); ta.elem_stride = elem_stride; ta.off_records = off_records;
-        if (args_only) { args_only->ta = ta; args_only->has_trace = true; return H2R_OK; }
+        if (how.seg) { ta.n_items = batch * how.seg->t_cnt; ta.T = how.seg->t_cnt; ta.t_lo = how.seg->t_lo; ta.T_ops = T; }   // this segment's mul_mods of every element
+        ta.trace = static_cast<u8 *>(trace); ta.elem_stride = call.elem_stride; ta.off_records = call.off_records;
+        if (how.args_only) { how.args_only->ta = ta; how.args_only->has_trace = true; return H2R_OK; }
         hipStream_t ts = st;
         // LDS share of the record kernel's workgroups (the occupancy lever on this hardware: an LDS request the kernel never
         // touches).  ALONE the 64-bit-limb shapes up to RSA-2048 write fastest with FEW concurrent store streams: one
@@ -363,26 +450,14 @@ int32_t run_path(const h2r_ctx *c, u32 mode, const void *a, const void *b, const
             ts = trace_st;
         }
         ProfScope ps(H2R_KERNEL_TRACE, ts, true);
-        HIP_TRY(launch_trace(c, ta, ts, ps.a, ps.on ? ps.b : trace_done));
-        if (done_ref) {
-            if (ps.on) { std::lock_guard<std::mutex> lk(g_prof_mu); *done_ref = DoneRef{ps.b, g_prof_gen, true}; }
-            else *done_ref = DoneRef{trace_done, 0, false};
+        HIP_TRY(launch_trace(c, ta, ts, ps.a, ps.on ? ps.b : how.trace_done));
+        if (how.done_ref) {
+            if (ps.on) { std::lock_guard<std::mutex> lk(g_prof_mu); *how.done_ref = DoneRef{ps.b, g_prof_gen, true}; }
+            else *how.done_ref = DoneRef{how.trace_done, 0, false};
         }
-    } else if (done_ref) {
-        *done_ref = DoneRef{};
+    } else if (how.done_ref) {
+        *how.done_ref = DoneRef{};
     }
-    return H2R_OK;
-}
-
-int32_t exp_to_bits(const uint8_t *e_le, size_t e_len, ExpBits *eb, u32 *T) {
-    if (!e_le && e_len) return H2R_E_NULL;
-    std::memset(eb, 0, sizeof *eb);
-    eb->nbits = exp_num_bits(e_le, e_len);
-    if (eb->nbits > 8 * sizeof eb->bytes) return H2R_E_UNSUPPORTED;
-    std::memcpy(eb->bytes, e_le, (eb->nbits + 7) / 8);
-    u32 t = 0;
-    for (u32 i = 0; i < eb->nbits; ++i) t += 1 + exp_bit(e_le, i);  // one square per bit, one mul per set bit
-    *T = t;
     return H2R_OK;
 }
 
@@ -418,6 +493,57 @@ void fresh_sections(const AuxGeom &g, u32 op, F &&emit) {
 }
 template <typename F>
 void in_field_sections(const AuxGeom &g, F &&emit) { fresh_sections(g, FRESH_IS_IN_FIELD, emit); }
+
+// One pow element: the records of its mul_mods, then the result; a per-element exponent adds its selected operands and its bits.
+int32_t pow_layout(const h2r_ctx *ctx, const Exponent &e, h2r_pow_layout *out) {
+    if (!ctx || !out) return H2R_E_NULL;
+    const h2r_layout &lo = ctx->layout;
+    if (!e.var()) {
+        if (e.rc) return e.rc;
+        std::memset(out, 0, sizeof *out);
+        out->num_mul_mods = e.T; out->num_exp_bits = e.bits.nbits;
+        out->off_records = 0;
+        out->off_result = (u64)e.T * lo.record_stride;
+        out->off_e_bits = UINT64_MAX; out->off_selected = UINT64_MAX; out->selected_stride = 0;
+        out->elem_stride = odd_stride_256(out->off_result + (u64)lo.num_limbs * lo.limb_bytes);
+        out->stream_bytes = (u64)e.T * lo.stream_bytes + (u64)lo.num_limbs * lo.limb_bytes;
+        return H2R_OK;
+    }
+    if (e.num_limbs == 0 || e.limb_bits == 0 || e.limb_bits > lo.limb_width) return H2R_E_SHAPE;
+    const u64 nbits = (u64)e.num_limbs * e.limb_bits;
+    if (nbits > (1u << 20)) return H2R_E_UNSUPPORTED;
+    std::memset(out, 0, sizeof *out);
+    out->num_mul_mods = (u32)(2 * nbits); out->num_exp_bits = (u32)nbits;
+    out->exp_limb_bits = e.limb_bits; out->e_num_limbs = e.num_limbs;
+    out->off_records = 0;
+    const u64 limbs_bytes = round_up((u64)lo.num_limbs * lo.limb_bytes, 256);
+    out->off_selected = 2 * nbits * lo.record_stride;
+    out->selected_stride = limbs_bytes;
+    out->off_result = out->off_selected + nbits * limbs_bytes;
+    out->off_e_bits = out->off_result + limbs_bytes;
+    out->elem_stride = odd_stride_256(out->off_e_bits + nbits);
+    out->stream_bytes = nbits + nbits * (2 * lo.stream_bytes + (u64)lo.num_limbs * lo.limb_bytes) + (u64)lo.num_limbs * lo.limb_bytes;
+    return H2R_OK;
+}
+
+// One RSAChip::verify_pkcs1v15_signature element: the pow element, then the in-field and the encoded-message witness.
+int32_t verify_layout(const h2r_ctx *ctx, const Exponent &e, h2r_verify_layout *out) {
+    if (!ctx || !out) return H2R_E_NULL;
+    if (ctx->layout.limb_width != 64 || ctx->L < 9) return H2R_E_SHAPE;  // RSAChip::LIMB_WIDTH, src/chip.rs:203
+    std::memset(out, 0, sizeof *out);
+    int32_t rc = pow_layout(ctx, e, &out->pow);
+    if (rc) return rc;
+    const AuxGeom g(ctx->L, 64);
+    out->off_in_field = out->pow.elem_stride;
+    u64 sb = 0;
+    in_field_sections(g, [&](u64, u64 len) { sb += len; });
+    out->in_field_stream_bytes = sb;
+    out->off_em = out->off_in_field + round_up(g.in_field_sz(), 256);
+    out->em_stream_bytes = 2ull * ctx->L + 34;
+    out->elem_stride = odd_stride_256(out->off_em + g.em_sz());
+    out->stream_bytes = out->in_field_stream_bytes + out->pow.stream_bytes + out->em_stream_bytes;
+    return H2R_OK;
+}
 
 }  // namespace
 
@@ -590,263 +716,17 @@ int32_t h2r_trace_layout(const h2r_ctx *ctx, h2r_layout *out) try {
 } H2R_CATCH_STATUS
 
 int32_t h2r_pow_fixed_layout(const h2r_ctx *ctx, const uint8_t *e_le, size_t e_len, h2r_pow_layout *out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    ExpBits eb; u32 T;
-    int32_t rc = exp_to_bits(e_le, e_len, &eb, &T);
-    if (rc) return rc;
-    const h2r_layout &lo = ctx->layout;
-    std::memset(out, 0, sizeof *out);
-    out->num_mul_mods = T; out->num_exp_bits = eb.nbits;
-    out->off_records = 0;
-    out->off_result = (u64)T * lo.record_stride;
-    out->off_e_bits = UINT64_MAX; out->off_selected = UINT64_MAX; out->selected_stride = 0;
-    out->elem_stride = odd_stride_256(out->off_result + (u64)lo.num_limbs * lo.limb_bytes);
-    out->stream_bytes = (u64)T * lo.stream_bytes + (u64)lo.num_limbs * lo.limb_bytes;
-    return H2R_OK;
+    return pow_layout(ctx, Exponent::fixed(e_le, e_len), out);
 } H2R_CATCH_STATUS
 
 int32_t h2r_pow_var_layout(const h2r_ctx *ctx, uint32_t e_num_limbs, uint32_t exp_limb_bits, h2r_pow_layout *out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    const h2r_layout &lo = ctx->layout;
-    if (e_num_limbs == 0 || exp_limb_bits == 0 || exp_limb_bits > lo.limb_width) return H2R_E_SHAPE;
-    const u64 nbits = (u64)e_num_limbs * exp_limb_bits;
-    if (nbits > (1u << 20)) return H2R_E_UNSUPPORTED;
-    std::memset(out, 0, sizeof *out);
-    out->num_mul_mods = (u32)(2 * nbits); out->num_exp_bits = (u32)nbits;
-    out->exp_limb_bits = exp_limb_bits; out->e_num_limbs = e_num_limbs;
-    out->off_records = 0;
-    const u64 limbs_bytes = round_up((u64)lo.num_limbs * lo.limb_bytes, 256);
-    out->off_selected = 2 * nbits * lo.record_stride;
-    out->selected_stride = limbs_bytes;
-    out->off_result = out->off_selected + nbits * limbs_bytes;
-    out->off_e_bits = out->off_result + limbs_bytes;
-    out->elem_stride = odd_stride_256(out->off_e_bits + nbits);
-    out->stream_bytes = nbits + nbits * (2 * lo.stream_bytes + (u64)lo.num_limbs * lo.limb_bytes) + (u64)lo.num_limbs * lo.limb_bytes;
-    return H2R_OK;
+    return pow_layout(ctx, Exponent::per_element(nullptr, e_num_limbs, exp_limb_bits), out);
 } H2R_CATCH_STATUS
 
 uint64_t h2r_workspace_bytes(const h2r_ctx *ctx, uint64_t batch, uint32_t num_mul_mods) try {
     if (!ctx) return 0;
     return workspace_plan(ctx->layout.limb_bytes, ctx->L, batch, num_mul_mods ? num_mul_mods : 1).total;
 } H2R_CATCH_ZERO
-
-int32_t h2r_mul_mod_batch(const h2r_ctx *ctx, const void *a, const void *b, const void *n, uint64_t batch,
-                          uint32_t flags, void *trace, void *r_out, uint8_t *status, void *workspace,
-                          h2r_stream_t stream) try {
-    if (!ctx || !b) return H2R_E_NULL;
-    return run_path(ctx, CHAIN_MULMOD, a, b, n, nullptr, 0, 0, nullptr, 0, batch, flags, 1, trace,
-                    ctx->layout.record_stride, 0, nullptr, r_out, status, workspace, static_cast<hipStream_t>(stream));
-} H2R_CATCH_STATUS
-
-int32_t h2r_square_mod_batch(const h2r_ctx *ctx, const void *a, const void *n, uint64_t batch, uint32_t flags,
-                             void *trace, void *r_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    return h2r_mul_mod_batch(ctx, a, a, n, batch, flags, trace, r_out, status, workspace, stream);  // chip.rs:648
-} H2R_CATCH_STATUS
-
-namespace {
-int32_t launch_verify_aux(const h2r_ctx *ctx, const void *sig, const void *n, const uint64_t *hashed, uint64_t batch, uint32_t flags,
-                          void *trace, const h2r_verify_layout &vl, void *powed_out, uint8_t *is_valid_out, uint8_t *status, hipStream_t st);
-AuxArgs verify_aux_args(const h2r_ctx *ctx, const void *sig, const void *n, const uint64_t *hashed, uint64_t batch, uint32_t flags,
-                        void *trace, const h2r_verify_layout &vl, void *powed_out, uint8_t *is_valid_out, uint8_t *status);
-int32_t launch_in_field(const h2r_ctx *ctx, const void *x, const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, hipStream_t st);
-int32_t in_field_args(const h2r_ctx *ctx, const void *x, const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, AuxArgs *aa, u32 *lds);
-}
-
-namespace {
-bool plain_call_overlaps(const h2r_ctx *c, u64 batch);
-u32 exp_segment_count(const h2r_ctx *c, u64 batch, u32 nbits, bool has_trace, bool single_call = false);
-int32_t overlapped_pow_fixed(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch,
-                             uint32_t flags, void *trace, const h2r_pow_layout &pl, uint64_t elem_stride, void *out, uint8_t *status,
-                             void *workspace, hipStream_t st, u32 check_in_field, u32 T,
-                             const void *e_limbs = nullptr, u32 e_num_limbs = 0, u32 exp_limb_bits = 0);
-}
-
-static int32_t pow_fixed_impl(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le, size_t e_len,
-                              uint64_t batch, uint32_t flags, void *trace, void *out, uint8_t *status,
-                              void *workspace, h2r_stream_t stream, u32 check_in_field) {
-    if (!ctx) return H2R_E_NULL;
-    ExpBits eb; u32 T;
-    int32_t rc = exp_to_bits(e_le, e_len, &eb, &T);
-    if (rc) return rc;
-    h2r_pow_layout pl;
-    rc = h2r_pow_fixed_layout(ctx, e_le, e_len, &pl);
-    if (rc) return rc;
-    // a large call with a trace: sub-batches whose chain kernels run next to the previous sub-batch's record kernel (a side
-    // stream of the ctx), joined back onto the caller's stream before returning -- stream-ordered as ever for the caller
-    if (trace && T && x && n && status && ctx->params.device >= 0 && (plain_call_overlaps(ctx, batch) || exp_segment_count(ctx, batch, eb.nbits, true, true) > 1))
-        return overlapped_pow_fixed(ctx, x, n, e_le, e_len, batch, flags, trace, pl, pl.elem_stride, out, status, workspace,
-                                    static_cast<hipStream_t>(stream), check_in_field, T);
-    return run_path(ctx, CHAIN_POW_FIXED, x, nullptr, n, nullptr, 0, 0, &eb, check_in_field, batch, flags, T, trace,
-                    pl.elem_stride, pl.off_records, &pl, out, status, workspace, static_cast<hipStream_t>(stream));
-}
-
-static int32_t pow_var_impl(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs, uint32_t exp_limb_bits,
-                            const void *n, uint64_t batch, uint32_t flags, void *trace, void *out, uint8_t *status,
-                            void *workspace, h2r_stream_t stream, u32 check_in_field) {
-    if (!ctx || !e_limbs) return H2R_E_NULL;
-    h2r_pow_layout pl;
-    int32_t rc = h2r_pow_var_layout(ctx, e_num_limbs, exp_limb_bits, &pl);
-    if (rc) return rc;
-    // a long exponent on a latency-bound batch: walked as segments of its bits, each segment's records next to the next one's chains
-    if (trace && pl.num_mul_mods && x && n && status && ctx->params.device >= 0 && exp_segment_count(ctx, batch, e_num_limbs * exp_limb_bits, true) > 1)
-        return overlapped_pow_fixed(ctx, x, n, nullptr, 0, batch, flags, trace, pl, pl.elem_stride, out, status, workspace,
-                                    static_cast<hipStream_t>(stream), check_in_field, pl.num_mul_mods, e_limbs, e_num_limbs, exp_limb_bits);
-    return run_path(ctx, CHAIN_POW_VAR, x, nullptr, n, e_limbs, e_num_limbs, exp_limb_bits, nullptr, check_in_field, batch, flags,
-                    pl.num_mul_mods, trace, pl.elem_stride, pl.off_records, &pl, out, status, workspace,
-                    static_cast<hipStream_t>(stream));
-}
-
-int32_t h2r_pow_mod_fixed_exp_batch(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le,
-                                    size_t e_len, uint64_t batch, uint32_t flags, void *trace, void *out,
-                                    uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    return pow_fixed_impl(ctx, x, n, e_le, e_len, batch, flags, trace, out, status, workspace, stream, 0);
-} H2R_CATCH_STATUS
-
-int32_t h2r_pow_mod_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs,
-                          uint32_t exp_limb_bits, const void *n, uint64_t batch, uint32_t flags, void *trace,
-                          void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    return pow_var_impl(ctx, x, e_limbs, e_num_limbs, exp_limb_bits, n, batch, flags, trace, out, status, workspace, stream, 0);
-} H2R_CATCH_STATUS
-
-// RSAChip::modpow_public_key (src/chip.rs:99-114): assert_in_field witness (:106), then the pow path with the in-field
-// predicate folded into the chain kernel's status.
-int32_t h2r_modpow_public_key_batch(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le,
-                                    size_t e_len, uint64_t batch, uint32_t flags, void *trace, void *in_field_trace,
-                                    void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    const int32_t rc = pow_fixed_impl(ctx, x, n, e_le, e_len, batch, flags, trace, out, status, workspace, stream, 1);
-    if (rc || !in_field_trace) return rc;
-    return launch_in_field(ctx, x, n, batch, flags, in_field_trace, static_cast<hipStream_t>(stream));
-} H2R_CATCH_STATUS
-
-int32_t h2r_modpow_public_key_var_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs,
-                                        uint32_t exp_limb_bits, const void *n, uint64_t batch, uint32_t flags, void *trace,
-                                        void *in_field_trace, void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    const int32_t rc = pow_var_impl(ctx, x, e_limbs, e_num_limbs, exp_limb_bits, n, batch, flags, trace, out, status, workspace, stream, 1);
-    if (rc || !in_field_trace) return rc;
-    return launch_in_field(ctx, x, n, batch, flags, in_field_trace, static_cast<hipStream_t>(stream));
-} H2R_CATCH_STATUS
-
-int32_t h2r_verify_layout_fixed(const h2r_ctx *ctx, const uint8_t *e_le, size_t e_len, h2r_verify_layout *out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    if (ctx->layout.limb_width != 64 || ctx->L < 9) return H2R_E_SHAPE;  // RSAChip::LIMB_WIDTH, src/chip.rs:203
-    std::memset(out, 0, sizeof *out);
-    int32_t rc = h2r_pow_fixed_layout(ctx, e_le, e_len, &out->pow);
-    if (rc) return rc;
-    const AuxGeom g(ctx->L, 64);
-    out->off_in_field = out->pow.elem_stride;
-    u64 sb = 0;
-    in_field_sections(g, [&](u64, u64 len) { sb += len; });
-    out->in_field_stream_bytes = sb;
-    out->off_em = out->off_in_field + round_up(g.in_field_sz(), 256);
-    out->em_stream_bytes = 2ull * ctx->L + 34;
-    out->elem_stride = odd_stride_256(out->off_em + g.em_sz());
-    out->stream_bytes = out->in_field_stream_bytes + out->pow.stream_bytes + out->em_stream_bytes;
-    return H2R_OK;
-} H2R_CATCH_STATUS
-
-
-int32_t h2r_verify_pkcs1v15_batch(const h2r_ctx *ctx, const void *sig, const void *n, const uint8_t *e_le, size_t e_len,
-                                  const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace, void *powed_out,
-                                  uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!ctx || !sig || !n || !hashed || !trace || !powed_out || !status) return H2R_E_NULL;
-    h2r_verify_layout vl;
-    int32_t rc = h2r_verify_layout_fixed(ctx, e_le, e_len, &vl);
-    if (rc) return rc;
-    ExpBits eb; u32 T;
-    rc = exp_to_bits(e_le, e_len, &eb, &T);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (T && ctx->params.device >= 0 && plain_call_overlaps(ctx, batch))   // large call: overlapping sub-batches, as pow_fixed_impl
-        rc = overlapped_pow_fixed(ctx, sig, n, e_le, e_len, batch, flags, trace, vl.pow, vl.elem_stride, powed_out, status, workspace, st, 1, T);
-    else
-        rc = run_path(ctx, CHAIN_POW_FIXED, sig, nullptr, n, nullptr, 0, 0, &eb, 1, batch, flags, T, trace, vl.elem_stride,
-                      vl.pow.off_records, &vl.pow, powed_out, status, workspace, st);
-    if (rc || batch == 0) return rc;
-    return launch_verify_aux(ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status, st);
-} H2R_CATCH_STATUS
-
-// RSAPubE::Var arm of the same call (src/chip.rs:108-110: pow_mod with the chip's exp_limb_bits)
-int32_t h2r_verify_layout_var(const h2r_ctx *ctx, uint32_t e_num_limbs, uint32_t exp_limb_bits, h2r_verify_layout *out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    if (ctx->layout.limb_width != 64 || ctx->L < 9) return H2R_E_SHAPE;
-    std::memset(out, 0, sizeof *out);
-    int32_t rc = h2r_pow_var_layout(ctx, e_num_limbs, exp_limb_bits, &out->pow);
-    if (rc) return rc;
-    const AuxGeom g(ctx->L, 64);
-    out->off_in_field = out->pow.elem_stride;
-    u64 sb = 0;
-    in_field_sections(g, [&](u64, u64 len) { sb += len; });
-    out->in_field_stream_bytes = sb;
-    out->off_em = out->off_in_field + round_up(g.in_field_sz(), 256);
-    out->em_stream_bytes = 2ull * ctx->L + 34;
-    out->elem_stride = odd_stride_256(out->off_em + g.em_sz());
-    out->stream_bytes = out->in_field_stream_bytes + out->pow.stream_bytes + out->em_stream_bytes;
-    return H2R_OK;
-} H2R_CATCH_STATUS
-
-int32_t h2r_verify_pkcs1v15_var_batch(const h2r_ctx *ctx, const void *sig, const void *n, const void *e_limbs, uint32_t e_num_limbs,
-                                      uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace,
-                                      void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!ctx || !sig || !n || !e_limbs || !hashed || !trace || !powed_out || !status) return H2R_E_NULL;
-    h2r_verify_layout vl;
-    int32_t rc = h2r_verify_layout_var(ctx, e_num_limbs, exp_limb_bits, &vl);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = run_path(ctx, CHAIN_POW_VAR, sig, nullptr, n, e_limbs, e_num_limbs, exp_limb_bits, nullptr, 1, batch, flags, vl.pow.num_mul_mods, trace,
-                  vl.elem_stride, vl.pow.off_records, &vl.pow, powed_out, status, workspace, st);
-    if (rc || batch == 0) return rc;
-    return launch_verify_aux(ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status, st);
-} H2R_CATCH_STATUS
-
-int32_t h2r_verify_trace_flatten(const h2r_ctx *ctx, const h2r_verify_layout *vl, const void *elem_host, void *stream_out) try {
-    if (!ctx || !vl || !elem_host || !stream_out) return H2R_E_NULL;
-    if (vl->pow.off_records == UINT64_MAX) return H2R_E_SHAPE;   // h2r_verify_layout_compact: no records to flatten
-    const u8 *e = static_cast<const u8 *>(elem_host);
-    u8 *o = static_cast<u8 *>(stream_out);
-    const AuxGeom g(ctx->L, ctx->layout.limb_width);
-    in_field_sections(g, [&](u64 off, u64 len) { std::memcpy(o, e + vl->off_in_field + off, len); o += len; });
-    int32_t rc = h2r_pow_trace_flatten(ctx, &vl->pow, e, o);
-    if (rc) return rc;
-    o += vl->pow.stream_bytes;
-    std::memcpy(o, e + vl->off_em, vl->em_stream_bytes); o += vl->em_stream_bytes;
-    if ((u64)(o - static_cast<u8 *>(stream_out)) != vl->stream_bytes) return H2R_E_SHAPE;
-    return H2R_OK;
-} H2R_CATCH_STATUS
-
-// ---- the caller of the path: RSASignatureVerifier::verify_pkcs1v15_signature (src/lib.rs:183-246) ---------------------
-// SHA-256 of every element's message, the reversed digest packed into the four hashed-message limbs (:213-239), and -- in
-// h2r_signature_verifier_batch -- RSAChip::verify_pkcs1v15_signature on them, all in stream order on the caller's stream.
-int32_t h2r_sha256_hashed_msg_batch(const h2r_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t fixed_len, uint64_t batch,
-                                    uint8_t *digest_out, uint64_t *hashed_out, void *hm_trace, uint64_t hm_stride, h2r_stream_t stream) try {
-    if (!ctx || (!msgs && (msg_off || fixed_len))) return H2R_E_NULL;
-    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
-    if (hm_trace && hm_stride == 0) hm_stride = HM_REGION;
-    if ((reinterpret_cast<u64>(digest_out) | reinterpret_cast<u64>(hashed_out) | reinterpret_cast<u64>(hm_trace) | hm_stride) & 15) return H2R_E_SHAPE;
-    if (hm_trace && hm_stride < HM_REGION) return H2R_E_SHAPE;
-    if (batch == 0) return H2R_OK;
-    if (batch >= (1ull << 37)) return H2R_E_UNSUPPORTED;
-    H2R_ON_DEVICE(ctx->params.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    Sha256Args sa;
-    sa.msgs = msgs; sa.off = msg_off; sa.fixed_len = fixed_len; sa.batch = batch;
-    sa.digest = digest_out; sa.hashed = hashed_out; sa.region = static_cast<u8 *>(hm_trace); sa.region_stride = hm_stride;
-    sa.done = nullptr; sa.target = 0;
-    ProfScope ps(H2R_KERNEL_SHA256, st, true);
-    hipExtLaunchKernelGGL(sha256_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, sa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
-} H2R_CATCH_STATUS
-
-int32_t h2r_signature_verifier_batch(const h2r_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t fixed_len, const void *sig,
-                                     const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch, uint32_t flags, void *trace,
-                                     void *hm_trace, uint64_t hm_stride, uint8_t *digest_out, uint64_t *hashed_out, void *powed_out,
-                                     uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!hashed_out) return H2R_E_NULL;
-    if (ctx && (ctx->layout.limb_width != 64 || ctx->L < 9)) return H2R_E_SHAPE;   // before any launch: RSAChip::LIMB_WIDTH
-    const int32_t rc = h2r_sha256_hashed_msg_batch(ctx, msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, stream);
-    if (rc) return rc;
-    return h2r_verify_pkcs1v15_batch(ctx, sig, n, e_le, e_len, hashed_out, batch, flags, trace, powed_out, is_valid_out, status, workspace, stream);
-} H2R_CATCH_STATUS
 
 struct h2r_pipeline {
     const h2r_ctx *ctx;
@@ -1049,16 +929,6 @@ void arena_free_region(h2r_arena::Region &r) {
     if (r.va) (void)hipMemAddressFree(r.va, r.mapped);
     r.va = nullptr; r.handles.clear(); r.n_mapped = 0;
 }
-}  // namespace
-
-int32_t h2r_arena_create(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t first_record_off, uint32_t records_per_elem,
-                         uint64_t batch, uint32_t regions, uint32_t candidates, h2r_stream_t stream, h2r_arena **out) try {
-    return h2r_arena_create_ex(ctx, elem_stride, first_record_off, records_per_elem, batch, regions, candidates, 0, stream, out);
-} H2R_CATCH_STATUS
-
-// max_look_bytes != 0: an upper bound on the device memory the look may hold at any time BESIDES the kept regions (rejected
-// candidates kept so that the next one lands elsewhere; the placeholder rounds are skipped) -- a service that shares the device
-namespace {
 // a streaming fill in the product kernels' store pattern (16 bytes per lane, non-temporal, whole 4 KB runs per workgroup step,
 // XCD-contiguous blocks): what h2r_image_arena_create times on a candidate region
 __global__ __launch_bounds__(256) void arena_fill_kernel(u8 *p, u64 bytes) {
@@ -1069,84 +939,6 @@ __global__ __launch_bounds__(256) void arena_fill_kernel(u8 *p, u64 bytes) {
     for (u64 o = (u64)threadIdx.x * 16; o + 16 <= n; o += 4096) st16(q + o, 0x0123456789abcdefull ^ o, b);
 }
 using ArenaMeasure = std::function<int32_t(void *va, hipStream_t st, hipEvent_t ea, hipEvent_t eb, float *ms)>;
-int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes, hipStream_t st,
-                    const ArenaMeasure &measure, bool plain, h2r_arena **out);
-}  // namespace
-
-int32_t h2r_arena_create_ex(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t first_record_off, uint32_t records_per_elem,
-                            uint64_t batch, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes, h2r_stream_t stream,
-                            h2r_arena **out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    *out = nullptr;
-    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
-    const h2r_layout &lo = ctx->layout;
-    if (!regions || candidates < regions || !batch || !records_per_elem ||
-        elem_stride < first_record_off + (u64)records_per_elem * lo.record_stride) return H2R_E_SHAPE;
-    if (batch * (u64)records_per_elem >= (1ull << 32)) return H2R_E_UNSUPPORTED;
-    H2R_ON_DEVICE(ctx->params.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // operands of the measurement launches: any values do (the record kernel's store pattern does not depend on them)
-    const u64 n_items = batch * records_per_elem;
-    const u64 ops_bytes = n_items * 4ull * ctx->L * lo.limb_bytes;
-    u8 *scratch = nullptr;
-    HIP_TRY(hipMalloc(&scratch, ops_bytes + batch + 4096));
-    struct ScratchFree { u8 *p; ~ScratchFree() { if (p) (void)hipFree(p); } } scratch_free{scratch};
-    HIP_TRY(hipMemsetAsync(scratch, 0x5a, ops_bytes, st));
-    HIP_TRY(hipMemsetAsync(scratch + ops_bytes, 0, batch + 4096, st));
-    // three launches of the record kernel in the production geometry
-    const ArenaMeasure measure = [&](void *va, hipStream_t s2, hipEvent_t ea, hipEvent_t eb, float *ms_out) -> int32_t {
-        TraceArgs ta;
-        fill_trace_args(ctx, ta);
-        const u64 lb = lo.limb_width / 8;
-        ta.opA = scratch; ta.opB = scratch + ctx->L * lb; ta.opQ = scratch + 2 * ctx->L * lb; ta.opR = scratch + 3 * ctx->L * lb;
-        ta.op_stride = 4ull * ctx->L;
-        ta.n = scratch; ta.n_stride = 0;
-        ta.status = scratch + ops_bytes; ta.n_items = n_items; ta.T = records_per_elem;
-        ta.trace = static_cast<u8 *>(va); ta.elem_stride = elem_stride; ta.off_records = first_record_off;
-        if (knobs().trace_dyn_lds < 0 && lo.limb_width == 64 && ctx->L <= 32) ta.residency = 1;   // the kernel's stand-alone launch shape
-        float sum = 0.f;
-        for (int rep = 0; rep < 3; ++rep) {
-            if (!hip_ok(launch_trace(ctx, ta, s2, ea, eb), "launch_trace")) return H2R_E_HIP;
-            if (!hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
-            float ms = 0.f;
-            if (!hip_ok(hipEventElapsedTime(&ms, ea, eb), "hipEventElapsedTime")) return H2R_E_HIP;
-            if (rep) sum += ms;   // the first launch touches the pages
-        }
-        *ms_out = sum / 2.f;
-        return H2R_OK;
-    };
-    return arena_build(ctx, batch * elem_stride, regions, candidates, max_look_bytes, st, measure, false, out);
-} H2R_CATCH_STATUS
-
-// The same look for ANY large output the kernels stream into -- advice images, the lookup argument's A' / S' columns: where such a
-// buffer lies physically decides its store rate exactly as for the trace (cells_kernel 1.82-2.39 ms, lookup_fill_kernel 5.05-6.73 TB/s
-// by buffer).  The candidates are timed with a streaming fill in the product kernels' store pattern; h2r_arena_region etc. apply.
-int32_t h2r_image_arena_create(const h2r_ctx *ctx, uint64_t region_bytes, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes,
-                               h2r_stream_t stream, h2r_arena **out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    *out = nullptr;
-    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
-    if (!regions || candidates < regions || region_bytes < (1ull << 20) || (region_bytes >> 16) >= (1ull << 31)) return H2R_E_SHAPE;
-    H2R_ON_DEVICE(ctx->params.device);
-    const ArenaMeasure measure = [&](void *va, hipStream_t s2, hipEvent_t ea, hipEvent_t eb, float *ms_out) -> int32_t {
-        const unsigned blocks = (unsigned)((region_bytes + (64ull << 10) - 1) >> 16);
-        float sum = 0.f;
-        for (int rep = 0; rep < 3; ++rep) {
-            hipExtLaunchKernelGGL(arena_fill_kernel, dim3(blocks), dim3(256), 0, s2, ea, eb, 0, static_cast<u8 *>(va), region_bytes);
-            if (!hip_ok(hipGetLastError(), "arena_fill_kernel") || !hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
-            float ms = 0.f;
-            if (!hip_ok(hipEventElapsedTime(&ms, ea, eb), "hipEventElapsedTime")) return H2R_E_HIP;
-            if (rep) sum += ms;
-        }
-        *ms_out = sum / 2.f;
-        return H2R_OK;
-    };
-    // (plain hipMalloc candidates: regions stitched from physical chunks with the virtual-memory API aborted inside the runtime now and then
-    //  under this look -- "Memobj map does not have ptr", tools/image_arena_probe.py -- and a streaming buffer has no use for the stitching)
-    return arena_build(ctx, region_bytes, regions, candidates, max_look_bytes, static_cast<hipStream_t>(stream), measure, true, out);
-} H2R_CATCH_STATUS
-
-namespace {
 int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes, hipStream_t st,
                     const ArenaMeasure &measure, bool plain, h2r_arena **out) {
     hipMemAllocationProp prop = {};
@@ -1276,6 +1068,86 @@ int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint
 }
 }  // namespace
 
+int32_t h2r_arena_create(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t first_record_off, uint32_t records_per_elem,
+                         uint64_t batch, uint32_t regions, uint32_t candidates, h2r_stream_t stream, h2r_arena **out) try {
+    return h2r_arena_create_ex(ctx, elem_stride, first_record_off, records_per_elem, batch, regions, candidates, 0, stream, out);
+} H2R_CATCH_STATUS
+
+// max_look_bytes != 0: an upper bound on the device memory the look may hold at any time BESIDES the kept regions (rejected
+// candidates kept so that the next one lands elsewhere; the placeholder rounds are skipped) -- a service that shares the device
+int32_t h2r_arena_create_ex(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t first_record_off, uint32_t records_per_elem,
+                            uint64_t batch, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes, h2r_stream_t stream,
+                            h2r_arena **out) try {
+    if (!ctx || !out) return H2R_E_NULL;
+    *out = nullptr;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    const h2r_layout &lo = ctx->layout;
+    if (!regions || candidates < regions || !batch || !records_per_elem ||
+        elem_stride < first_record_off + (u64)records_per_elem * lo.record_stride) return H2R_E_SHAPE;
+    if (batch * (u64)records_per_elem >= (1ull << 32)) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // operands of the measurement launches: any values do (the record kernel's store pattern does not depend on them)
+    const u64 n_items = batch * records_per_elem;
+    const u64 ops_bytes = n_items * 4ull * ctx->L * lo.limb_bytes;
+    u8 *scratch = nullptr;
+    HIP_TRY(hipMalloc(&scratch, ops_bytes + batch + 4096));
+    struct ScratchFree { u8 *p; ~ScratchFree() { if (p) (void)hipFree(p); } } scratch_free{scratch};
+    HIP_TRY(hipMemsetAsync(scratch, 0x5a, ops_bytes, st));
+    HIP_TRY(hipMemsetAsync(scratch + ops_bytes, 0, batch + 4096, st));
+    // three launches of the record kernel in the production geometry
+    const ArenaMeasure measure = [&](void *va, hipStream_t s2, hipEvent_t ea, hipEvent_t eb, float *ms_out) -> int32_t {
+        TraceArgs ta;
+        fill_trace_args(ctx, ta);
+        const u64 lb = lo.limb_width / 8;
+        ta.opA = scratch; ta.opB = scratch + ctx->L * lb; ta.opQ = scratch + 2 * ctx->L * lb; ta.opR = scratch + 3 * ctx->L * lb;
+        ta.op_stride = 4ull * ctx->L;
+        ta.n = scratch; ta.n_stride = 0;
+        ta.status = scratch + ops_bytes; ta.n_items = n_items; ta.T = records_per_elem;
+        ta.trace = static_cast<u8 *>(va); ta.elem_stride = elem_stride; ta.off_records = first_record_off;
+        if (knobs().trace_dyn_lds < 0 && lo.limb_width == 64 && ctx->L <= 32) ta.residency = 1;   // the kernel's stand-alone launch shape
+        float sum = 0.f;
+        for (int rep = 0; rep < 3; ++rep) {
+            if (!hip_ok(launch_trace(ctx, ta, s2, ea, eb), "launch_trace")) return H2R_E_HIP;
+            if (!hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
+            float ms = 0.f;
+            if (!hip_ok(hipEventElapsedTime(&ms, ea, eb), "hipEventElapsedTime")) return H2R_E_HIP;
+            if (rep) sum += ms;   // the first launch touches the pages
+        }
+        *ms_out = sum / 2.f;
+        return H2R_OK;
+    };
+    return arena_build(ctx, batch * elem_stride, regions, candidates, max_look_bytes, st, measure, false, out);
+} H2R_CATCH_STATUS
+
+// The same look for ANY large output the kernels stream into -- advice images, the lookup argument's A' / S' columns: where such a
+// buffer lies physically decides its store rate exactly as for the trace (cells_kernel 1.82-2.39 ms, lookup_fill_kernel 5.05-6.73 TB/s
+// by buffer).  The candidates are timed with a streaming fill in the product kernels' store pattern; h2r_arena_region etc. apply.
+int32_t h2r_image_arena_create(const h2r_ctx *ctx, uint64_t region_bytes, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes,
+                               h2r_stream_t stream, h2r_arena **out) try {
+    if (!ctx || !out) return H2R_E_NULL;
+    *out = nullptr;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (!regions || candidates < regions || region_bytes < (1ull << 20) || (region_bytes >> 16) >= (1ull << 31)) return H2R_E_SHAPE;
+    H2R_ON_DEVICE(ctx->params.device);
+    const ArenaMeasure measure = [&](void *va, hipStream_t s2, hipEvent_t ea, hipEvent_t eb, float *ms_out) -> int32_t {
+        const unsigned blocks = (unsigned)((region_bytes + (64ull << 10) - 1) >> 16);
+        float sum = 0.f;
+        for (int rep = 0; rep < 3; ++rep) {
+            hipExtLaunchKernelGGL(arena_fill_kernel, dim3(blocks), dim3(256), 0, s2, ea, eb, 0, static_cast<u8 *>(va), region_bytes);
+            if (!hip_ok(hipGetLastError(), "arena_fill_kernel") || !hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
+            float ms = 0.f;
+            if (!hip_ok(hipEventElapsedTime(&ms, ea, eb), "hipEventElapsedTime")) return H2R_E_HIP;
+            if (rep) sum += ms;
+        }
+        *ms_out = sum / 2.f;
+        return H2R_OK;
+    };
+    // (plain hipMalloc candidates: regions stitched from physical chunks with the virtual-memory API aborted inside the runtime now and then
+    //  under this look -- "Memobj map does not have ptr", tools/image_arena_probe.py -- and a streaming buffer has no use for the stitching)
+    return arena_build(ctx, region_bytes, regions, candidates, max_look_bytes, static_cast<hipStream_t>(stream), measure, true, out);
+} H2R_CATCH_STATUS
+
 void *h2r_arena_region(const h2r_arena *a, uint32_t i) try { return (a && i < a->kept.size()) ? a->kept[i].va : nullptr; } catch (...) { return nullptr; }
 uint64_t h2r_arena_region_bytes(const h2r_arena *a) try { return a ? a->region_bytes : 0; } H2R_CATCH_ZERO
 double h2r_arena_region_ms(const h2r_arena *a, uint32_t i) try { return (a && i < a->kept.size()) ? (double)a->kept[i].ms : 0.0; } catch (...) { return 0.0; }
@@ -1294,6 +1166,15 @@ void h2r_arena_destroy(h2r_arena *a) try {
     delete a;
 } H2R_CATCH_VOID
 
+// ---- the pow path and the pipeline that overlaps its calls: helpers first, then the exports ---------------------------------
+namespace {
+__global__ void queue_probe_kernel(unsigned long long ticks, unsigned long long *stamp) {   // one wave that holds its queue for `ticks` of the 100 MHz wall clock
+    const unsigned long long t0 = wall_clock64();
+    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
+    if (stamp && threadIdx.x == 0) { stamp[0] = t0; stamp[1] = wall_clock64(); }   // when it ran, on the device's own clock
+}
+}  // namespace
+extern "C++" {
 namespace {
 // Which calls are issued as one-launch steps: the shape both roles of step_kernel are built for (RSA-2048: 64-bit limbs,
 // 32 limbs -- 64-digit chains on four waves, record workgroups of 256 threads), at batches the throughput chain build serves.
@@ -1343,18 +1224,7 @@ int32_t pipeline_flush(h2r_pipeline *p, hipStream_t st) {
     }
     return H2R_OK;
 }
-}  // namespace
 
-int32_t h2r_pipeline_create(const h2r_ctx *ctx, h2r_pipeline **out) try { return h2r_pipeline_create_ex(ctx, 2, 1, out); } H2R_CATCH_STATUS
-
-namespace {
-__global__ void queue_probe_kernel(unsigned long long ticks, unsigned long long *stamp) {   // one wave that holds its queue for `ticks` of the 100 MHz wall clock
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-    if (stamp && threadIdx.x == 0) { stamp[0] = t0; stamp[1] = wall_clock64(); }   // when it ran, on the device's own clock
-}
-}  // namespace
-namespace {
 // force: measure again although `st` has a cached verdict (h2r_pipeline_info: the caller's way to refresh it after streams were created or
 // destroyed -- HIP may have re-assigned queues, and a destroyed stream's handle can come back for a new stream)
 bool pipeline_three_queues(h2r_pipeline *p, hipStream_t st, bool force = false) {
@@ -1407,7 +1277,532 @@ bool pipeline_three_queues(h2r_pipeline *p, hipStream_t st, bool force = false) 
     p->queue_probe[st] = three;
     return three != 0;
 }
+
+// Order `st` after the record kernel of the call in `slot`.
+int32_t pipeline_wait_slot(h2r_pipeline *p, u32 slot, hipStream_t st) {
+    DoneRef &d = p->done[slot];
+    if (!d.ev) return H2R_OK;   // that call launched no record kernel
+    if (!d.alive()) {
+        // the profiler's events were released in between: fall back to the tail of that record stream, which is
+        // behind the kernel in question (over-synchronises, never under-synchronises)
+        HIP_TRY(hipEventRecord(p->trace_done[slot], p->done_stream[slot]));
+        d = DoneRef{p->trace_done[slot], 0, false};
+    }
+    HIP_TRY(hipStreamWaitEvent(st, d.ev, 0));
+    return H2R_OK;
+}
+// lazy join: the NEXT call reuses the buffers of call k - depth, so order the user stream after that call's record kernel
+// now -- behind this call's chain kernel, which therefore overlaps the record kernels in flight
+int32_t pipeline_lazy_join(h2r_pipeline *p, hipStream_t st) {
+    for (; p->joined + p->depth <= p->k; ++p->joined) {
+        const int32_t rc = pipeline_wait_slot(p, p->joined % p->depth, st);
+        if (rc) return rc;
+    }
+    return H2R_OK;
+}
+// The end of every pipelined call: the call counts as issued, then `after_chain` (nullable) on the caller's stream, then the lazy join.
+int32_t pipeline_finish_call(h2r_pipeline *p, u32 slot, hipStream_t done_stream, hipStream_t st, const std::function<int32_t()> &after_chain) {
+    p->done_stream[slot] = done_stream;
+    p->k += 1;
+    if (after_chain) {
+        const int32_t rc = after_chain();
+        if (rc) return rc;
+    }
+    return pipeline_lazy_join(p, st);
+}
+// Is the record kernel of the previous pipelined call still queued or running?
+bool pipeline_busy(h2r_pipeline *p) {
+    if (p->pending) return true;
+    if (p->k == 0) return false;
+    const DoneRef &d = p->done[(p->k - 1) % p->depth];
+    if (!d.ev || !d.alive()) return false;
+    return hipEventQuery(d.ev) == hipErrorNotReady;
+}
+
+// Does a plain (non-pipelined) pow call of this size gain from being walked as overlapping sub-batches?  The shapes and
+// sizes call_plan splits for an empty pipeline.
+bool plain_call_overlaps(const h2r_ctx *c, u64 batch) {
+    if (knobs().plain_overlap == 0) return false;
+    const u64 unit = (u64)c->num_cus * (c->K > 64 ? 2 : 4);
+    if (c->layout.limb_width != 64) return false;
+    if (c->L > 32) return batch > 3 * unit;
+    return c->L > 16 && batch > unit + unit / 2;
+}
+
+// How one pipelined call is walked: the sizes of its sub-batches (each gets its own chain and record kernel) and whether
+// sub-batch i+1's chain kernel is held back until sub-batch i's record kernel starts.  What is at stake is the start and
+// the end of a call, not its steady state: an unsplit call exposes its whole chain kernel when no record kernel is in flight
+// (0.94 ms for 8,192 RSA-2048 signatures against 1.77 ms of record kernel), while at steady state one large launch per call
+// is the fastest form (fewer kernel boundaries: 1.77-1.81 ms per 8,192 against 1.93 as eight launches).  Measured per shape
+// (tools/sub_batch_ab.sh, profiles/r02_sub_batches.txt):
+//  * record-bound shapes (64-bit limbs, RSA-1536/2048): a call that finds the pipeline EMPTY is walked as sub-batches growing
+//    by 3/2 from one chain-kernel grid (1024, 1536, 2304, ...): each chain kernel then fits next to the record kernel of the
+//    sub-batch before it; paced (an unpaced train of chain kernels slows the record kernels it overlaps by 5 %).  A call
+//    that finds a record kernel in flight is not split.
+//  * chain-bound shapes (RSA-3072: chain kernel 0.65 ms, record kernel 0.49 ms per 1,024): uniform sub-batches, unpaced --
+//    the chain kernels run back to back either way, the record kernels hide behind them, and the last record kernel of a
+//    call is a quarter as long (4,096 signatures: 1.39-1.44 -> 1.60-1.62 M assigns/s over six calls).
+//  * RSA-1024 and the 32-bit-limb shapes: no gain measured from any split; one launch.
+// (busy: a record kernel of the previous call is still queued or running)
+void call_plan(const h2r_ctx *c, u64 batch, bool busy, std::vector<u64> &sizes, bool &pace) {
+    sizes.clear(); pace = false;
+    const u64 unit = (u64)c->num_cus * (c->K > 64 ? 2 : 4);   // one chain-kernel grid: four 4-wave (two 8-wave) workgroups per CU
+    if (knobs().pipe_sub_batch > 0) {
+        pace = knobs().pipe_pace != 0;
+        for (u64 o = 0; o < batch; o += (u64)knobs().pipe_sub_batch) sizes.push_back(std::min<u64>((u64)knobs().pipe_sub_batch, batch - o));
+        if (sizes.empty()) sizes.push_back(batch);
+        return;
+    }
+    const bool w64 = c->layout.limb_width == 64;
+    if (w64 && c->L > 32 && batch > 3 * unit) {                         // chain-bound (RSA-3072, RSA-4096 at 64-bit limbs)
+        for (u64 o = 0; o < batch; o += 2 * unit) sizes.push_back(std::min<u64>(2 * unit, batch - o));
+        return;
+    }
+    if (w64 && c->L > 16 && c->L <= 32 && batch > unit + unit / 2 && !busy) {   // record-bound, pipeline empty
+        pace = true;
+        u64 cur = unit, left = batch;
+        while (left) {
+            u64 take = std::min(cur, left);
+            if (left - take < cur / 2) take = left;
+            sizes.push_back(take); left -= take;
+            cur = (cur * 3 / 2) & ~255ull;
+        }
+        return;
+    }
+    sizes.push_back(batch);
+}
+// A LONG exponent on a latency-bound batch (at most two elements per CU: every chain's own length is what the call waits for --
+// BASELINE config 5: 256 elements x 3,072 dependent mul_mods, 7-8.5 ms of chain and 7.9 ms of record kernel) is walked as SEGMENTS of
+// its bits: the chain kernel of bits [lo, hi) of every element, then -- on the record stream -- the record kernel of those bits'
+// mul_mods, next to the chain kernel of the following segment.  A call's records then trail its own chains by one segment instead of
+// by the whole chain: a single call drops from chain + records to chain + 1/S records, and a train of pipelined calls loses the
+// exposed first chain / last record kernel.  Same values, same buffers; the (squared, acc) pair crosses launches in the workspace.
+u32 exp_segment_count(const h2r_ctx *c, u64 batch, u32 nbits, bool has_trace, bool single_call = false) {
+    if (!has_trace || batch == 0) return 1;
+    // single_call: a stream-ordered export that neither follows nor is followed by another call's kernels.  EXPERIMENT, off in the
+    // product (the knob's default): the same cut for a SHORT exponent (e = 65537: 19 mul_mods) on a batch that fills the chip but is
+    // too small to be walked as sub-batches of elements -- measured +2 % with two segments at 1,024 RSA-2048 elements and a loss
+    // everywhere else (a 9-mul_mod chain kernel is latency-bound, every segment adds a cross-queue wait): profiles/r03_exp_segments.txt
+    if (single_call && nbits >= 8 && nbits < 512 && c->layout.limb_width == 64 && c->L == 32 && batch > 512 && !plain_call_overlaps(c, batch)) {
+        const long k = knobs().single_call_segments;
+        return k >= 0 ? (u32)std::max<long>(1, std::min<long>(k, nbits / 2)) : 1;
+    }
+    if (batch > 2ull * c->num_cus || nbits < 512) return 1;
+    if (knobs().exp_segments >= 0) return knobs().exp_segments > 1 ? (u32)std::min<long>(knobs().exp_segments, nbits / 32) : 1;
+    // measured (tools/exp_segments_ab.sh, config 5, same box, 1 / 2 / 4 / 8 / 16 / 32 segments): pipelined 26.2 / 28.1 / 29.3 / 30.5 / 30.3 / 29.3 k
+    // assigns/s, single calls 17.4 / 21.4 / 25.2 / 27.4 / 28.7 / 27.6 k
+    return std::min<u32>(16, nbits / 128);   // >= 128 bits (128-256 mul_mods per element, ~0.5 ms of chain) per segment
+}
+// The segments themselves: equal parts of the exponent's bits (long exponents: boundaries on 32-bit words of e) with the mul_mods each covers
+// -- one squaring per bit plus one multiply per set bit of a fixed exponent `eb`, two per bit of a variable one (eb == nullptr).
+void exp_segment_plan(u32 n_seg, u32 nbits, const ExpBits *eb, std::vector<ExpSegment> &out) {
+    out.clear();
+    const u32 word = nbits >= 512 ? ~31u : ~0u;
+    u32 t_lo = 0;
+    for (u32 sgi = 0; sgi < n_seg; ++sgi) {
+        ExpSegment sg;
+        sg.bit_lo = (u32)((u64)nbits * sgi / n_seg) & word;
+        sg.bit_hi = sgi + 1 == n_seg ? nbits : (u32)((u64)nbits * (sgi + 1) / n_seg) & word;
+        sg.t_lo = t_lo; sg.t_cnt = 0;
+        for (u32 bi = sg.bit_lo; bi < sg.bit_hi; ++bi) sg.t_cnt += eb ? 1u + ((eb->words[bi >> 5] >> (bi & 31)) & 1u) : 2u;
+        t_lo += sg.t_cnt;
+        out.push_back(sg);
+    }
+}
+
+AuxArgs verify_aux_args(const h2r_ctx *ctx, const void *sig, const void *n, const uint64_t *hashed, uint64_t batch, uint32_t flags,
+                        void *trace, const h2r_verify_layout &vl, void *powed_out, uint8_t *is_valid_out, uint8_t *status) {
+    AuxArgs aa;
+    std::memset(&aa, 0, sizeof aa);
+    aa.x = sig; aa.n = n; aa.n_stride = shared(flags) ? 0 : ctx->L;
+    aa.hashed = hashed; aa.powed = powed_out; aa.batch = batch; aa.L = ctx->L;
+    aa.trace = static_cast<u8 *>(trace); aa.elem_stride = vl.elem_stride; aa.off_in_field = vl.off_in_field; aa.off_em = vl.off_em;
+    aa.is_valid = is_valid_out; aa.status = status;
+    return aa;
+}
+
+int32_t launch_verify_aux(const h2r_ctx *ctx, const AuxArgs &aa, hipStream_t st) {
+    ProfScope ps(H2R_KERNEL_AUX, st, true);   // dispatch-stamped events: no marker packets on the caller's stream
+    const AuxGeom ag(ctx->L, 64);
+    hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)aa.batch), dim3(64), (unsigned)(ag.in_field_sz() + ag.em_sz()), st, ps.a, ps.b, 0, aa);
+    HIP_TRY(hipGetLastError());
+    return H2R_OK;
+}
+
+// The assert_in_field(x, n) witness alone (src/chip.rs:106), one element every h2r_fresh_op_layout(IS_IN_FIELD) stride.
+int32_t in_field_args(const h2r_ctx *ctx, const void *x, const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, AuxArgs *aa, u32 *lds) {
+    u64 es = 0;
+    const int32_t rc = h2r_fresh_op_layout(ctx, FRESH_IS_IN_FIELD, &es, nullptr, nullptr);
+    if (rc) return rc;
+    std::memset(aa, 0, sizeof *aa);
+    aa->x = x; aa->n = n; aa->n_stride = shared(flags) ? 0 : ctx->L;
+    aa->batch = batch; aa->L = ctx->L;
+    aa->trace = static_cast<u8 *>(in_field_trace); aa->elem_stride = es; aa->off_in_field = 0;
+    const AuxGeom ag(ctx->L, ctx->layout.limb_width);
+    *lds = (u32)(ag.in_field_sz() + ag.em_sz());
+    return H2R_OK;
+}
+int32_t launch_in_field(const h2r_ctx *ctx, const void *x, const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, hipStream_t st) {
+    if (batch == 0) return H2R_OK;
+    AuxArgs aa; u32 lds = 0;
+    const int32_t rc = in_field_args(ctx, x, n, batch, flags, in_field_trace, &aa, &lds);
+    if (rc) return rc;
+    H2R_ON_DEVICE(ctx->params.device);
+    ProfScope ps(H2R_KERNEL_AUX, st, true);
+    if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
+    else hipExtLaunchKernelGGL((aux_kernel<32>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
+    HIP_TRY(hipGetLastError());
+    return H2R_OK;
+}
+
+// The SHA-256 / hashed-message step: the checks of its buffers (hm_stride == 0: HM_REGION) and its kernel's arguments.
+int32_t sha_args(const uint8_t *msgs, const uint64_t *msg_off, uint64_t fixed_len, uint64_t batch, uint8_t *digest_out, uint64_t *hashed_out,
+                 void *hm_trace, uint64_t hm_stride, Sha256Args *sa) {
+    if (hm_trace && hm_stride == 0) hm_stride = HM_REGION;
+    if ((reinterpret_cast<u64>(digest_out) | reinterpret_cast<u64>(hashed_out) | reinterpret_cast<u64>(hm_trace) | hm_stride) & 15) return H2R_E_SHAPE;
+    if (hm_trace && hm_stride < HM_REGION) return H2R_E_SHAPE;
+    sa->msgs = msgs; sa->off = msg_off; sa->fixed_len = fixed_len; sa->batch = batch;
+    sa->digest = digest_out; sa->hashed = hashed_out; sa->region = static_cast<u8 *>(hm_trace); sa->region_stride = hm_stride;
+    sa->done = nullptr; sa->target = 0;
+    return H2R_OK;
+}
+int32_t launch_sha(const Sha256Args &sa, hipStream_t st) {
+    ProfScope ps(H2R_KERNEL_SHA256, st, true);
+    hipExtLaunchKernelGGL(sha256_kernel, dim3((unsigned)((sa.batch + 63) / 64)), dim3(64), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, sa);
+    HIP_TRY(hipGetLastError());
+    return H2R_OK;
+}
+
+// What rides along with the chains and records of a pipelined call (all nullable).
+struct PipeRoles {
+    std::function<int32_t()> after_chain;   // e.g. the verifier's aux kernel: on the caller's stream behind the call's chain kernels
+    // what `after_chain` would launch, when that is a kernel whose output belongs to the call's TRACE (the assert_in_field witness):
+    // a call issued as one-launch steps writes it together with its records
+    const AuxArgs *witness_aux = nullptr; u32 witness_aux_lds = 0;
+    // the verifier's in-field + encoded-message witness of the whole call (what `after_chain` launches as a kernel): when every
+    // sub-batch of the call goes out as a step launch, the chain role writes it element by element instead
+    const AuxArgs *verify_aux = nullptr;
+    // the SHA-256 / hashed-message step of RSASignatureVerifier for THIS call's messages; `after_chain` consumes its output.  It
+    // rides on the call's first step launch when there is one, and is a kernel of its own on the caller's stream otherwise.
+    const Sha256Args *sha = nullptr;
+    bool assume_empty = false;              // a single stream-ordered call (overlapped_pow_fixed): nothing of another call is in flight
+};
+
+// How one pipelined call goes out.  pipeline_form() says which of the three forms; pipeline_plan() its parts -- after the records
+// another form still owes have been flushed, because both the step sizes and the busy query look at what is pending then.
+struct PipePlan {
+    bool as_steps = false;         // every sub-batch one step launch: its chains + the records of the sub-batch before it
+    bool overlap_records = false;  // the two-queue form
+    u32 n_seg_single = 1;          // exponent segments of a single stream-ordered call (an experiment: exp_segment_count)
+    u32 n_seg = 1;                 // > 1: the whole call as segments of its exponent's bits
+    std::vector<u64> sizes;        // else: sub-batches of these sizes ...
+    bool pace = false;             // ... sub-batch i + 1's chain kernel held back until sub-batch i's record kernel starts
+};
+PipePlan pipeline_form(h2r_pipeline *p, const PowCall &call, hipStream_t st, bool assume_empty) {
+    const h2r_ctx *ctx = p->ctx;
+    PipePlan plan;
+    plan.n_seg_single = assume_empty ? exp_segment_count(ctx, call.batch, call.e.nbits(), call.trace && call.T, /*single_call=*/true) : 1;
+    // RSA-2048 on a pipeline created with TWO side streams and three or more buffer sets: the two-queue form -- chain kernels on the caller's
+    // stream, record kernels alternating between the side streams, so that call k + 1's record kernel starts while call k's tail drains --
+    // beats the one-launch step (same box, alternating: 5.41 / 5.41 M assigns/s against 5.18 / 5.32 M at 1,024 per call, 5.55-5.58 against
+    // 5.50-5.51 M at 2,048).  The other step shapes were chain-bound enough to lose that way in round 4 (RSA-1024 with its four-wave chain 9.4
+    // against 12.4 M, RSA-3072 2.1 against 2.5 M, RSA-4096 1.2 against 1.5 M; 128 x 32-bit limbs: the same): tools/two_queue_ab.sh,
+    // profiles/r04_two_queue.txt.  [r6] RSA-1024 with the one-wave chain wins from 1,280 per call (two_queue_shape).
+    // (calls of up to 2,048: at 4,096 per call one launch has little boundary left to hide and the step is ahead again, 5.37-5.42 against 5.27-5.33 M)
+    // ... provided the three streams sit on three hardware queues, which the pipeline measures once per caller stream (pipeline_three_queues);
+    // with a shared queue the call falls back to the one-launch step
+    plan.overlap_records = two_queue_shape(ctx, call.batch) && p->aux[0] != p->aux[1] && p->depth >= 3 && knobs().pipe_step < 1 &&
+                           pipeline_three_queues(p, st);
+    plan.as_steps = step_eligible(ctx, call.batch, call.trace, call.T) && plan.n_seg_single <= 1 && !plan.overlap_records;
+    return plan;
+}
+// A large call may be walked as sub-batches, each with its own chain and record kernel (call_plan): sub-batch
+// i+1's chain kernel then runs next to sub-batch i's record kernel INSIDE the call, exactly as consecutive calls do.
+void pipeline_plan(h2r_pipeline *p, const PowCall &call, bool assume_empty, PipePlan &plan) {
+    const h2r_ctx *ctx = p->ctx;
+    const u64 batch = call.batch;
+    std::vector<u64> &sizes = plan.sizes;
+    if (plan.as_steps) {
+        // every sub-batch is one launch: its chains together with the records of the sub-batch before it (of this call or of
+        // the previous one).  With records pending the call is not split; a call that starts a train is, so that its first,
+        // exposed chain kernel is short (the sizes an empty pipeline gets)
+        if (p->pending) sizes.push_back(batch); else call_plan(ctx, batch, /*busy=*/false, sizes, plan.pace);
+        std::vector<u64> capped;
+        for (u64 sz : sizes) {
+            const u64 parts = (sz + kStepMax - 1) / kStepMax;
+            const u64 each = round_up((sz + parts - 1) / parts, 256);
+            for (u64 o2 = 0; o2 < sz; o2 += each) capped.push_back(std::min(each, sz - o2));
+        }
+        sizes.swap(capped);
+        return;
+    }
+    const bool may_grow = ctx->layout.limb_width == 64 && ctx->L > 16 && ctx->L <= 32;   // (the busy query is only made where the answer matters)
+    call_plan(ctx, batch, may_grow && !assume_empty && pipeline_busy(p), sizes, plan.pace);
+    if (plan.overlap_records && ctx->L == 16 && batch > 4096 && knobs().pipe_sub_batch <= 0) {
+        // RSA-1024 in the two-queue form: a call above 4,096 as uniform sub-batches of 2,048, unpaced (8,192 per call 15.1 -> 15.6-15.9 M assigns/s,
+        // 16,384 13.9-14.1 -> 14.4-14.5 M; paced or as sub-batches of 4,096 it loses: profiles/r06_two_queue_rsa1024.txt)
+        sizes.clear(); plan.pace = false;
+        for (u64 o2 = 0; o2 < batch; o2 += 2048) sizes.push_back(std::min<u64>(2048, batch - o2));
+    }
+    plan.n_seg = plan.n_seg_single > 1 ? plan.n_seg_single : (sizes.size() == 1 ? exp_segment_count(ctx, batch, call.e.nbits(), call.trace && call.T) : 1);
+}
+
+// Form 1, one-launch steps: the records of the last sub-batch issued are written by the NEXT launch, together with that launch's chains.
+int32_t issue_as_steps(h2r_pipeline *p, const PowCall &call, hipStream_t st, const PipeRoles &roles, const PipePlan &plan, u32 slot) {
+    const h2r_ctx *ctx = p->ctx;
+    const h2r_layout &lo = ctx->layout;
+    const AuxArgs *witness_aux = roles.witness_aux, *verify_aux = roles.verify_aux;
+    const Sha256Args *sha = roles.sha;
+    const Workspace wp = workspace_plan(lo.limb_bytes, ctx->L, call.batch, call.T ? call.T : 1);
+    const bool split = plan.sizes.size() > 1;
+    const bool aux_as_role = witness_aux && witness_aux->batch && roles.witness_aux_lds <= step_shared_bytes(ctx);
+    bool aux_done = false;
+    bool sha_done = !sha || !p->pending;
+    // the verifier's witness inside the chain role: only when the whole call is step launches (a call that starts a train keeps
+    // the kernel behind it) and the roles' LDS holds its staging.  When this very launch's SHA role produces the hashed limbs
+    // the chain role waits for that role's message count (Sha256Args::done / target)
+    const AuxGeom vg(ctx->L, lo.limb_width);
+    // measured per shape (tools/verify_fold_ab.sh, ms per 1,024-signature step, digests / messages): RSA-2048 0.2040 / 0.2079 -> 0.1973 /
+    // 0.1989 with the fold; the chain-bound shapes do not gain -- RSA-1024 0.0975 / 0.1097 -> 0.0988 / 0.1080, RSA-4096 0.6745 / 0.6854 ->
+    // 0.6773 / 0.6795 -- or lose: RSA-3072 0.4195 / 0.4258 -> 0.4381 / 0.4601 (the witness lengthens the role the launch waits for)
+    const bool fold_shape = knobs().verify_fold >= 0 ? knobs().verify_fold != 0 : ctx->L == 32;
+    const bool fold_verify = fold_shape && verify_aux && verify_aux->batch && p->pending && (!sha || p->sha_done_dev) && vg.in_field_sz() + vg.em_sz() <= step_shared_bytes(ctx);
+    u64 off = 0;
+    for (size_t i = 0; i < plan.sizes.size(); off += plan.sizes[i], ++i) {
+        const u64 nb = plan.sizes[i];
+        const PowCall sub = call.slice(ctx, off, nb, split ? &wp : nullptr);
+        PathArgs pa;
+        PowIssue how = PowIssue::on(st);
+        how.trace_st = p->aux[0]; how.args_only = &pa;
+        const int32_t rc = run_path(ctx, sub, how);
+        if (rc) return rc;
+        if (!pa.has_trace) return H2R_E_SHAPE;
+        if (p->pending) {
+            // THIS call's assert_in_field witness rides on the first step launch the call issues: it needs only x and n,
+            // which are therefore read in `stream` order inside the call, like every other input
+            const bool with_aux = aux_as_role && !aux_done;
+            ProfScope ps(H2R_KERNEL_STEP, st, true);
+            AuxArgs va;
+            if (fold_verify) {   // the slice of the call this launch's chains cover
+                va = *verify_aux;
+                va.x = sub.a; va.n = sub.n;
+                va.hashed = verify_aux->hashed + off * 4;
+                va.powed = static_cast<const u8 *>(verify_aux->powed) + off * ((u64)ctx->K * 4);
+                va.batch = nb;
+                va.trace = verify_aux->trace + off * call.elem_stride;
+                va.is_valid = verify_aux->is_valid ? verify_aux->is_valid + off : nullptr;
+                va.status = verify_aux->status + off;
+            }
+            Sha256Args sr;
+            u32 sha_target = p->sha_issued;
+            if (!sha_done) {
+                sr = *sha;
+                if (fold_verify) { sha_target += (u32)sha->batch; sr.done = p->sha_done_dev; sr.target = sha_target; }
+            }
+            HIP_TRY(launch_step(ctx, pa.ca, p->pending_ta, with_aux ? witness_aux : nullptr, fold_verify ? &va : nullptr, sha_done ? nullptr : &sr, st, ps.a, ps.b));
+            p->sha_issued = sha_target;   // (only a launch that went out counts: the device word never runs behind the host's target)
+            aux_done = aux_done || with_aux;
+            sha_done = true;
+        } else {
+            ProfScope ps(H2R_KERNEL_CHAIN, st, true);
+            HIP_TRY(launch_chain(ctx, pa.ca, /*co_running=*/false, st, ps.a, ps.b));
+        }
+        p->pending = true; p->pending_ta = pa.ta; p->pending_st = st;
+    }
+    // `after_chain` only where no launch did its work as a role (a call that starts a train as one chain kernel: the in-field kernel
+    // behind it); the join is for calls issued the two-queue way earlier on
+    static const std::function<int32_t()> nothing;
+    return pipeline_finish_call(p, slot, st, st, (!aux_done && !fold_verify) ? roles.after_chain : nothing);
+}
+
+// Part i of a call whose record kernels run on the call's side stream; the last part's record kernel marks the end of the call.
+PowIssue on_record_stream(h2r_pipeline *p, u32 slot, hipStream_t st, size_t i, bool last, DoneRef *cur) {
+    PowIssue how = PowIssue::on(st);
+    how.trace_st = p->aux[p->k & 1];
+    how.chain_done = p->chain_done[slot];
+    how.trace_done = last ? p->trace_done[slot] : p->sub_done[i & 1];
+    how.done_ref = last ? &p->done[slot] : cur;
+    return how;
+}
+
+// Form 2, a long exponent on a latency-bound batch (exp_segment_count): every segment's records next to the next segment's chains.
+int32_t issue_as_segments(h2r_pipeline *p, const PowCall &call, hipStream_t st, const PipeRoles &roles, const PipePlan &plan, u32 slot) {
+    std::vector<ExpSegment> segs;
+    exp_segment_plan(plan.n_seg, call.e.nbits(), call.e.var() ? nullptr : &call.e.bits, segs);
+    for (u32 sgi = 0; sgi < plan.n_seg; ++sgi) {
+        DoneRef cur{};
+        PowIssue how = on_record_stream(p, slot, st, sgi, sgi + 1 == plan.n_seg, &cur);
+        how.seg = &segs[sgi];
+        const int32_t rc = run_path(p->ctx, call, how);   // (the whole batch every time: PowCall::slice cuts elements, a segment cuts mul_mods)
+        if (rc) return rc;
+    }
+    return pipeline_finish_call(p, slot, p->aux[p->k & 1], st, roles.after_chain);
+}
+
+// Form 3, sub-batches: chain kernels on the caller's stream, each one's record kernel on the call's side stream.
+int32_t issue_as_sub_batches(h2r_pipeline *p, const PowCall &call, hipStream_t st, const PipeRoles &roles, const PipePlan &plan, u32 slot) {
+    const h2r_ctx *ctx = p->ctx;
+    const Workspace wp = workspace_plan(ctx->layout.limb_bytes, ctx->L, call.batch, call.T ? call.T : 1);
+    const bool split = plan.sizes.size() > 1;
+    DoneRef prev{};   // the record kernel of the sub-batch before the current one
+    u64 off = 0;
+    for (size_t i = 0; i < plan.sizes.size(); off += plan.sizes[i], ++i) {
+        DoneRef cur{};
+        const int32_t rc = run_path(ctx, call.slice(ctx, off, plan.sizes[i], split ? &wp : nullptr),
+                                    on_record_stream(p, slot, st, i, i + 1 == plan.sizes.size(), &cur));
+        if (rc) return rc;
+        // paced: as consecutive calls are paced by the lazy join, sub-batch i+1's chain kernel starts with sub-batch
+        // i's record kernel, not earlier
+        if (prev.ev && plan.pace && prev.alive()) HIP_TRY(hipStreamWaitEvent(st, prev.ev, 0));
+        prev = cur;
+    }
+    return pipeline_finish_call(p, slot, p->aux[p->k & 1], st, roles.after_chain);
+}
+
+// One pipelined call: chain kernel (+ `after_chain`, e.g. the verifier's aux kernel) on the caller's stream, the
+// record kernel on a side stream, then the lazy join of the call whose buffers the next call may reuse.
+int32_t pipeline_issue(h2r_pipeline *p, const PowCall &call, hipStream_t st, const PipeRoles &roles) {
+    if (call.e.rc) return call.e.rc;
+    int32_t rc = H2R_OK;
+    const u32 slot = p->k % p->depth;
+    p->done[slot] = DoneRef{};
+    if (knobs().pipe_serialize && p->aux[0] != p->aux[1] && p->k > 0) {   // order this record stream behind the previous record kernel
+        rc = pipeline_wait_slot(p, (p->k - 1) % p->depth, p->aux[p->k & 1]);
+        if (rc) return rc;
+    }
+    PipePlan plan = pipeline_form(p, call, st, roles.assume_empty);
+    if (p->pending && (!plan.as_steps || p->pending_st != st)) {   // the records still owed go out alone, `st` behind them
+        rc = pipeline_flush(p, st);
+        if (rc) return rc;
+    }
+    pipeline_plan(p, call, roles.assume_empty, plan);
+    // no step launch to ride on (two-queue form, or a call that starts a train with a chain kernel): the SHA step as a kernel of its own
+    if ((!plan.as_steps || !p->pending) && roles.sha && roles.sha->batch) {
+        rc = launch_sha(*roles.sha, st);
+        if (rc) return rc;
+    }
+    if (plan.as_steps) return issue_as_steps(p, call, st, roles, plan, slot);
+    if (plan.n_seg > 1) return issue_as_segments(p, call, st, roles, plan, slot);
+    return issue_as_sub_batches(p, call, st, roles, plan, slot);
+}
+
+// A plain stream-ordered call the overlapped way: through the ctx's own pipeline, joined back onto the caller's stream before returning
+// (either arm of the exponent; only the long-exponent walk of per-element exponents comes this way).
+int32_t overlapped_pow_fixed(const h2r_ctx *ctx, PowCall call, hipStream_t st) {
+    H2R_ON_DEVICE(ctx->params.device);
+    std::lock_guard<std::mutex> lk(ctx->pipe_mu);
+    if (!ctx->pipe) {
+        const int32_t rc = h2r_pipeline_create_ex(ctx, 2, 1, &ctx->pipe);
+        if (rc) return rc;
+    }
+    ScratchGuard sg; sg.st = st;
+    if (!call.workspace) {   // freed in stream order behind the join below, i.e. after the record kernels that read it
+        HIP_TRY(hipMallocAsync(&sg.p, workspace_plan(ctx->layout.limb_bytes, ctx->L, call.batch, call.T).total, st));
+        sg.owned = true; call.workspace = sg.p;
+    }
+    PipeRoles roles;
+    roles.assume_empty = true;
+    const int32_t rc = pipeline_issue(ctx->pipe, call, st, roles);
+    const int32_t rj = h2r_pipeline_join(ctx->pipe, st);   // also after a failed issue: whatever was queued is ordered
+    return rc ? rc : rj;
+}
+
+// the buffers every pow export names
+PowCall pow_buffers(const void *x, const void *n, uint64_t batch, uint32_t flags, void *trace, void *out, uint8_t *status, void *workspace) {
+    PowCall call;
+    call.a = x; call.n = n; call.batch = batch; call.flags = flags; call.trace = trace; call.out = out; call.status = status; call.workspace = workspace;
+    return call;
+}
+// One pow call on the caller's stream.  `call` names a, n, check_in_field, batch, flags, trace, out, status and workspace; the exponent's
+// element layout is filled in here.
+int32_t pow_impl(const h2r_ctx *ctx, const Exponent &e, PowCall call, hipStream_t st) {
+    h2r_pow_layout pl;
+    const int32_t rc = pow_layout(ctx, e, &pl);
+    if (rc) return rc;
+    call.pow(e, pl, pl.elem_stride);
+    if (call.trace && call.T && call.a && call.n && call.status && ctx->params.device >= 0) {
+        // a large call with a trace: sub-batches whose chain kernels run next to the previous sub-batch's record kernel (a side
+        // stream of the ctx), joined back onto the caller's stream before returning -- stream-ordered as ever for the caller.
+        // A long exponent on a latency-bound batch: walked as segments of its bits, each segment's records next to the next one's chains.
+        // A fixed exponent goes either way (and asks about segments as a single call); per-element exponents only the second.
+        const bool has_trace = true;
+        const bool overlap = e.var() ? exp_segment_count(ctx, call.batch, e.nbits(), has_trace) > 1
+                                     : plain_call_overlaps(ctx, call.batch) || exp_segment_count(ctx, call.batch, e.nbits(), has_trace, /*single_call=*/true) > 1;
+        if (overlap) return overlapped_pow_fixed(ctx, call, st);
+    }
+    return run_path(ctx, call, PowIssue::on(st));
+}
+// RSAChip::modpow_public_key (src/chip.rs:99-114): assert_in_field witness (:106), then the pow path with the in-field
+// predicate folded into the chain kernel's status.
+int32_t modpow_public_key_impl(const h2r_ctx *ctx, const Exponent &e, PowCall call, void *in_field_trace, hipStream_t st) {
+    call.check_in_field = 1;
+    const int32_t rc = pow_impl(ctx, e, call, st);
+    if (rc || !in_field_trace) return rc;
+    return launch_in_field(ctx, call.a, call.n, call.batch, call.flags, in_field_trace, st);
+}
+
+// RSAChip::verify_pkcs1v15_signature (src/chip.rs:116-200) on the caller's stream: the pow path, then the in-field / encoded-message kernel.
+int32_t verify_impl(const h2r_ctx *ctx, const void *sig, const void *n, const Exponent &e, const uint64_t *hashed, uint64_t batch, uint32_t flags,
+                    void *trace, void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, hipStream_t st) {
+    if (!ctx || !sig || !n || !hashed || !trace || !powed_out || !status) return H2R_E_NULL;
+    h2r_verify_layout vl;
+    int32_t rc = verify_layout(ctx, e, &vl);
+    if (rc) return rc;
+    PowCall call = pow_buffers(sig, n, batch, flags, trace, powed_out, status, workspace);
+    call.check_in_field = 1;
+    call.pow(e, vl.pow, vl.elem_stride);
+    // large call: overlapping sub-batches, as pow_impl -- the fixed arm only (the Var arm is always one chain + one record kernel)
+    if (!e.var() && call.T && ctx->params.device >= 0 && plain_call_overlaps(ctx, batch)) rc = overlapped_pow_fixed(ctx, call, st);
+    else rc = run_path(ctx, call, PowIssue::on(st));
+    if (rc || batch == 0) return rc;
+    return launch_verify_aux(ctx, verify_aux_args(ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status), st);
+}
+
+// The pipelined RSAChip::modpow_public_key.  The in-field witness needs only x and n: its kernel runs on the caller's stream right
+// behind the chain kernel -- or, when the call is issued as one-launch steps, as a role of the launch that writes the call's records.
+int32_t pipeline_modpow_public_key(h2r_pipeline *p, const void *x, const void *n, const Exponent &e, uint64_t batch, uint32_t flags, void *trace,
+                                   void *in_field_trace, void *out, uint8_t *status, void *workspace, hipStream_t st) {
+    if (!p || !trace || !workspace) return H2R_E_NULL;
+    h2r_pow_layout pl;
+    const int32_t rc = pow_layout(p->ctx, e, &pl);
+    if (rc) return rc;
+    PowCall call = pow_buffers(x, n, batch, flags, trace, out, status, workspace);
+    call.check_in_field = 1;
+    call.pow(e, pl, pl.elem_stride);
+    AuxArgs aa; u32 aux_lds = 0;
+    const bool have_aux = in_field_trace && batch && in_field_args(p->ctx, x, n, batch, flags, in_field_trace, &aa, &aux_lds) == H2R_OK;
+    PipeRoles roles;
+    roles.after_chain = [&]() -> int32_t {
+        if (!in_field_trace) return H2R_OK;
+        return launch_in_field(p->ctx, x, n, batch, flags, in_field_trace, st);
+    };
+    if (have_aux) { roles.witness_aux = &aa; roles.witness_aux_lds = aux_lds; }
+    return pipeline_issue(p, call, st, roles);
+}
+
+// The pipelined verifier.  The in-field / encoded-message kernel needs only the chain's result: it runs on the caller's stream right
+// behind the chain kernel and writes the element's in-field and EM regions (disjoint from the records).  `sha` (nullable): the
+// SHA-256 / hashed-message step that produces `hashed` (h2r_pipeline_signature_verifier).
+int32_t pipeline_verify(h2r_pipeline *p, const void *sig, const void *n, const Exponent &e, const uint64_t *hashed, uint64_t batch, uint32_t flags,
+                        void *trace, void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, const Sha256Args *sha, hipStream_t st) {
+    if (!p || !sig || !n || !hashed || !trace || !powed_out || !status || !workspace) return H2R_E_NULL;
+    h2r_verify_layout vl;
+    const int32_t rc = verify_layout(p->ctx, e, &vl);
+    if (rc) return rc;
+    PowCall call = pow_buffers(sig, n, batch, flags, trace, powed_out, status, workspace);
+    call.check_in_field = 1;
+    call.pow(e, vl.pow, vl.elem_stride);
+    const AuxArgs va = verify_aux_args(p->ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status);
+    PipeRoles roles;
+    roles.after_chain = [&]() -> int32_t { return batch ? launch_verify_aux(p->ctx, va, st) : H2R_OK; };
+    roles.verify_aux = &va;
+    roles.sha = sha;
+    return pipeline_issue(p, call, st, roles);
+}
 }  // namespace
+}  // extern "C++"
+
+int32_t h2r_pipeline_create(const h2r_ctx *ctx, h2r_pipeline **out) try { return h2r_pipeline_create_ex(ctx, 2, 1, out); } H2R_CATCH_STATUS
 
 int32_t h2r_pipeline_info(h2r_pipeline *p, h2r_stream_t stream, uint64_t batch, h2r_pipeline_info_t *out) try {
     if (!p || !out) return H2R_E_NULL;
@@ -1487,26 +1882,6 @@ void h2r_pipeline_destroy(h2r_pipeline *p) try {
     delete p;
 } H2R_CATCH_VOID
 
-namespace {
-// Order `st` after the record kernel of the call in `slot`.
-int32_t pipeline_wait_slot(h2r_pipeline *p, u32 slot, hipStream_t st) {
-    DoneRef &d = p->done[slot];
-    if (!d.ev) return H2R_OK;   // that call launched no record kernel
-    bool alive = true;
-    if (d.borrowed) { std::lock_guard<std::mutex> lk(g_prof_mu); alive = d.gen == g_prof_gen; }
-    if (!alive) {
-        // the profiler's events were released in between: fall back to the tail of that record stream, which is
-        // behind the kernel in question (over-synchronises, never under-synchronises)
-        HIP_TRY(hipEventRecord(p->trace_done[slot], p->done_stream[slot]));
-        d = DoneRef{p->trace_done[slot], 0, false};
-    }
-    HIP_TRY(hipStreamWaitEvent(st, d.ev, 0));
-    return H2R_OK;
-}
-}  // namespace
-
-namespace { void call_plan(const h2r_ctx *c, u64 batch, bool busy, std::vector<u64> &sizes, bool &pace); }
-
 int32_t h2r_pipeline_call_plan(const h2r_ctx *ctx, uint64_t batch, uint32_t pipeline_busy_, uint64_t *sizes_out, uint32_t cap,
                                uint32_t *n_out, uint32_t *paced_out) try {
     if (!ctx || !n_out) return H2R_E_NULL;
@@ -1518,10 +1893,6 @@ int32_t h2r_pipeline_call_plan(const h2r_ctx *ctx, uint64_t batch, uint32_t pipe
     return H2R_OK;
 } H2R_CATCH_STATUS
 
-namespace {
-u32 exp_segment_count(const h2r_ctx *c, u64 batch, u32 nbits, bool has_trace, bool single_call);
-void exp_segment_plan(u32 n_seg, u32 nbits, const ExpBits *eb, std::vector<ExpSegment> &out);
-}
 int32_t h2r_exp_segment_plan(const h2r_ctx *ctx, uint64_t batch, const uint8_t *e_le_bytes, size_t e_len, uint32_t var_exp_bits,
                              uint32_t *bit_bounds_out, uint32_t *mul_mod_bounds_out, uint32_t cap, uint32_t *n_out) try {
     if (!ctx || !n_out) return H2R_E_NULL;
@@ -1532,7 +1903,7 @@ int32_t h2r_exp_segment_plan(const h2r_ctx *ctx, uint64_t batch, const uint8_t *
         if (rc) return rc;
         nbits = eb.nbits;
     }
-    const u32 n_seg = exp_segment_count(ctx, batch, nbits, true, false);
+    const u32 n_seg = exp_segment_count(ctx, batch, nbits, /*has_trace=*/true);
     std::vector<ExpSegment> segs;
     exp_segment_plan(n_seg, nbits, var_exp_bits ? nullptr : &eb, segs);
     *n_out = n_seg;
@@ -1557,473 +1928,148 @@ int32_t h2r_pipeline_join(h2r_pipeline *p, h2r_stream_t stream) try {
     return H2R_OK;
 } H2R_CATCH_STATUS
 
-namespace {
-// Is the record kernel of the previous pipelined call still queued or running?
-bool pipeline_busy(h2r_pipeline *p) {
-    if (p->pending) return true;
-    if (p->k == 0) return false;
-    const DoneRef &d = p->done[(p->k - 1) % p->depth];
-    if (!d.ev) return false;
-    if (d.borrowed) { std::lock_guard<std::mutex> lk(g_prof_mu); if (d.gen != g_prof_gen) return false; }
-    return hipEventQuery(d.ev) == hipErrorNotReady;
-}
+int32_t h2r_mul_mod_batch(const h2r_ctx *ctx, const void *a, const void *b, const void *n, uint64_t batch,
+                          uint32_t flags, void *trace, void *r_out, uint8_t *status, void *workspace,
+                          h2r_stream_t stream) try {
+    if (!ctx || !b) return H2R_E_NULL;
+    PowCall call = pow_buffers(a, n, batch, flags, trace, r_out, status, workspace);   // (one mul_mod per element: PowCall's defaults)
+    call.b = b; call.elem_stride = ctx->layout.record_stride;
+    return run_path(ctx, call, PowIssue::on(static_cast<hipStream_t>(stream)));
+} H2R_CATCH_STATUS
 
-// How one pipelined call is walked: the sizes of its sub-batches (each gets its own chain and record kernel) and whether
-// sub-batch i+1's chain kernel is held back until sub-batch i's record kernel starts.  What is at stake is the start and
-// the end of a call, not its steady state: an unsplit call exposes its whole chain kernel when no record kernel is in flight
-// (0.94 ms for 8,192 RSA-2048 signatures against 1.77 ms of record kernel), while at steady state one large launch per call
-// is the fastest form (fewer kernel boundaries: 1.77-1.81 ms per 8,192 against 1.93 as eight launches).  Measured per shape
-// (tools/sub_batch_ab.sh, profiles/r02_sub_batches.txt):
-//  * record-bound shapes (64-bit limbs, RSA-1536/2048): a call that finds the pipeline EMPTY is walked as sub-batches growing
-//    by 3/2 from one chain-kernel grid (1024, 1536, 2304, ...): each chain kernel then fits next to the record kernel of the
-//    sub-batch before it; paced (an unpaced train of chain kernels slows the record kernels it overlaps by 5 %).  A call
-//    that finds a record kernel in flight is not split.
-//  * chain-bound shapes (RSA-3072: chain kernel 0.65 ms, record kernel 0.49 ms per 1,024): uniform sub-batches, unpaced --
-//    the chain kernels run back to back either way, the record kernels hide behind them, and the last record kernel of a
-//    call is a quarter as long (4,096 signatures: 1.39-1.44 -> 1.60-1.62 M assigns/s over six calls).
-//  * RSA-1024 and the 32-bit-limb shapes: no gain measured from any split; one launch.
-// (busy: a record kernel of the previous call is still queued or running)
-void call_plan(const h2r_ctx *c, u64 batch, bool busy, std::vector<u64> &sizes, bool &pace) {
-    sizes.clear(); pace = false;
-    const u64 unit = (u64)c->num_cus * (c->K > 64 ? 2 : 4);   // one chain-kernel grid: four 4-wave (two 8-wave) workgroups per CU
-    if (knobs().pipe_sub_batch > 0) {
-        pace = knobs().pipe_pace != 0;
-        for (u64 o = 0; o < batch; o += (u64)knobs().pipe_sub_batch) sizes.push_back(std::min<u64>((u64)knobs().pipe_sub_batch, batch - o));
-        if (sizes.empty()) sizes.push_back(batch);
-        return;
-    }
-    const bool w64 = c->layout.limb_width == 64;
-    if (w64 && c->L > 32 && batch > 3 * unit) {                         // chain-bound (RSA-3072, RSA-4096 at 64-bit limbs)
-        for (u64 o = 0; o < batch; o += 2 * unit) sizes.push_back(std::min<u64>(2 * unit, batch - o));
-        return;
-    }
-    if (w64 && c->L > 16 && c->L <= 32 && batch > unit + unit / 2 && !busy) {   // record-bound, pipeline empty
-        pace = true;
-        u64 cur = unit, left = batch;
-        while (left) {
-            u64 take = std::min(cur, left);
-            if (left - take < cur / 2) take = left;
-            sizes.push_back(take); left -= take;
-            cur = (cur * 3 / 2) & ~255ull;
-        }
-        return;
-    }
-    sizes.push_back(batch);
-}
-// A LONG exponent on a latency-bound batch (at most two elements per CU: every chain's own length is what the call waits for --
-// BASELINE config 5: 256 elements x 3,072 dependent mul_mods, 7-8.5 ms of chain and 7.9 ms of record kernel) is walked as SEGMENTS of
-// its bits: the chain kernel of bits [lo, hi) of every element, then -- on the record stream -- the record kernel of those bits'
-// mul_mods, next to the chain kernel of the following segment.  A call's records then trail its own chains by one segment instead of
-// by the whole chain: a single call drops from chain + records to chain + 1/S records, and a train of pipelined calls loses the
-// exposed first chain / last record kernel.  Same values, same buffers; the (squared, acc) pair crosses launches in the workspace.
-u32 exp_segment_count(const h2r_ctx *c, u64 batch, u32 nbits, bool has_trace, bool single_call) {
-    if (!has_trace || batch == 0) return 1;
-    // single_call: a stream-ordered export that neither follows nor is followed by another call's kernels.  EXPERIMENT, off in the
-    // product (the knob's default): the same cut for a SHORT exponent (e = 65537: 19 mul_mods) on a batch that fills the chip but is
-    // too small to be walked as sub-batches of elements -- measured +2 % with two segments at 1,024 RSA-2048 elements and a loss
-    // everywhere else (a 9-mul_mod chain kernel is latency-bound, every segment adds a cross-queue wait): profiles/r03_exp_segments.txt
-    if (single_call && nbits >= 8 && nbits < 512 && c->layout.limb_width == 64 && c->L == 32 && batch > 512 && !plain_call_overlaps(c, batch)) {
-        const long k = knobs().single_call_segments;
-        return k >= 0 ? (u32)std::max<long>(1, std::min<long>(k, nbits / 2)) : 1;
-    }
-    if (batch > 2ull * c->num_cus || nbits < 512) return 1;
-    if (knobs().exp_segments >= 0) return knobs().exp_segments > 1 ? (u32)std::min<long>(knobs().exp_segments, nbits / 32) : 1;
-    // measured (tools/exp_segments_ab.sh, config 5, same box, 1 / 2 / 4 / 8 / 16 / 32 segments): pipelined 26.2 / 28.1 / 29.3 / 30.5 / 30.3 / 29.3 k
-    // assigns/s, single calls 17.4 / 21.4 / 25.2 / 27.4 / 28.7 / 27.6 k
-    return std::min<u32>(16, nbits / 128);   // >= 128 bits (128-256 mul_mods per element, ~0.5 ms of chain) per segment
-}
-// The segments themselves: equal parts of the exponent's bits (long exponents: boundaries on 32-bit words of e) with the mul_mods each covers
-// -- one squaring per bit plus one multiply per set bit of a fixed exponent `eb`, two per bit of a variable one (eb == nullptr).
-void exp_segment_plan(u32 n_seg, u32 nbits, const ExpBits *eb, std::vector<ExpSegment> &out) {
-    out.clear();
-    const u32 word = nbits >= 512 ? ~31u : ~0u;
-    u32 t_lo = 0;
-    for (u32 sgi = 0; sgi < n_seg; ++sgi) {
-        ExpSegment sg;
-        sg.bit_lo = (u32)((u64)nbits * sgi / n_seg) & word;
-        sg.bit_hi = sgi + 1 == n_seg ? nbits : (u32)((u64)nbits * (sgi + 1) / n_seg) & word;
-        sg.t_lo = t_lo; sg.t_cnt = 0;
-        for (u32 bi = sg.bit_lo; bi < sg.bit_hi; ++bi) sg.t_cnt += eb ? 1u + ((eb->words[bi >> 5] >> (bi & 31)) & 1u) : 2u;
-        t_lo += sg.t_cnt;
-        out.push_back(sg);
-    }
-}
-void pipeline_plan(h2r_pipeline *p, u64 batch, bool assume_empty, std::vector<u64> &sizes, bool &pace) {
-    // (the busy query is only made where the answer matters)
-    const h2r_ctx *c = p->ctx;
-    const bool may_grow = c->layout.limb_width == 64 && c->L > 16 && c->L <= 32;
-    call_plan(c, batch, may_grow && !assume_empty && pipeline_busy(p), sizes, pace);
-}
+int32_t h2r_square_mod_batch(const h2r_ctx *ctx, const void *a, const void *n, uint64_t batch, uint32_t flags,
+                             void *trace, void *r_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    return h2r_mul_mod_batch(ctx, a, a, n, batch, flags, trace, r_out, status, workspace, stream);  // chip.rs:648
+} H2R_CATCH_STATUS
 
-// One pipelined call: chain kernel (+ `after_chain`, e.g. the verifier's aux kernel) on the caller's stream, the
-// record kernel on a side stream, then the lazy join of the call whose buffers the next call may reuse.
-int32_t pipeline_issue(h2r_pipeline *p, const void *x, const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch,
-                       uint32_t flags, void *trace, const h2r_pow_layout &pl, uint64_t elem_stride, void *out,
-                       uint8_t *status, void *workspace, hipStream_t st, const std::function<int32_t()> &after_chain,
-                       u32 check_in_field = 1, bool assume_empty = false, const AuxArgs *witness_aux = nullptr, u32 witness_aux_lds = 0,
-                       const void *e_limbs = nullptr, u32 e_num_limbs = 0, u32 exp_limb_bits = 0, const Sha256Args *sha = nullptr,
-                       const AuxArgs *verify_aux = nullptr) {
-    // verify_aux (nullable): the verifier's in-field + encoded-message witness of the whole call (what `after_chain` launches as a
-    // kernel): when every sub-batch of the call goes out as a step launch, the chain role writes it element by element instead
-    // sha (nullable): the SHA-256 / hashed-message step of RSASignatureVerifier for THIS call's messages; `after_chain` consumes
-    // its output.  It rides on the call's first step launch when there is one, and is a kernel of its own on `st` otherwise.
-    // witness_aux (nullable): what `after_chain` would launch, when that is a kernel whose output belongs to the call's
-    // TRACE (the assert_in_field witness): a call issued as one-launch steps writes it together with its records
-    // e_limbs (nullable): per-element variable exponents (BigIntChip::pow_mod, chip.rs:664-696) instead of the fixed e_le
-    const h2r_ctx *ctx = p->ctx;
-    ExpBits eb; u32 T;
-    int32_t rc = H2R_OK;
-    const u32 mode = e_limbs ? CHAIN_POW_VAR : CHAIN_POW_FIXED;
-    if (e_limbs) { std::memset(&eb, 0, sizeof eb); T = pl.num_mul_mods; }
-    else rc = exp_to_bits(e_le, e_len, &eb, &T);
+int32_t h2r_pow_mod_fixed_exp_batch(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le,
+                                    size_t e_len, uint64_t batch, uint32_t flags, void *trace, void *out,
+                                    uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx) return H2R_E_NULL;
+    return pow_impl(ctx, Exponent::fixed(e_le, e_len), pow_buffers(x, n, batch, flags, trace, out, status, workspace), static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_pow_mod_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs,
+                          uint32_t exp_limb_bits, const void *n, uint64_t batch, uint32_t flags, void *trace,
+                          void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !e_limbs) return H2R_E_NULL;
+    return pow_impl(ctx, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), pow_buffers(x, n, batch, flags, trace, out, status, workspace),
+                    static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_modpow_public_key_batch(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le,
+                                    size_t e_len, uint64_t batch, uint32_t flags, void *trace, void *in_field_trace,
+                                    void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx) return H2R_E_NULL;
+    return modpow_public_key_impl(ctx, Exponent::fixed(e_le, e_len), pow_buffers(x, n, batch, flags, trace, out, status, workspace), in_field_trace,
+                                  static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_modpow_public_key_var_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs,
+                                        uint32_t exp_limb_bits, const void *n, uint64_t batch, uint32_t flags, void *trace,
+                                        void *in_field_trace, void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !e_limbs) return H2R_E_NULL;
+    return modpow_public_key_impl(ctx, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits),
+                                  pow_buffers(x, n, batch, flags, trace, out, status, workspace), in_field_trace, static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_verify_layout_fixed(const h2r_ctx *ctx, const uint8_t *e_le, size_t e_len, h2r_verify_layout *out) try {
+    return verify_layout(ctx, Exponent::fixed(e_le, e_len), out);
+} H2R_CATCH_STATUS
+
+// RSAPubE::Var arm (src/chip.rs:108-110: pow_mod with the chip's exp_limb_bits)
+int32_t h2r_verify_layout_var(const h2r_ctx *ctx, uint32_t e_num_limbs, uint32_t exp_limb_bits, h2r_verify_layout *out) try {
+    return verify_layout(ctx, Exponent::per_element(nullptr, e_num_limbs, exp_limb_bits), out);
+} H2R_CATCH_STATUS
+
+int32_t h2r_verify_pkcs1v15_batch(const h2r_ctx *ctx, const void *sig, const void *n, const uint8_t *e_le, size_t e_len,
+                                  const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace, void *powed_out,
+                                  uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    return verify_impl(ctx, sig, n, Exponent::fixed(e_le, e_len), hashed, batch, flags, trace, powed_out, is_valid_out, status, workspace,
+                       static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_verify_pkcs1v15_var_batch(const h2r_ctx *ctx, const void *sig, const void *n, const void *e_limbs, uint32_t e_num_limbs,
+                                      uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace,
+                                      void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!e_limbs) return H2R_E_NULL;
+    return verify_impl(ctx, sig, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), hashed, batch, flags, trace, powed_out, is_valid_out,
+                       status, workspace, static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_verify_trace_flatten(const h2r_ctx *ctx, const h2r_verify_layout *vl, const void *elem_host, void *stream_out) try {
+    if (!ctx || !vl || !elem_host || !stream_out) return H2R_E_NULL;
+    if (vl->pow.off_records == UINT64_MAX) return H2R_E_SHAPE;   // h2r_verify_layout_compact: no records to flatten
+    const u8 *e = static_cast<const u8 *>(elem_host);
+    u8 *o = static_cast<u8 *>(stream_out);
+    const AuxGeom g(ctx->L, ctx->layout.limb_width);
+    in_field_sections(g, [&](u64 off, u64 len) { std::memcpy(o, e + vl->off_in_field + off, len); o += len; });
+    int32_t rc = h2r_pow_trace_flatten(ctx, &vl->pow, e, o);
     if (rc) return rc;
-    const u64 e_bytes = (u64)e_num_limbs * ctx->layout.limb_bytes;   // per element
-    const u32 slot = p->k % p->depth;
-    p->done[slot] = DoneRef{};
-    if (knobs().pipe_serialize && p->aux[0] != p->aux[1] && p->k > 0) {   // order this record stream behind the previous record kernel
-        rc = pipeline_wait_slot(p, (p->k - 1) % p->depth, p->aux[p->k & 1]);
-        if (rc) return rc;
-    }
-    // A large call may be walked as sub-batches, each with its own chain and record kernel (pipeline_plan): sub-batch
-    // i+1's chain kernel then runs next to sub-batch i's record kernel INSIDE the call, exactly as consecutive calls do.
-    // The sub-batches are slices of the caller's buffers and of the whole call's workspace plan ([batch*T][4][L],
-    // element-major), so audits and emitters see one call.
-    std::vector<u64> sizes; bool pace = false;
-    const u32 nbits_all = e_limbs ? e_num_limbs * exp_limb_bits : eb.nbits;
-    const u32 n_seg_single = assume_empty ? exp_segment_count(ctx, batch, nbits_all, trace && T, true) : 1;   // (a single stream-ordered call)
-    // RSA-2048 on a pipeline created with TWO side streams and three or more buffer sets: the two-queue form -- chain kernels on the caller's
-    // stream, record kernels alternating between the side streams, so that call k + 1's record kernel starts while call k's tail drains --
-    // beats the one-launch step (same box, alternating: 5.41 / 5.41 M assigns/s against 5.18 / 5.32 M at 1,024 per call, 5.55-5.58 against
-    // 5.50-5.51 M at 2,048).  The other step shapes were chain-bound enough to lose that way in round 4 (RSA-1024 with its four-wave chain 9.4
-    // against 12.4 M, RSA-3072 2.1 against 2.5 M, RSA-4096 1.2 against 1.5 M; 128 x 32-bit limbs: the same): tools/two_queue_ab.sh,
-    // profiles/r04_two_queue.txt.  [r6] RSA-1024 with the one-wave chain wins from 1,280 per call (two_queue_shape).
-    // (calls of up to 2,048: at 4,096 per call one launch has little boundary left to hide and the step is ahead again, 5.37-5.42 against 5.27-5.33 M)
-    // ... provided the three streams sit on three hardware queues, which the pipeline measures once per caller stream (pipeline_three_queues);
-    // with a shared queue the call falls back to the one-launch step
-    const bool overlap_records = two_queue_shape(ctx, batch) && p->aux[0] != p->aux[1] && p->depth >= 3 && knobs().pipe_step < 1 &&
-                                 pipeline_three_queues(p, st);
-    const bool as_steps = step_eligible(ctx, batch, trace, T) && n_seg_single <= 1 && !overlap_records;
-    if (p->pending && (!as_steps || p->pending_st != st)) {   // the records still owed go out alone, `st` behind them
-        rc = pipeline_flush(p, st);
-        if (rc) return rc;
-    }
-    if (as_steps) {
-        // every sub-batch is one launch: its chains together with the records of the sub-batch before it (of this call or of
-        // the previous one).  With records pending the call is not split; a call that starts a train is, so that its first,
-        // exposed chain kernel is short (the sizes an empty pipeline gets)
-        if (p->pending) sizes.push_back(batch); else call_plan(ctx, batch, false, sizes, pace);
-        std::vector<u64> capped;
-        for (u64 sz : sizes) {
-            const u64 parts = (sz + kStepMax - 1) / kStepMax;
-            const u64 each = round_up((sz + parts - 1) / parts, 256);
-            for (u64 o2 = 0; o2 < sz; o2 += each) capped.push_back(std::min(each, sz - o2));
-        }
-        sizes.swap(capped);
-    } else {
-        pipeline_plan(p, batch, assume_empty, sizes, pace);
-        if (overlap_records && ctx->L == 16 && batch > 4096 && knobs().pipe_sub_batch <= 0) {
-            // RSA-1024 in the two-queue form: a call above 4,096 as uniform sub-batches of 2,048, unpaced (8,192 per call 15.1 -> 15.6-15.9 M assigns/s,
-            // 16,384 13.9-14.1 -> 14.4-14.5 M; paced or as sub-batches of 4,096 it loses: profiles/r06_two_queue_rsa1024.txt)
-            sizes.clear(); pace = false;
-            for (u64 o2 = 0; o2 < batch; o2 += 2048) sizes.push_back(std::min<u64>(2048, batch - o2));
-        }
-    }
-    const bool split = sizes.size() > 1;
-    const h2r_layout &lo = ctx->layout;
-    const Workspace wp = workspace_plan(lo.limb_bytes, ctx->L, batch, T ? T : 1);
-    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
-    const u64 in_bytes = (u64)ctx->K * 4, ws_elem = (u64)(T ? T : 1) * 4 * ctx->L * lo.limb_bytes;
-    auto launch_sha_alone = [&]() -> int32_t {
-        if (!sha || sha->batch == 0) return H2R_OK;
-        ProfScope ps(H2R_KERNEL_SHA256, st, true);
-        hipExtLaunchKernelGGL(sha256_kernel, dim3((unsigned)((sha->batch + 63) / 64)), dim3(64), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, *sha);
-        HIP_TRY(hipGetLastError());
-        return H2R_OK;
-    };
-    if (!as_steps || !p->pending) {   // no step launch to ride on (two-queue form, or a call that starts a train with a chain kernel)
-        rc = launch_sha_alone();
-        if (rc) return rc;
-    }
-    if (as_steps) {
-        const bool aux_as_role = witness_aux && witness_aux->batch && witness_aux_lds <= step_shared_bytes(ctx);
-        bool aux_done = false;
-        bool sha_done = !sha || !p->pending;
-        // the verifier's witness inside the chain role: only when the whole call is step launches (a call that starts a train keeps
-        // the kernel behind it) and the roles' LDS holds its staging.  When this very launch's SHA role produces the hashed limbs
-        // the chain role waits for that role's message count (Sha256Args::done / target)
-        const AuxGeom vg(ctx->L, lo.limb_width);
-        // measured per shape (tools/verify_fold_ab.sh, ms per 1,024-signature step, digests / messages): RSA-2048 0.2040 / 0.2079 -> 0.1973 /
-        // 0.1989 with the fold; the chain-bound shapes do not gain -- RSA-1024 0.0975 / 0.1097 -> 0.0988 / 0.1080, RSA-4096 0.6745 / 0.6854 ->
-        // 0.6773 / 0.6795 -- or lose: RSA-3072 0.4195 / 0.4258 -> 0.4381 / 0.4601 (the witness lengthens the role the launch waits for)
-        const bool fold_shape = knobs().verify_fold >= 0 ? knobs().verify_fold != 0 : ctx->L == 32;
-        const bool fold_verify = fold_shape && verify_aux && verify_aux->batch && p->pending && (!sha || p->sha_done_dev) && vg.in_field_sz() + vg.em_sz() <= step_shared_bytes(ctx);
-        u64 off = 0;
-        for (size_t i = 0; i < sizes.size(); off += sizes[i], ++i) {
-            const u64 nb = sizes[i];
-            const u8 *xs = static_cast<const u8 *>(x) + off * in_bytes;
-            const u8 *ns = static_cast<const u8 *>(n) + ((flags & H2R_F_SHARED_MODULUS) ? 0 : off * in_bytes);
-            PathArgs pa;
-            rc = run_path(ctx, mode, xs, nullptr, ns, e_limbs ? static_cast<const u8 *>(e_limbs) + off * e_bytes : nullptr, e_num_limbs, exp_limb_bits,
-                          e_limbs ? nullptr : &eb, check_in_field, nb, flags, T,
-                          static_cast<u8 *>(trace) + off * elem_stride, elem_stride, pl.off_records, &pl,
-                          out ? static_cast<u8 *>(out) + off * in_bytes : nullptr, status + off, split ? ws + off * ws_elem : workspace,
-                          st, p->aux[0], nullptr, nullptr, nullptr, split ? ws + wp.off_pre : nullptr, &pa,
-                          split ? ws + wp.off_n + off * in_bytes : nullptr);
-            if (rc) return rc;
-            if (!pa.has_trace) return H2R_E_SHAPE;
-            if (p->pending) {
-                // THIS call's assert_in_field witness rides on the first step launch the call issues: it needs only x and n,
-                // which are therefore read in `stream` order inside the call, like every other input
-                const bool with_aux = aux_as_role && !aux_done;
-                ProfScope ps(H2R_KERNEL_STEP, st, true);
-                AuxArgs va;
-                if (fold_verify) {   // the slice of the call this launch's chains cover
-                    va = *verify_aux;
-                    va.x = xs; va.n = ns;
-                    va.hashed = verify_aux->hashed + off * 4;
-                    va.powed = static_cast<const u8 *>(verify_aux->powed) + off * in_bytes;
-                    va.batch = nb;
-                    va.trace = verify_aux->trace + off * elem_stride;
-                    va.is_valid = verify_aux->is_valid ? verify_aux->is_valid + off : nullptr;
-                    va.status = verify_aux->status + off;
-                }
-                Sha256Args sr;
-                u32 sha_target = p->sha_issued;
-                if (!sha_done) {
-                    sr = *sha;
-                    if (fold_verify) { sha_target += (u32)sha->batch; sr.done = p->sha_done_dev; sr.target = sha_target; }
-                }
-                HIP_TRY(launch_step(ctx, pa.ca, p->pending_ta, with_aux ? witness_aux : nullptr, fold_verify ? &va : nullptr, sha_done ? nullptr : &sr, st, ps.a, ps.b));
-                p->sha_issued = sha_target;   // (only a launch that went out counts: the device word never runs behind the host's target)
-                aux_done = aux_done || with_aux;
-                sha_done = true;
-            } else {
-                ProfScope ps(H2R_KERNEL_CHAIN, st, true);
-                HIP_TRY(launch_chain(ctx, pa.ca, false, st, ps.a, ps.b));
-            }
-            p->pending = true; p->pending_ta = pa.ta; p->pending_st = st;
-        }
-        p->done_stream[slot] = st;
-        p->k += 1;
-        if (!aux_done && !fold_verify) rc = after_chain();   // (a call that starts a train as one chain kernel: the in-field kernel behind it)
-        if (rc) return rc;
-        for (; p->joined + p->depth <= p->k; ++p->joined) {   // calls issued the two-queue way earlier on
-            rc = pipeline_wait_slot(p, p->joined % p->depth, st);
-            if (rc) return rc;
-        }
-        return H2R_OK;
-    }
-    const u32 n_seg = n_seg_single > 1 ? n_seg_single : (sizes.size() == 1 ? exp_segment_count(ctx, batch, nbits_all, trace && T) : 1);
-    if (n_seg > 1) {
-        std::vector<ExpSegment> segs;
-        exp_segment_plan(n_seg, nbits_all, e_limbs ? nullptr : &eb, segs);
-        for (u32 sgi = 0; sgi < n_seg; ++sgi) {
-            const ExpSegment &sg = segs[sgi];
-            const bool last = sgi + 1 == n_seg;
-            DoneRef cur{};
-            rc = run_path(ctx, mode, x, nullptr, n, e_limbs, e_num_limbs, exp_limb_bits, e_limbs ? nullptr : &eb, check_in_field, batch, flags, T,
-                          trace, elem_stride, pl.off_records, &pl, out, status, workspace, st, p->aux[p->k & 1], p->chain_done[slot],
-                          last ? p->trace_done[slot] : p->sub_done[sgi & 1], last ? &p->done[slot] : &cur, nullptr, nullptr, nullptr, &sg);
-            if (rc) return rc;
-        }
-        p->done_stream[slot] = p->aux[p->k & 1];
-        p->k += 1;
-        rc = after_chain();
-        if (rc) return rc;
-        for (; p->joined + p->depth <= p->k; ++p->joined) {
-            rc = pipeline_wait_slot(p, p->joined % p->depth, st);
-            if (rc) return rc;
-        }
-        return H2R_OK;
-    }
-    DoneRef prev{};   // the record kernel of the sub-batch before the current one
-    u64 o = 0;
-    for (size_t i = 0; i < sizes.size(); o += sizes[i], ++i) {
-        const u64 nb = sizes[i];
-        const bool last = i + 1 == sizes.size();
-        DoneRef cur{};
-        const u8 *xs = static_cast<const u8 *>(x) + o * in_bytes;
-        const u8 *ns = static_cast<const u8 *>(n) + ((flags & H2R_F_SHARED_MODULUS) ? 0 : o * in_bytes);
-        rc = run_path(ctx, mode, xs, nullptr, ns, e_limbs ? static_cast<const u8 *>(e_limbs) + o * e_bytes : nullptr, e_num_limbs, exp_limb_bits,
-                      e_limbs ? nullptr : &eb, check_in_field, nb, flags, T,
-                      static_cast<u8 *>(trace) + o * elem_stride, elem_stride, pl.off_records, &pl,
-                      out ? static_cast<u8 *>(out) + o * in_bytes : nullptr, status + o, split ? ws + o * ws_elem : workspace,
-                      st, p->aux[p->k & 1], p->chain_done[slot], last ? p->trace_done[slot] : p->sub_done[i & 1],
-                      last ? &p->done[slot] : &cur, split ? ws + wp.off_pre : nullptr, nullptr,
-                      split ? ws + wp.off_n + o * in_bytes : nullptr);
-        if (rc) return rc;
-        // paced: as consecutive calls are paced by the lazy join below, sub-batch i+1's chain kernel starts with sub-batch
-        // i's record kernel, not earlier
-        if (prev.ev && pace) {
-            bool alive = true;
-            if (prev.borrowed) { std::lock_guard<std::mutex> lk(g_prof_mu); alive = prev.gen == g_prof_gen; }
-            if (alive) HIP_TRY(hipStreamWaitEvent(st, prev.ev, 0));
-        }
-        prev = cur;
-    }
-    p->done_stream[slot] = p->aux[p->k & 1];
-    p->k += 1;
-    rc = after_chain();
+    o += vl->pow.stream_bytes;
+    std::memcpy(o, e + vl->off_em, vl->em_stream_bytes); o += vl->em_stream_bytes;
+    if ((u64)(o - static_cast<u8 *>(stream_out)) != vl->stream_bytes) return H2R_E_SHAPE;
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the caller of the path: RSASignatureVerifier::verify_pkcs1v15_signature (src/lib.rs:183-246) ---------------------
+// SHA-256 of every element's message, the reversed digest packed into the four hashed-message limbs (:213-239), and -- in
+// h2r_signature_verifier_batch -- RSAChip::verify_pkcs1v15_signature on them, all in stream order on the caller's stream.
+
+int32_t h2r_sha256_hashed_msg_batch(const h2r_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t fixed_len, uint64_t batch,
+                                    uint8_t *digest_out, uint64_t *hashed_out, void *hm_trace, uint64_t hm_stride, h2r_stream_t stream) try {
+    if (!ctx || (!msgs && (msg_off || fixed_len))) return H2R_E_NULL;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    Sha256Args sa;
+    const int32_t rc = sha_args(msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, &sa);
     if (rc) return rc;
-    // lazy join: the NEXT call reuses the buffers of call k - depth, so order the user stream after that call's
-    // record kernel now -- behind this call's chain kernel, which therefore overlaps the record kernels in flight
-    for (; p->joined + p->depth <= p->k; ++p->joined) {
-        rc = pipeline_wait_slot(p, p->joined % p->depth, st);
-        if (rc) return rc;
-    }
-    return H2R_OK;
-}
-
-// Does a plain (non-pipelined) pow call of this size gain from being walked as overlapping sub-batches?  The shapes and
-// sizes pipeline_plan splits for an empty pipeline.
-bool plain_call_overlaps(const h2r_ctx *c, u64 batch) {
-    if (knobs().plain_overlap == 0) return false;
-    const u64 unit = (u64)c->num_cus * (c->K > 64 ? 2 : 4);
-    if (c->layout.limb_width != 64) return false;
-    if (c->L > 32) return batch > 3 * unit;
-    return c->L > 16 && batch > unit + unit / 2;
-}
-
-int32_t overlapped_pow_fixed(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch,
-                             uint32_t flags, void *trace, const h2r_pow_layout &pl, uint64_t elem_stride, void *out, uint8_t *status,
-                             void *workspace, hipStream_t st, u32 check_in_field, u32 T,
-                             const void *e_limbs, u32 e_num_limbs, u32 exp_limb_bits) {
-    // (e_limbs: per-element variable exponents -- BigIntChip::pow_mod -- instead of e_le; only its long-exponent walk comes this way)
-    H2R_ON_DEVICE(ctx->params.device);
-    std::lock_guard<std::mutex> lk(ctx->pipe_mu);
-    if (!ctx->pipe) {
-        const int32_t rc = h2r_pipeline_create_ex(ctx, 2, 1, &ctx->pipe);
-        if (rc) return rc;
-    }
-    ScratchGuard sg; sg.st = st;
-    void *ws = workspace;
-    if (!ws) {   // freed in stream order behind the join below, i.e. after the record kernels that read it
-        HIP_TRY(hipMallocAsync(&sg.p, workspace_plan(ctx->layout.limb_bytes, ctx->L, batch, T).total, st));
-        sg.owned = true; ws = sg.p;
-    }
-    const int32_t rc = pipeline_issue(ctx->pipe, x, n, e_le, e_len, batch, flags, trace, pl, elem_stride, out, status, ws, st,
-                                      []() -> int32_t { return H2R_OK; }, check_in_field, true, nullptr, 0, e_limbs, e_num_limbs, exp_limb_bits);
-    const int32_t rj = h2r_pipeline_join(ctx->pipe, st);   // also after a failed issue: whatever was queued is ordered
-    return rc ? rc : rj;
-}
-
-AuxArgs verify_aux_args(const h2r_ctx *ctx, const void *sig, const void *n, const uint64_t *hashed, uint64_t batch, uint32_t flags,
-                        void *trace, const h2r_verify_layout &vl, void *powed_out, uint8_t *is_valid_out, uint8_t *status) {
-    AuxArgs aa;
-    std::memset(&aa, 0, sizeof aa);
-    aa.x = sig; aa.n = n; aa.n_stride = (flags & H2R_F_SHARED_MODULUS) ? 0 : ctx->L;
-    aa.hashed = hashed; aa.powed = powed_out; aa.batch = batch; aa.L = ctx->L;
-    aa.trace = static_cast<u8 *>(trace); aa.elem_stride = vl.elem_stride; aa.off_in_field = vl.off_in_field; aa.off_em = vl.off_em;
-    aa.is_valid = is_valid_out; aa.status = status;
-    return aa;
-}
-int32_t launch_verify_aux(const h2r_ctx *ctx, const void *sig, const void *n, const uint64_t *hashed, uint64_t batch, uint32_t flags,
-                          void *trace, const h2r_verify_layout &vl, void *powed_out, uint8_t *is_valid_out, uint8_t *status, hipStream_t st) {
-    const AuxArgs aa = verify_aux_args(ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status);
-    ProfScope ps(H2R_KERNEL_AUX, st, true);   // dispatch-stamped events: no marker packets on the caller's stream
-    const AuxGeom ag(ctx->L, 64);
-    hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)batch), dim3(64), (unsigned)(ag.in_field_sz() + ag.em_sz()), st, ps.a, ps.b, 0, aa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
-}
-
-// The assert_in_field(x, n) witness alone (src/chip.rs:106), one element every h2r_fresh_op_layout(IS_IN_FIELD) stride.
-int32_t in_field_args(const h2r_ctx *ctx, const void *x, const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, AuxArgs *aa, u32 *lds) {
-    u64 es = 0;
-    const int32_t rc = h2r_fresh_op_layout(ctx, FRESH_IS_IN_FIELD, &es, nullptr, nullptr);
-    if (rc) return rc;
-    std::memset(aa, 0, sizeof *aa);
-    aa->x = x; aa->n = n; aa->n_stride = (flags & H2R_F_SHARED_MODULUS) ? 0 : ctx->L;
-    aa->batch = batch; aa->L = ctx->L;
-    aa->trace = static_cast<u8 *>(in_field_trace); aa->elem_stride = es; aa->off_in_field = 0;
-    const AuxGeom ag(ctx->L, ctx->layout.limb_width);
-    *lds = (u32)(ag.in_field_sz() + ag.em_sz());
-    return H2R_OK;
-}
-int32_t launch_in_field(const h2r_ctx *ctx, const void *x, const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, hipStream_t st) {
     if (batch == 0) return H2R_OK;
-    AuxArgs aa; u32 lds = 0;
-    const int32_t rc = in_field_args(ctx, x, n, batch, flags, in_field_trace, &aa, &lds);
-    if (rc) return rc;
+    if (batch >= (1ull << 37)) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
-    ProfScope ps(H2R_KERNEL_AUX, st, true);
-    if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    else hipExtLaunchKernelGGL((aux_kernel<32>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
-}
-}  // namespace
+    return launch_sha(sa, static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_signature_verifier_batch(const h2r_ctx *ctx, const uint8_t *msgs, const uint64_t *msg_off, uint64_t fixed_len, const void *sig,
+                                     const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch, uint32_t flags, void *trace,
+                                     void *hm_trace, uint64_t hm_stride, uint8_t *digest_out, uint64_t *hashed_out, void *powed_out,
+                                     uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!hashed_out) return H2R_E_NULL;
+    if (ctx && (ctx->layout.limb_width != 64 || ctx->L < 9)) return H2R_E_SHAPE;   // before any launch: RSAChip::LIMB_WIDTH
+    const int32_t rc = h2r_sha256_hashed_msg_batch(ctx, msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, stream);
+    if (rc) return rc;
+    return h2r_verify_pkcs1v15_batch(ctx, sig, n, e_le, e_len, hashed_out, batch, flags, trace, powed_out, is_valid_out, status, workspace, stream);
+} H2R_CATCH_STATUS
 
 int32_t h2r_pipeline_modpow_public_key(h2r_pipeline *p, const void *x, const void *n, const uint8_t *e_le, size_t e_len,
                                        uint64_t batch, uint32_t flags, void *trace, void *in_field_trace, void *out,
                                        uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!p || !trace || !workspace) return H2R_E_NULL;
-    h2r_pow_layout pl;
-    const int32_t rc = h2r_pow_fixed_layout(p->ctx, e_le, e_len, &pl);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // the in-field witness needs only x and n: its kernel runs on the caller's stream right behind the chain kernel -- or,
-    // when the call is issued as one-launch steps, as a role of the launch that writes the call's records
-    AuxArgs aa; u32 aux_lds = 0;
-    const bool have_aux = in_field_trace && batch && in_field_args(p->ctx, x, n, batch, flags, in_field_trace, &aa, &aux_lds) == H2R_OK;
-    return pipeline_issue(p, x, n, e_le, e_len, batch, flags, trace, pl, pl.elem_stride, out, status, workspace, st,
-                          [&]() -> int32_t {
-                              if (!in_field_trace) return H2R_OK;
-                              return launch_in_field(p->ctx, x, n, batch, flags, in_field_trace, st);
-                          }, 1, false, have_aux ? &aa : nullptr, aux_lds);
+    return pipeline_modpow_public_key(p, x, n, Exponent::fixed(e_le, e_len), batch, flags, trace, in_field_trace, out, status, workspace,
+                                      static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 // RSAPubE::Var (src/chip.rs:108-110): per-element exponents; the same pipelining as the fixed-exponent form
 int32_t h2r_pipeline_modpow_public_key_var(h2r_pipeline *p, const void *x, const void *e_limbs, uint32_t e_num_limbs, uint32_t exp_limb_bits,
                                            const void *n, uint64_t batch, uint32_t flags, void *trace, void *in_field_trace, void *out,
                                            uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!p || !trace || !workspace || !e_limbs) return H2R_E_NULL;
-    h2r_pow_layout pl;
-    const int32_t rc = h2r_pow_var_layout(p->ctx, e_num_limbs, exp_limb_bits, &pl);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    AuxArgs aa; u32 aux_lds = 0;
-    const bool have_aux = in_field_trace && batch && in_field_args(p->ctx, x, n, batch, flags, in_field_trace, &aa, &aux_lds) == H2R_OK;
-    return pipeline_issue(p, x, n, nullptr, 0, batch, flags, trace, pl, pl.elem_stride, out, status, workspace, st,
-                          [&]() -> int32_t {
-                              if (!in_field_trace) return H2R_OK;
-                              return launch_in_field(p->ctx, x, n, batch, flags, in_field_trace, st);
-                          }, 1, false, have_aux ? &aa : nullptr, aux_lds, e_limbs, e_num_limbs, exp_limb_bits);
+    if (!e_limbs) return H2R_E_NULL;
+    return pipeline_modpow_public_key(p, x, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), batch, flags, trace, in_field_trace, out,
+                                      status, workspace, static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 int32_t h2r_pipeline_verify_pkcs1v15(h2r_pipeline *p, const void *sig, const void *n, const uint8_t *e_le, size_t e_len,
                                      const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace, void *powed_out,
                                      uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!p || !sig || !n || !hashed || !trace || !powed_out || !status || !workspace) return H2R_E_NULL;
-    h2r_verify_layout vl;
-    const int32_t rc = h2r_verify_layout_fixed(p->ctx, e_le, e_len, &vl);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    // the in-field / encoded-message kernel needs only the chain's result: it runs on the caller's stream right
-    // behind the chain kernel and writes the element's in-field and EM regions (disjoint from the records)
-    const AuxArgs va = verify_aux_args(p->ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status);
-    return pipeline_issue(p, sig, n, e_le, e_len, batch, flags, trace, vl.pow, vl.elem_stride, powed_out, status, workspace, st,
-                          [&]() -> int32_t {
-                              if (batch == 0) return H2R_OK;
-                              return launch_verify_aux(p->ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status, st);
-                          }, 1, false, nullptr, 0, nullptr, 0, 0, nullptr, &va);
+    return pipeline_verify(p, sig, n, Exponent::fixed(e_le, e_len), hashed, batch, flags, trace, powed_out, is_valid_out, status, workspace,
+                           /*sha=*/nullptr, static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 // RSAPubE::Var arm of the pipelined verifier (src/chip.rs:108-110)
 int32_t h2r_pipeline_verify_pkcs1v15_var(h2r_pipeline *p, const void *sig, const void *n, const void *e_limbs, uint32_t e_num_limbs,
                                          uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace,
                                          void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
-    if (!p || !sig || !n || !e_limbs || !hashed || !trace || !powed_out || !status || !workspace) return H2R_E_NULL;
-    h2r_verify_layout vl;
-    const int32_t rc = h2r_verify_layout_var(p->ctx, e_num_limbs, exp_limb_bits, &vl);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const AuxArgs va = verify_aux_args(p->ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status);
-    return pipeline_issue(p, sig, n, nullptr, 0, batch, flags, trace, vl.pow, vl.elem_stride, powed_out, status, workspace, st,
-                          [&]() -> int32_t {
-                              if (batch == 0) return H2R_OK;
-                              return launch_verify_aux(p->ctx, sig, n, hashed, batch, flags, trace, vl, powed_out, is_valid_out, status, st);
-                          }, 1, false, nullptr, 0, e_limbs, e_num_limbs, exp_limb_bits, nullptr, &va);
+    if (!e_limbs) return H2R_E_NULL;
+    return pipeline_verify(p, sig, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), hashed, batch, flags, trace, powed_out, is_valid_out,
+                           status, workspace, /*sha=*/nullptr, static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 // RSASignatureVerifier::verify_pkcs1v15_signature (src/lib.rs:183-246) as a pipelined call: the SHA-256 / hashed-message step of this
@@ -2034,23 +2080,11 @@ int32_t h2r_pipeline_signature_verifier(h2r_pipeline *p, const uint8_t *msgs, co
                                         void *hm_trace, uint64_t hm_stride, uint8_t *digest_out, uint64_t *hashed_out, void *powed_out,
                                         uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
     if (!p || !sig || !n || !hashed_out || !trace || !powed_out || !status || !workspace || (!msgs && (msg_off || fixed_len))) return H2R_E_NULL;
-    if (hm_trace && hm_stride == 0) hm_stride = HM_REGION;
-    if ((reinterpret_cast<u64>(digest_out) | reinterpret_cast<u64>(hashed_out) | reinterpret_cast<u64>(hm_trace) | hm_stride) & 15) return H2R_E_SHAPE;
-    if (hm_trace && hm_stride < HM_REGION) return H2R_E_SHAPE;
-    h2r_verify_layout vl;
-    const int32_t rc = h2r_verify_layout_fixed(p->ctx, e_le, e_len, &vl);
-    if (rc) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
     Sha256Args sa;
-    sa.msgs = msgs; sa.off = msg_off; sa.fixed_len = fixed_len; sa.batch = batch;
-    sa.digest = digest_out; sa.hashed = hashed_out; sa.region = static_cast<u8 *>(hm_trace); sa.region_stride = hm_stride;
-    sa.done = nullptr; sa.target = 0;
-    const AuxArgs va = verify_aux_args(p->ctx, sig, n, hashed_out, batch, flags, trace, vl, powed_out, is_valid_out, status);
-    return pipeline_issue(p, sig, n, e_le, e_len, batch, flags, trace, vl.pow, vl.elem_stride, powed_out, status, workspace, st,
-                          [&]() -> int32_t {
-                              if (batch == 0) return H2R_OK;
-                              return launch_verify_aux(p->ctx, sig, n, hashed_out, batch, flags, trace, vl, powed_out, is_valid_out, status, st);
-                          }, 1, false, nullptr, 0, nullptr, 0, 0, &sa, &va);
+    const int32_t rc = sha_args(msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, &sa);
+    if (rc) return rc;
+    return pipeline_verify(p, sig, n, Exponent::fixed(e_le, e_len), hashed_out, batch, flags, trace, powed_out, is_valid_out, status, workspace, &sa,
+                           static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 int32_t h2r_fresh_op_layout(const h2r_ctx *ctx, uint32_t op, uint64_t *elem_stride, uint64_t *stream_bytes, uint32_t *value_limbs) try {
@@ -2129,14 +2163,11 @@ int32_t h2r_range_decompose_batch(const h2r_ctx *ctx, const void *values, uint32
 
 uint32_t h2r_hist_len(const h2r_ctx *ctx) try { return ctx ? ctx->hist_len : 0; } H2R_CATCH_ZERO
 
-int32_t h2r_trace_lookup_hist(const h2r_ctx *ctx, const void *trace, uint64_t first_record_off, uint64_t elem_stride,
-                              uint64_t num_elems, uint32_t records_per_elem, uint32_t *hist_out, h2r_stream_t stream) try {
-    if (!ctx || !trace || !hist_out) return H2R_E_NULL;
-    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
-    if (num_elems == 0) return H2R_OK;
+namespace {
+// where the sub-limb planes of the records lie and which table rows they look up (hist_kernel, perm_kernel)
+void fill_hist_args(const h2r_ctx *ctx, const void *trace, uint64_t first_record_off, uint64_t elem_stride, uint64_t num_elems,
+                    uint32_t records_per_elem, uint32_t *hist_out, HistArgs &ha) {
     const h2r_layout &lo = ctx->layout;
-    HistArgs ha;
-    std::memset(&ha, 0, sizeof ha);
     ha.trace = static_cast<const u8 *>(trace); ha.first_record_off = first_record_off; ha.elem_stride = elem_stride;
     ha.record_stride = lo.record_stride; ha.num_elems = num_elems; ha.records_per_elem = records_per_elem;
     ha.off_q_sub = lo.plane_off[H2R_PL_Q_SUB]; ha.off_r_sub = lo.plane_off[H2R_PL_R_SUB];
@@ -2146,6 +2177,17 @@ int32_t h2r_trace_lookup_hist(const h2r_ctx *ctx, const void *trace, uint64_t fi
     ha.tab0_len = ctx->tab0_len; ha.tab1_off = ctx->tab1_off; ha.tab1_len = ctx->tab1_len;
     ha.tab2_off = ctx->tab2_off; ha.tab2_len = ctx->tab2_len; ha.hist_len = ctx->hist_len;
     ha.hist = hist_out;
+}
+}  // namespace
+
+int32_t h2r_trace_lookup_hist(const h2r_ctx *ctx, const void *trace, uint64_t first_record_off, uint64_t elem_stride,
+                              uint64_t num_elems, uint32_t records_per_elem, uint32_t *hist_out, h2r_stream_t stream) try {
+    if (!ctx || !trace || !hist_out) return H2R_E_NULL;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (num_elems == 0) return H2R_OK;
+    HistArgs ha;
+    std::memset(&ha, 0, sizeof ha);
+    fill_hist_args(ctx, trace, first_record_off, elem_stride, num_elems, records_per_elem, hist_out, ha);
     H2R_ON_DEVICE(ctx->params.device);
     ProfScope ps(H2R_KERNEL_HIST, static_cast<hipStream_t>(stream));
     hipLaunchKernelGGL(hist_kernel, dim3((unsigned)num_elems), dim3(256), ctx->hist_len * sizeof(u32),
@@ -2178,20 +2220,12 @@ int32_t h2r_trace_lookup_permutation_hist(const h2r_ctx *ctx, const void *trace,
     if ((2ull * lo.num_limbs * 8 + (u64)(lo.num_cols - 1) * lo.carry_sub_stride) / 16 > (u64)PERM_STAGE_U4) return H2R_E_UNSUPPORTED;
     PermArgs pa;
     std::memset(&pa, 0, sizeof pa);
-    HistArgs &ha = pa.h;
-    ha.trace = static_cast<const u8 *>(trace); ha.first_record_off = first_record_off; ha.elem_stride = elem_stride;
-    ha.record_stride = lo.record_stride; ha.num_elems = num_elems; ha.records_per_elem = records_per_elem;
-    ha.off_q_sub = lo.plane_off[H2R_PL_Q_SUB]; ha.off_r_sub = lo.plane_off[H2R_PL_R_SUB];
-    ha.off_carry_sub = lo.plane_off[H2R_PL_CARRY_SUB];
-    ha.L = lo.num_limbs; ha.C = lo.num_cols; ha.carry_nsub = lo.carry_nsub; ha.carry_sub_stride = lo.carry_sub_stride;
-    ha.carry_has_ov = (lo.carry_bits % lo.carry_sub_bits) ? 1 : 0;
-    ha.tab0_len = ctx->tab0_len; ha.tab1_off = ctx->tab1_off; ha.tab1_len = ctx->tab1_len;
-    ha.tab2_off = ctx->tab2_off; ha.tab2_len = ctx->tab2_len; ha.hist_len = ctx->hist_len;
+    // (hist_out nullable: the rows' multiplicities fall out of the counting pass, = h2r_trace_lookup_hist's output)
+    fill_hist_args(ctx, trace, first_record_off, elem_stride, num_elems, records_per_elem, hist_out, pa.h);
     pa.cells_per_record = h2r_lookups_per_record(ctx);
     const u64 n_cells = (u64)pa.cells_per_record * records_per_elem;
     if (n_cells >= (1ull << 31)) return H2R_E_UNSUPPORTED;
     pa.n_cells = (u32)n_cells; pa.perm = perm_out; pa.rows = rows_out;
-    ha.hist = hist_out;   // nullable: the rows' multiplicities fall out of the counting pass (= h2r_trace_lookup_hist's output)
     H2R_ON_DEVICE(ctx->params.device);
     const u64 stage_bytes = 4ull * ((2ull * lo.num_limbs * 8 + (u64)(lo.num_cols - 1) * lo.carry_sub_stride) / 16) * 16;
     const u64 same_bytes = perm_same_bytes(ctx->hist_len);   // match masks: per wave, group and table row
@@ -2352,27 +2386,6 @@ int32_t h2r_lookup_hist_values_strided(const h2r_ctx *ctx, const h2r_lookup_conf
 
 extern "C++" {
 namespace {
-int32_t lookup_hist_fresh_impl(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t op, const void *trace, uint64_t first_off,
-                               uint64_t elem_stride, uint64_t num_elems, const uint8_t *status, uint32_t *hist, h2r_stream_t stream);
-}  // namespace
-}  // extern "C++"
-
-// Every lookup of one verify_pkcs1v15_signature element that the witness holds (src/chip.rs:99-199): the range assigns inside
-// assert_in_field, the q / r limbs and carries of every mul_mod record, and the two RangeChip::assign(half, 4, 32) of the
-// encoded-message check (:170-171; the halves sit at bytes 12 and 24 of the EM region, aux_em).
-int32_t h2r_lookup_hist_verify(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const h2r_verify_layout *vl, const void *trace,
-                               uint64_t num_elems, const uint8_t *status, uint32_t *hist, h2r_stream_t stream) try {
-    if (!ctx || !cfg || !vl || !trace || !hist) return H2R_E_NULL;
-    if (vl->pow.off_records == UINT64_MAX) return H2R_E_SHAPE;   // h2r_verify_layout_compact: the q / r limbs and carries are not in this witness (h2r_lookup_hist_advice counts them from the image)
-    int32_t rc = lookup_hist_fresh_impl(ctx, cfg, H2R_OP_IS_IN_FIELD, trace, vl->off_in_field, vl->elem_stride, num_elems, status, hist, stream);   // (a failed element counts nothing, as in the two passes below)
-    if (!rc) rc = h2r_lookup_hist_records(ctx, cfg, trace, vl->pow.off_records, vl->elem_stride, num_elems, vl->pow.num_mul_mods, status, hist, stream);
-    if (!rc) rc = lookup_hist_values_impl(ctx, cfg, static_cast<const u8 *>(trace) + vl->off_em + 12, 4, 2, num_elems, vl->elem_stride, 12, 32, 4,
-                                          status, hist, stream);
-    return rc;
-} H2R_CATCH_STATUS
-
-extern "C++" {
-namespace {
 // The RangeChip::assign entries of a Fresh-op region, in the region's own geometry (fresh_sections): add(n) holds two per step
 // (c and the carry, chip.rs:279-282), sub_unchecked's difference one per limb (chip.rs:1307-1308).
 template <typename F>
@@ -2398,11 +2411,6 @@ void fresh_range_runs(const AuxGeom &g, u32 op, F &&run) {
         default: break;   // is_zero, is_equal_fresh: no range assign
     }
 }
-}  // namespace
-}  // extern "C++"
-
-extern "C++" {
-namespace {
 int32_t lookup_hist_fresh_impl(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t op, const void *trace, uint64_t first_off,
                                uint64_t elem_stride, uint64_t num_elems, const uint8_t *status, uint32_t *hist, h2r_stream_t stream) {
     if (!ctx || !cfg || !trace || !hist) return H2R_E_NULL;
@@ -2433,6 +2441,20 @@ int32_t lookup_hist_fresh_impl(const h2r_ctx *ctx, const h2r_lookup_config *cfg,
 }
 }  // namespace
 }  // extern "C++"
+
+// Every lookup of one verify_pkcs1v15_signature element that the witness holds (src/chip.rs:99-199): the range assigns inside
+// assert_in_field, the q / r limbs and carries of every mul_mod record, and the two RangeChip::assign(half, 4, 32) of the
+// encoded-message check (:170-171; the halves sit at bytes 12 and 24 of the EM region, aux_em).
+int32_t h2r_lookup_hist_verify(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const h2r_verify_layout *vl, const void *trace,
+                               uint64_t num_elems, const uint8_t *status, uint32_t *hist, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !vl || !trace || !hist) return H2R_E_NULL;
+    if (vl->pow.off_records == UINT64_MAX) return H2R_E_SHAPE;   // h2r_verify_layout_compact: the q / r limbs and carries are not in this witness (h2r_lookup_hist_advice counts them from the image)
+    int32_t rc = lookup_hist_fresh_impl(ctx, cfg, H2R_OP_IS_IN_FIELD, trace, vl->off_in_field, vl->elem_stride, num_elems, status, hist, stream);   // (a failed element counts nothing, as in the two passes below)
+    if (!rc) rc = h2r_lookup_hist_records(ctx, cfg, trace, vl->pow.off_records, vl->elem_stride, num_elems, vl->pow.num_mul_mods, status, hist, stream);
+    if (!rc) rc = lookup_hist_values_impl(ctx, cfg, static_cast<const u8 *>(trace) + vl->off_em + 12, 4, 2, num_elems, vl->elem_stride, 12, 32, 4,
+                                          status, hist, stream);
+    return rc;
+} H2R_CATCH_STATUS
 
 int32_t h2r_lookup_hist_fresh_op(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t op, const void *trace, uint64_t first_off,
                                  uint64_t elem_stride, uint64_t num_elems, uint32_t *hist, h2r_stream_t stream) try {
@@ -2936,11 +2958,6 @@ int32_t h2r_advice_row_kinds(const h2r_ctx *ctx, uint8_t *kinds_out) try {
     return H2R_OK;
 } H2R_CATCH_STATUS
 
-namespace { int32_t fixed_row_repr(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t kind, bool mont, h2r_fixed_row *out); }
-int32_t h2r_advice_fixed_row(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t kind, h2r_fixed_row *out) try {
-    if (!ctx || !out) return H2R_E_NULL;
-    return fixed_row_repr(ctx, cfg, kind, (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0, out);   // the selectors are field elements like the cells: the ctx's representation
-} H2R_CATCH_STATUS
 namespace {
 int32_t fixed_row_repr(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t kind, bool mont, h2r_fixed_row *out) {
     std::memset(out, 0, sizeof *out);
@@ -3026,6 +3043,11 @@ int32_t fixed_row_repr(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_
     return H2R_OK;
 }
 }  // namespace
+
+int32_t h2r_advice_fixed_row(const h2r_ctx *ctx, const h2r_lookup_config *cfg, uint32_t kind, h2r_fixed_row *out) try {
+    if (!ctx || !out) return H2R_E_NULL;
+    return fixed_row_repr(ctx, cfg, kind, (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0, out);   // the selectors are field elements like the cells: the ctx's representation
+} H2R_CATCH_STATUS
 
 // ---- advice rows of the Fresh-integer family (h2r_rowprog.hpp) ---------------------------------------------------------------
 namespace {
@@ -3407,55 +3429,70 @@ int32_t h2r_modpow_public_key_emit_advice(const h2r_ctx *ctx, const h2r_pow_layo
 // caller's stream, its pow rows (cells_kernel, from the operands in the workspace) on a side stream of the pipeline, next to the chains
 // of call k + 1.  No records are written.  The moduli the cells kernel needs are copied into the workspace inside the call, so x and n
 // are read in `stream` order inside the call like every other pipelined form's inputs.
-int32_t h2r_pipeline_modpow_public_key_advice(h2r_pipeline *p, const void *x, const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch,
-                                              uint32_t flags, void *in_field_trace, void *out, uint8_t *status, void *workspace,
-                                              void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
-    if (!p || !x || !n || !e_le || !in_field_trace || !status || !workspace || !advice_out) return H2R_E_NULL;
+namespace {
+// One records-free pipelined call (this form, its Var arm and the verifier's).  The forms differ in the two stages on the caller's stream:
+// `chains` (the chains and the call's witness kernel) and `short_rows` (the short row programs of the image).  `c`: the pow element whose
+// rows go to pow_dst on the side stream (c.trace: a Var element's witness -- its bits and selected operands --, else nullptr).
+int32_t pipeline_records_free(h2r_pipeline *p, hipStream_t st, const PowCall &c, AdviceDst pow_dst, const std::function<int32_t()> &chains,
+                              const std::function<int32_t()> &short_rows) {
     const h2r_ctx *ctx = p->ctx;
-    h2r_pow_layout pl;
-    int32_t rc = h2r_pow_fixed_layout(ctx, e_le, e_len, &pl);
-    if (rc) return rc;
-    u64 sec[2];
-    const u64 rows = h2r_modpow_public_key_advice_rows(ctx, &pl, sec);
-    if (!rows) return H2R_E_UNSUPPORTED;
-    AdviceDst dst;
-    if ((rc = advice_dst(ctx, advice_out, out_stride, rows, batch, &dst))) return rc;
-    if (batch == 0) return H2R_OK;
-    H2R_ON_DEVICE(ctx->params.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
+    int32_t rc;
     if (p->pending) {   // records still owed by a call of another form: they go out alone, `st` behind them
         rc = pipeline_flush(p, st);
         if (rc) return rc;
     }
     const u32 slot = p->k % p->depth;
     p->done[slot] = DoneRef{};
-    rc = h2r_modpow_public_key_batch(ctx, x, n, e_le, e_len, batch, flags, nullptr, in_field_trace, out, status, workspace, stream);
-    if (rc) return rc;
+    if ((rc = chains())) return rc;
     // the elements' moduli, where the record writers of the other forms find them too (Workspace::off_n)
     const h2r_layout &lo = ctx->layout;
-    const Workspace wp = workspace_plan(lo.limb_bytes, ctx->L, batch, pl.num_mul_mods ? pl.num_mul_mods : 1);
-    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
-    const bool shared = (flags & H2R_F_SHARED_MODULUS) != 0;
-    HIP_TRY(hipMemcpyAsync(ws + wp.off_n, n, (shared ? 1ull : batch) * ctx->L * lo.limb_bytes, hipMemcpyDeviceToDevice, st));
+    const Workspace wp = workspace_plan(lo.limb_bytes, ctx->L, c.batch, c.pl->num_mul_mods ? c.pl->num_mul_mods : 1);
+    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(c.workspace), 256));
+    HIP_TRY(hipMemcpyAsync(ws + wp.off_n, c.n, (shared(c.flags) ? 1ull : c.batch) * ctx->L * lo.limb_bytes, hipMemcpyDeviceToDevice, st));
     HIP_TRY(hipEventRecord(p->chain_done[slot], st));
-    rc = fresh_emit_advice(ctx, FRESH_IS_IN_FIELD, (flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_ASSERT_ONE, x, n, nullptr, in_field_trace, 0, 0,
-                           batch, status, &dst, nullptr, 0, stream);
-    if (rc) return rc;
+    if ((rc = short_rows())) return rc;
     hipStream_t side = p->aux[p->k & 1];
     HIP_TRY(hipStreamWaitEvent(side, p->chain_done[slot], 0));
-    rc = pow_emit_advice(ctx, &pl, ws + wp.off_n, (flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_DIRECT, nullptr, 0, workspace, batch, status,
-                         dst.at_row(sec[0]), static_cast<h2r_stream_t>(side));
+    rc = pow_emit_advice(ctx, c.pl, ws + wp.off_n, (c.flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_DIRECT, c.trace, c.trace ? c.elem_stride : 0, c.workspace,
+                         c.batch, c.status, pow_dst, static_cast<h2r_stream_t>(side));
     if (rc) return rc;
     HIP_TRY(hipEventRecord(p->trace_done[slot], side));
     p->done[slot] = DoneRef{p->trace_done[slot], 0, false};
-    p->done_stream[slot] = side;
-    p->k += 1;
-    // lazy join, as in the other forms: the NEXT call reuses the buffers of call k - depth
-    for (; p->joined + p->depth <= p->k; ++p->joined) {
-        rc = pipeline_wait_slot(p, p->joined % p->depth, st);
-        if (rc) return rc;
-    }
-    return H2R_OK;
+    return pipeline_finish_call(p, slot, side, st, /*after_chain=*/nullptr);   // (the lazy join, as in the other forms)
+}
+// the two modpow_public_key forms: image = [assert_in_field rows] [pow rows].  `call`: the pow element (trace: the Var arm's witness, else null)
+int32_t pipeline_modpow_public_key_advice(h2r_pipeline *p, const PowCall &call, void *in_field_trace, void *advice_out, uint64_t out_stride,
+                                          hipStream_t st, const std::function<int32_t()> &chains) {
+    const h2r_ctx *ctx = p->ctx;
+    u64 sec[2];
+    const u64 rows = h2r_modpow_public_key_advice_rows(ctx, call.pl, sec);
+    if (!rows) return H2R_E_UNSUPPORTED;
+    AdviceDst dst;
+    const int32_t rc = advice_dst(ctx, advice_out, out_stride, rows, call.batch, &dst);
+    if (rc) return rc;
+    if (call.batch == 0) return H2R_OK;
+    H2R_ON_DEVICE(ctx->params.device);
+    return pipeline_records_free(p, st, call, dst.at_row(sec[0]), chains, [&]() -> int32_t {
+        return fresh_emit_advice(ctx, FRESH_IS_IN_FIELD, (call.flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_ASSERT_ONE, call.a, call.n, nullptr, in_field_trace,
+                                 0, 0, call.batch, call.status, &dst, nullptr, 0, static_cast<h2r_stream_t>(st));
+    });
+}
+}  // namespace
+
+int32_t h2r_pipeline_modpow_public_key_advice(h2r_pipeline *p, const void *x, const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch,
+                                              uint32_t flags, void *in_field_trace, void *out, uint8_t *status, void *workspace,
+                                              void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (!p || !x || !n || !e_le || !in_field_trace || !status || !workspace || !advice_out) return H2R_E_NULL;
+    const Exponent e = Exponent::fixed(e_le, e_len);
+    h2r_pow_layout pl;
+    const int32_t rc = pow_layout(p->ctx, e, &pl);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PowCall call = pow_buffers(x, n, batch, flags, /*trace=*/nullptr, out, status, workspace);
+    call.pow(e, pl, pl.elem_stride);
+    return pipeline_modpow_public_key_advice(p, call, in_field_trace, advice_out, out_stride, st, [&]() -> int32_t {
+        return modpow_public_key_impl(p->ctx, e, call, in_field_trace, st);   // h2r_modpow_public_key_batch: its in-field kernel is launched inside
+    });
 } H2R_CATCH_STATUS
 
 // ---- the whole RSAChip::verify_pkcs1v15_signature element as advice rows, no records, pipelined --------------------------------
@@ -3487,16 +3524,14 @@ int32_t h2r_verify_layout_compact(const h2r_ctx *ctx, const h2r_verify_layout *f
 // three short row programs (is_eq seed, assert_in_field, the encoded-message check) of call k on the caller's stream; its pow rows
 // (cells_kernel, from the operands in the workspace) on a side stream of the pipeline, next to the chains of call k + 1.
 namespace {
-int32_t pipeline_verify_advice(h2r_pipeline *p, const void *sig, const void *n, const uint8_t *e_le, size_t e_len, const void *e_limbs,
-                               uint32_t e_num_limbs, uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *witness,
-                               void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, void *advice_out, uint64_t out_stride,
-                               h2r_stream_t stream) {
-    if (!p || !sig || !n || (!e_le && !e_limbs) || !hashed || !witness || !powed_out || !status || !workspace || !advice_out) return H2R_E_NULL;
+int32_t pipeline_verify_advice(h2r_pipeline *p, const void *sig, const void *n, const Exponent &e, const uint64_t *hashed, uint64_t batch,
+                               uint32_t flags, void *witness, void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace,
+                               void *advice_out, uint64_t out_stride, hipStream_t st) {
+    if (!p || !sig || !n || !hashed || !witness || !powed_out || !status || !workspace || !advice_out) return H2R_E_NULL;
     if (reinterpret_cast<u64>(witness) & 15) return H2R_E_SHAPE;   // (16-byte stores into the witness sections)
     const h2r_ctx *ctx = p->ctx;
-    const bool var = e_limbs != nullptr;
     h2r_verify_layout full, vl;
-    int32_t rc = var ? h2r_verify_layout_var(ctx, e_num_limbs, exp_limb_bits, &full) : h2r_verify_layout_fixed(ctx, e_le, e_len, &full);
+    int32_t rc = verify_layout(ctx, e, &full);
     if (rc) return rc;
     if ((rc = h2r_verify_layout_compact(ctx, &full, &vl))) return rc;
     const h2r_ctx::RowProg *pre, *inf, *em;
@@ -3508,50 +3543,31 @@ int32_t pipeline_verify_advice(h2r_pipeline *p, const void *sig, const void *n, 
     if ((rc = advice_dst(ctx, advice_out, out_stride, rows, batch, &dst))) return rc;
     if (batch == 0) return H2R_OK;
     H2R_ON_DEVICE(ctx->params.device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->pending) {   // records still owed by a call of another form: they go out alone, `st` behind them
-        rc = pipeline_flush(p, st);
-        if (rc) return rc;
-    }
-    const u32 slot = p->k % p->depth;
-    p->done[slot] = DoneRef{};
-    if (var) rc = run_path(ctx, CHAIN_POW_VAR, sig, nullptr, n, e_limbs, e_num_limbs, exp_limb_bits, nullptr, 1, batch, flags, vl.pow.num_mul_mods, witness,
-                           vl.elem_stride, UINT64_MAX, &vl.pow, powed_out, status, workspace, st);
-    else rc = pow_fixed_impl(ctx, sig, n, e_le, e_len, batch, flags, nullptr, powed_out, status, workspace, stream, 1);
-    if (rc) return rc;
-    if ((rc = launch_verify_aux(ctx, sig, n, hashed, batch, flags, witness, vl, powed_out, is_valid_out, status, st))) return rc;
-    const h2r_layout &lo = ctx->layout;
-    const Workspace wp = workspace_plan(lo.limb_bytes, ctx->L, batch, vl.pow.num_mul_mods ? vl.pow.num_mul_mods : 1);
-    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
-    const bool shared = (flags & H2R_F_SHARED_MODULUS) != 0;
-    HIP_TRY(hipMemcpyAsync(ws + wp.off_n, n, (shared ? 1ull : batch) * ctx->L * lo.limb_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipEventRecord(p->chain_done[slot], st));
-    RowProgArgs ra;
-    std::memset(&ra, 0, sizeof ra);
-    ra.a = sig; ra.b = n; ra.n = n; ra.a_stride = ctx->L; ra.b_stride = ra.n_stride = shared ? 0 : ctx->L;
-    ra.trace = static_cast<const u8 *>(witness); ra.elem_stride = vl.elem_stride; ra.first_off = vl.off_in_field;
-    ra.status = status; ra.batch = batch;
-    ra.dst = dst;                                   // is_eq = assign_constant(1), src/chip.rs:137
-    if ((rc = launch_row_prog(ctx, pre, ra, st))) return rc;
-    ra.dst = dst.at_row(sec[0]);                    // assert_in_field(sig, n), :106
-    if ((rc = launch_row_prog(ctx, inf, ra, st))) return rc;
-    ra.a = powed_out; ra.b = hashed; ra.b_stride = 4; ra.first_off = vl.off_em;
-    ra.dst = dst.at_row(sec[0] + sec[1] + sec[2]);  // :138-198
-    if ((rc = launch_row_prog(ctx, em, ra, st))) return rc;
-    hipStream_t side = p->aux[p->k & 1];
-    HIP_TRY(hipStreamWaitEvent(side, p->chain_done[slot], 0));
-    rc = pow_emit_advice(ctx, &vl.pow, ws + wp.off_n, (flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_DIRECT, var ? witness : nullptr, var ? vl.elem_stride : 0,
-                         workspace, batch, status, dst.at_row(sec[0] + sec[1]), static_cast<h2r_stream_t>(side));   // pow_mod_fixed_exp :111 / pow_mod :109
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(p->trace_done[slot], side));
-    p->done[slot] = DoneRef{p->trace_done[slot], 0, false};
-    p->done_stream[slot] = side;
-    p->k += 1;
-    for (; p->joined + p->depth <= p->k; ++p->joined) {
-        rc = pipeline_wait_slot(p, p->joined % p->depth, st);
-        if (rc) return rc;
-    }
-    return H2R_OK;
+    // the pow element: a Var one leaves its pow_mod's bits, selected operands and result in the witness, a Fix one nothing
+    PowCall call = pow_buffers(sig, n, batch, flags, e.var() ? witness : nullptr, powed_out, status, workspace);
+    call.check_in_field = 1;
+    call.pow(e, vl.pow, vl.elem_stride);
+    auto chains = [&]() -> int32_t {
+        const int32_t r = e.var() ? run_path(ctx, call, PowIssue::on(st)) : pow_impl(ctx, e, call, st);
+        if (r) return r;
+        return launch_verify_aux(ctx, verify_aux_args(ctx, sig, n, hashed, batch, flags, witness, vl, powed_out, is_valid_out, status), st);
+    };
+    auto short_rows = [&]() -> int32_t {
+        int32_t r;
+        RowProgArgs ra;
+        std::memset(&ra, 0, sizeof ra);
+        ra.a = sig; ra.b = n; ra.n = n; ra.a_stride = ctx->L; ra.b_stride = ra.n_stride = shared(flags) ? 0 : ctx->L;
+        ra.trace = static_cast<const u8 *>(witness); ra.elem_stride = vl.elem_stride; ra.first_off = vl.off_in_field;
+        ra.status = status; ra.batch = batch;
+        ra.dst = dst;                                   // is_eq = assign_constant(1), src/chip.rs:137
+        if ((r = launch_row_prog(ctx, pre, ra, st))) return r;
+        ra.dst = dst.at_row(sec[0]);                    // assert_in_field(sig, n), :106
+        if ((r = launch_row_prog(ctx, inf, ra, st))) return r;
+        ra.a = powed_out; ra.b = hashed; ra.b_stride = 4; ra.first_off = vl.off_em;
+        ra.dst = dst.at_row(sec[0] + sec[1] + sec[2]);  // :138-198
+        return launch_row_prog(ctx, em, ra, st);
+    };
+    return pipeline_records_free(p, st, call, dst.at_row(sec[0] + sec[1]), chains, short_rows);   // pow_mod_fixed_exp :111 / pow_mod :109
 }
 }  // namespace
 
@@ -3560,8 +3576,8 @@ int32_t h2r_pipeline_verify_pkcs1v15_advice(h2r_pipeline *p, const void *sig, co
                                             uint8_t *is_valid_out, uint8_t *status, void *workspace, void *advice_out, uint64_t out_stride,
                                             h2r_stream_t stream) try {
     if (!e_le) return H2R_E_NULL;
-    return pipeline_verify_advice(p, sig, n, e_le, e_len, nullptr, 0, 0, hashed, batch, flags, witness, powed_out, is_valid_out, status, workspace,
-                                  advice_out, out_stride, stream);
+    return pipeline_verify_advice(p, sig, n, Exponent::fixed(e_le, e_len), hashed, batch, flags, witness, powed_out, is_valid_out, status, workspace,
+                                  advice_out, out_stride, static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 // the RSAPubE::Var arm (src/chip.rs:108-110): the witness also keeps the pow_mod's exponent bits, selected operands and result
@@ -3570,8 +3586,8 @@ int32_t h2r_pipeline_verify_pkcs1v15_var_advice(h2r_pipeline *p, const void *sig
                                                 void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, void *advice_out,
                                                 uint64_t out_stride, h2r_stream_t stream) try {
     if (!e_limbs) return H2R_E_NULL;
-    return pipeline_verify_advice(p, sig, n, nullptr, 0, e_limbs, e_num_limbs, exp_limb_bits, hashed, batch, flags, witness, powed_out, is_valid_out, status,
-                                  workspace, advice_out, out_stride, stream);
+    return pipeline_verify_advice(p, sig, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), hashed, batch, flags, witness, powed_out,
+                                  is_valid_out, status, workspace, advice_out, out_stride, static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
 
 // ---- RSAPubE::Var (src/chip.rs:108-110) without records -------------------------------------------------------------------
@@ -3599,51 +3615,19 @@ int32_t h2r_pipeline_modpow_public_key_var_advice(h2r_pipeline *p, const void *x
     if (!p || !x || !e_limbs || !n || !in_field_trace || !witness || !status || !workspace || !advice_out) return H2R_E_NULL;
     if (reinterpret_cast<u64>(witness) & 15) return H2R_E_SHAPE;
     const h2r_ctx *ctx = p->ctx;
+    const Exponent e = Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits);
     h2r_pow_layout full, pl;
-    int32_t rc = h2r_pow_var_layout(ctx, e_num_limbs, exp_limb_bits, &full);
+    int32_t rc = pow_layout(ctx, e, &full);
     if (rc) return rc;
     if ((rc = h2r_pow_layout_compact(ctx, &full, &pl))) return rc;
-    u64 sec[2];
-    const u64 rows = h2r_modpow_public_key_advice_rows(ctx, &pl, sec);
-    if (!rows) return H2R_E_UNSUPPORTED;
-    AdviceDst dst;
-    if ((rc = advice_dst(ctx, advice_out, out_stride, rows, batch, &dst))) return rc;
-    if (batch == 0) return H2R_OK;
-    H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (p->pending) {   // records still owed by a call of another form: they go out alone, `st` behind them
-        rc = pipeline_flush(p, st);
-        if (rc) return rc;
-    }
-    const u32 slot = p->k % p->depth;
-    p->done[slot] = DoneRef{};
-    rc = run_path(ctx, CHAIN_POW_VAR, x, nullptr, n, e_limbs, e_num_limbs, exp_limb_bits, nullptr, 1, batch, flags, pl.num_mul_mods, witness,
-                  pl.elem_stride, pl.off_records, &pl, out, status, workspace, st);
-    if (rc) return rc;
-    if ((rc = launch_in_field(ctx, x, n, batch, flags, in_field_trace, st))) return rc;
-    const h2r_layout &lo = ctx->layout;
-    const Workspace wp = workspace_plan(lo.limb_bytes, ctx->L, batch, pl.num_mul_mods ? pl.num_mul_mods : 1);
-    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
-    const bool shared = (flags & H2R_F_SHARED_MODULUS) != 0;
-    HIP_TRY(hipMemcpyAsync(ws + wp.off_n, n, (shared ? 1ull : batch) * ctx->L * lo.limb_bytes, hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipEventRecord(p->chain_done[slot], st));
-    rc = fresh_emit_advice(ctx, FRESH_IS_IN_FIELD, (flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_ASSERT_ONE, x, n, nullptr, in_field_trace, 0, 0,
-                           batch, status, &dst, nullptr, 0, stream);
-    if (rc) return rc;
-    hipStream_t side = p->aux[p->k & 1];
-    HIP_TRY(hipStreamWaitEvent(side, p->chain_done[slot], 0));
-    rc = pow_emit_advice(ctx, &pl, ws + wp.off_n, (flags & H2R_F_SHARED_MODULUS) | H2R_ADVICE_DIRECT, witness, pl.elem_stride, workspace, batch, status,
-                         dst.at_row(sec[0]), static_cast<h2r_stream_t>(side));
-    if (rc) return rc;
-    HIP_TRY(hipEventRecord(p->trace_done[slot], side));
-    p->done[slot] = DoneRef{p->trace_done[slot], 0, false};
-    p->done_stream[slot] = side;
-    p->k += 1;
-    for (; p->joined + p->depth <= p->k; ++p->joined) {
-        rc = pipeline_wait_slot(p, p->joined % p->depth, st);
-        if (rc) return rc;
-    }
-    return H2R_OK;
+    PowCall call = pow_buffers(x, n, batch, flags, witness, out, status, workspace);
+    call.check_in_field = 1;
+    call.pow(e, pl, pl.elem_stride);
+    return pipeline_modpow_public_key_advice(p, call, in_field_trace, advice_out, out_stride, st, [&]() -> int32_t {
+        const int32_t r = run_path(ctx, call, PowIssue::on(st));
+        return r ? r : launch_in_field(ctx, x, n, batch, flags, in_field_trace, st);
+    });
 } H2R_CATCH_STATUS
 
 // ---- the hashed-message limbs of RSASignatureVerifier as advice rows (src/lib.rs:225-239) ---------------------------------
@@ -4203,5 +4187,4 @@ const char *h2r_status_str(int32_t s) try {
 const char *h2r_last_hip_error(void) try { return g_hip_err; } H2R_CATCH_STR
 
 }  // extern "C"
-
 
