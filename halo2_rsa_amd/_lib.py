@@ -17,6 +17,7 @@ H2R_OK, H2R_E_SHAPE, H2R_E_ZERO_MODULUS, H2R_E_NOT_REDUCED, H2R_E_FIELD_TOO_SMAL
     H2R_E_NULL, H2R_E_NOT_IN_FIELD, H2R_E_ASSERTION = range(10)
 FIELDS = {"bn254_fr": 0, "bn254_fq": 1, "pasta_fp": 2, "pasta_fq": 3}
 H2R_F_SHARED_MODULUS = 1
+H2R_F_KEYED_MODULI = 2   # `n` points to a host H2RKeyedModuli: a per-element index into a key table (h2r_key_table_build)
 
 
 class H2RParams(ctypes.Structure):
@@ -29,7 +30,12 @@ class H2RAdviceRepr(ctypes.Structure):
 
 
 H2R_ADVICE_COLUMNS, H2R_ADVICE_MONTGOMERY = 0x400, 0x800
-H2R_VERSION = 4
+H2R_VERSION = 5
+
+
+class H2RKeyedModuli(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("num_keys", ctypes.c_uint64),
+                ("table", ctypes.c_void_p), ("key_idx", ctypes.c_void_p)]
 
 
 class H2RPipelineInfo(ctypes.Structure):
@@ -105,6 +111,7 @@ class H2RError(RuntimeError):
 _lib = None
 EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_abi_version", "h2r_build_id", "h2r_ctx_destroy", "h2r_compute_range_lens", "h2r_rsa_compute_range_lens",
            "h2r_trace_layout", "h2r_pow_fixed_layout", "h2r_pow_var_layout", "h2r_workspace_bytes",
+           "h2r_key_table_bytes", "h2r_key_table_build", "h2r_key_table_expand",
            "h2r_mul_mod_batch", "h2r_square_mod_batch", "h2r_pow_mod_fixed_exp_batch", "h2r_pow_mod_batch",
            "h2r_modpow_public_key_batch", "h2r_modpow_public_key_var_batch", "h2r_pipeline_create", "h2r_pipeline_create_ex", "h2r_pipeline_destroy",
            "h2r_pipeline_modpow_public_key", "h2r_pipeline_modpow_public_key_advice", "h2r_pipeline_modpow_public_key_var", "h2r_pipeline_verify_pkcs1v15", "h2r_pipeline_join", "h2r_pipeline_info", "h2r_pipeline_call_plan", "h2r_exp_segment_plan", "h2r_arena_create", "h2r_arena_create_ex", "h2r_image_arena_create", "h2r_arena_region", "h2r_arena_region_bytes", "h2r_arena_region_ms", "h2r_arena_measurements", "h2r_arena_destroy", "h2r_verify_layout_fixed", "h2r_verify_pkcs1v15_batch",
@@ -176,6 +183,10 @@ def lib():
     L.h2r_pow_var_layout.argtypes = [vp, u32, u32, ctypes.POINTER(H2RPowLayout)]
     L.h2r_workspace_bytes.argtypes = [vp, u64, u32]
     L.h2r_workspace_bytes.restype = u64
+    L.h2r_key_table_bytes.argtypes = [vp, u64]
+    L.h2r_key_table_bytes.restype = u64
+    L.h2r_key_table_build.argtypes = [vp, vp, u64, vp, vp, vp]
+    L.h2r_key_table_expand.argtypes = [vp, vp, u64, vp, u64, vp, vp]
     L.h2r_mul_mod_batch.argtypes = [vp, vp, vp, vp, u64, u32, vp, vp, vp, vp, vp]
     L.h2r_square_mod_batch.argtypes = [vp, vp, vp, u64, u32, vp, vp, vp, vp, vp]
     L.h2r_pow_mod_fixed_exp_batch.argtypes = [vp, vp, vp, ctypes.c_char_p, ctypes.c_size_t, u64, u32, vp, vp, vp, vp, vp]

@@ -74,6 +74,77 @@ class AssignedInteger:
         return self.limbs_dev.data_ptr()
 
 
+class KeyTable:
+    """The moduli of a few keys with the constants of their Barrett reduction, built once on the device (h2r_key_table_build)
+    and then named per element by index: `select(key_idx)` gives what the keyed methods take as `n`.  .status: uint8 [num_keys],
+    H2R_OK or H2R_E_ZERO_MODULUS per key.  The table must stay unchanged while calls that name it are in flight."""
+
+    def __init__(self, chip: "BigIntChip", moduli):
+        self.chip = chip
+        keys = chip.assign_integer(moduli)
+        assert keys.num_limbs() == chip.num_limbs
+        self.num_keys = keys.batch
+        dev = "cuda:%d" % chip.device
+        nbytes = int(lib().h2r_key_table_bytes(chip._ctx, self.num_keys))
+        if nbytes == 0:
+            check(_lib.H2R_E_UNSUPPORTED, "h2r_key_table_bytes")
+        self.buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        self.status = torch.zeros(max(self.num_keys, 1), dtype=torch.uint8, device=dev)[:self.num_keys]
+        check(lib().h2r_key_table_build(chip._ctx, keys.data_ptr(), self.num_keys, self.buf.data_ptr(), self.status.data_ptr(),
+                                        chip._stream()), "h2r_key_table_build")
+        self._keys = keys   # alive until the stream has run the build
+
+    def copy(self) -> "KeyTable":
+        """A device-to-device copy of the table (it is position-independent)."""
+        t = KeyTable.__new__(KeyTable)
+        t.chip, t.num_keys, t.buf, t.status, t._keys = self.chip, self.num_keys, self.buf.clone(), self.status, self._keys
+        return t
+
+    def select(self, key_idx) -> "KeyedModuli":
+        """key_idx: one key index per element (a sequence, or an int32 device tensor that is used in place -- a staging buffer the
+        caller may refill in stream order once the call it was given to has returned)."""
+        return KeyedModuli(self, key_idx)
+
+
+class KeyedModuli:
+    """Per-element moduli given as indices into a KeyTable (H2R_F_KEYED_MODULI): accepted wherever a keyed method takes `n`."""
+
+    def __init__(self, table: KeyTable, key_idx):
+        self.table = table
+        dev = "cuda:%d" % table.chip.device
+        if isinstance(key_idx, torch.Tensor):
+            assert key_idx.is_cuda and key_idx.dtype == torch.int32 and key_idx.dim() == 1 and key_idx.is_contiguous()
+            self.key_idx = key_idx
+        else:
+            self.key_idx = torch.from_numpy(np.ascontiguousarray(np.asarray(key_idx, dtype=np.uint32).view(np.int32))).to(dev)
+        self.limb_width = table.chip.limb_width
+        self._c = _lib.H2RKeyedModuli(ctypes.sizeof(_lib.H2RKeyedModuli), 0, table.num_keys, table.buf.data_ptr(), self.key_idx.data_ptr())
+
+    @property
+    def batch(self):
+        return self.key_idx.shape[0]
+
+    def num_limbs(self):
+        return self.table.chip.num_limbs
+
+    def data_ptr(self):
+        """The address of the host h2r_keyed_moduli: what a keyed export takes as `n`."""
+        return ctypes.addressof(self._c)
+
+    def expand(self) -> AssignedInteger:
+        """Per-element moduli (h2r_key_table_expand) for the exports that are not keyed: the audits and the emitters."""
+        chip = self.table.chip
+        out = chip._new_limbs(self.batch)
+        check(lib().h2r_key_table_expand(chip._ctx, self.table.buf.data_ptr(), self.table.num_keys, self.key_idx.data_ptr(), self.batch,
+                                         out.data_ptr(), chip._stream()), "h2r_key_table_expand")
+        return AssignedInteger(out, chip.limb_width)
+
+
+def _plain_moduli(n):
+    """What an export that is not keyed takes: the per-element moduli of a keyed `n`."""
+    return n.expand() if isinstance(n, KeyedModuli) else n
+
+
 class Trace:
     """Witness records of a batch call, resident in HBM, plus the layout needed to walk them."""
 
@@ -172,6 +243,7 @@ class InFieldTrace:
 
     def emit_advice(self, x: "AssignedInteger", n: "AssignedInteger") -> torch.Tensor:
         """assert_in_field(x, n) as advice rows (is_less_than's cells + the assert_one row): uint8 [batch, rows * 160]."""
+        n = _plain_moduli(n)
         flags = _lib.H2R_F_SHARED_MODULUS if (n.batch == 1 and self.batch != 1) else 0
         return self.chip.fresh_op_emit_advice(_lib.FRESH_OPS.index("is_in_field"), x, n, None, flags, self.buf, 0, self.elem_stride,
                                               self.batch, None, assert_one=True)
@@ -203,6 +275,7 @@ class BatchResult:
         bad = torch.empty(batch, dtype=torch.int32, device=dev)
         first = torch.empty(batch, dtype=torch.int32, device=dev)
         kind, a, b, n, eb = self.inputs
+        n = _plain_moduli(n)   # (a keyed result expands for itself: the checks take per-element moduli)
         flags = chip._flags(n, batch)
         if kind == "mul_mod":
             check(lib().h2r_mul_mod_trace_check(chip._ctx, a.data_ptr(), b.data_ptr(), n.data_ptr(), flags, self.trace.buf.data_ptr(), batch,
@@ -222,6 +295,7 @@ class BatchResult:
         direct=True (H2R_ADVICE_DIRECT): the cells are recomputed from the operands, the records are not read -- a pow result
         made with want_trace=False (and a workspace) has only this form."""
         kind, a, b, n, eb = self.inputs
+        n = _plain_moduli(n)
         chip = self.trace.chip if self.trace is not None else self.chip
         batch, dev = a.batch, a.limbs_dev.device
         rows = int(lib().h2r_advice_rows(chip._ctx))
@@ -256,6 +330,7 @@ class BatchResult:
         [pow_mod_fixed_exp], uint8 [batch, rows * 160] in HBM.  A result made with want_trace=False (chain + in-field witness only)
         gets its pow rows written directly from the operands; direct=True asks for that with records present too."""
         kind, x, _, n, eb = self.inputs
+        n = _plain_moduli(n)
         if kind == "mul_mod" or self.in_field is None or self.workspace is None:
             raise ValueError("emit_modpow_advice: a modpow_public_key result with its in-field witness and workspace")
         chip = self.trace.chip if self.trace is not None else self.chip
@@ -376,7 +451,7 @@ class BigIntChip:
     def assign_integer(self, integer) -> AssignedInteger:
         """big_integer/chip.rs:62-82: here = move the limbs into HBM (the range-check sub-limbs of
         assigned inputs are the limbs' own bytes)."""
-        if isinstance(integer, AssignedInteger):
+        if isinstance(integer, (AssignedInteger, KeyedModuli)):   # (keyed moduli are assigned once, in their key table)
             return integer
         if isinstance(integer, UnassignedInteger):
             arr = integer.limbs
@@ -471,7 +546,14 @@ class BigIntChip:
     def _new_limbs(self, batch):
         return torch.empty((batch, self.num_limbs), dtype=self.torch_dtype, device="cuda:%d" % self.device)
 
-    def _flags(self, n: AssignedInteger, batch: int):
+    def key_table(self, moduli) -> KeyTable:
+        """The key table of `moduli` (integers, an UnassignedInteger or an AssignedInteger, one row per key): many elements, few keys."""
+        return KeyTable(self, moduli)
+
+    def _flags(self, n, batch: int):
+        if isinstance(n, KeyedModuli):
+            assert n.batch == batch and n.table.chip.bits_len == self.bits_len and n.table.chip.limb_width == self.limb_width
+            return _lib.H2R_F_KEYED_MODULI
         if n.batch == 1 and batch != 1:
             return _lib.H2R_F_SHARED_MODULUS
         assert n.batch == batch

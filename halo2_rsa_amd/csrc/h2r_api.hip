@@ -248,6 +248,47 @@ int32_t exp_to_bits(const uint8_t *e_le, size_t e_len, ExpBits *eb, u32 *T) {
 }
 
 inline bool shared(u32 flags) { return (flags & H2R_F_SHARED_MODULUS) != 0; }
+inline bool keyed(u32 flags) { return (flags & H2R_F_KEYED_MODULI) != 0; }
+// The first statement of every export that takes `n` and `flags`: with H2R_F_KEYED_MODULI `n` is a HOST struct, which an export that is
+// not keyed must refuse before anything treats it as device memory, and which a keyed export checks here once (run_path trusts it).
+int32_t moduli_guard(u32 flags, const void *n, bool keyed_export) {
+    if (!keyed(flags)) return H2R_OK;
+    if (!keyed_export || shared(flags)) return H2R_E_UNSUPPORTED;
+    if (!n) return H2R_E_NULL;
+    const h2r_keyed_moduli *km = static_cast<const h2r_keyed_moduli *>(n);
+    if (km->struct_size != sizeof(h2r_keyed_moduli) || km->num_keys >= 0xffffffffull) return H2R_E_UNSUPPORTED;
+    if (!km->table || !km->key_idx) return H2R_E_NULL;
+    if (reinterpret_cast<u64>(km->table) & 255) return H2R_E_SHAPE;
+    return H2R_OK;
+}
+// The key table (h2r_key_table_build; position-independent: both planes sit at offsets that follow from the shape and num_keys alone):
+//   [num_keys + 1][raw_stride] digits   the keys' raw limbs, zero-padded to a 16-byte multiple -- what the kernels next to the chain read
+//   [num_keys + 1][chain_pre_words(K)]  per key [shift, status, 0, 0], n'[K], mu'[K] (recip_kernel's format) for the K of the chain build
+// Entry num_keys is the sentinel: a zero modulus with status H2R_E_SHAPE, what every reader clamps an index out of range to.
+struct KeyTablePlan { u32 K, raw_stride; u64 off_pre, total; };
+KeyTablePlan key_table_plan(const h2r_ctx *c, u64 num_keys) {
+    KeyTablePlan t;
+    t.K = chain_digits(c->K);
+    t.raw_stride = (u32)round_up(c->K, 4);
+    t.off_pre = round_up((num_keys + 1) * t.raw_stride * 4ull, 256);
+    t.total = t.off_pre + round_up((num_keys + 1) * chain_pre_words(t.K) * 4ull, 256);
+    return t;
+}
+// What the kernels of a keyed call get: the index of the elements from `off` on and the table's two planes.
+struct KeyedView { const u32 *idx, *raw, *pre; u32 num_keys, raw_stride; };
+KeyedView keyed_view(const h2r_ctx *c, const void *n, u64 off) {
+    const h2r_keyed_moduli *km = static_cast<const h2r_keyed_moduli *>(n);
+    const KeyTablePlan t = key_table_plan(c, km->num_keys);
+    const u8 *tab = static_cast<const u8 *>(km->table);
+    return KeyedView{km->key_idx + off, reinterpret_cast<const u32 *>(tab), reinterpret_cast<const u32 *>(tab + t.off_pre), (u32)km->num_keys, t.raw_stride};
+}
+// The moduli of an in-field / encoded-message kernel: per element, shared, or -- keyed -- the table's raw plane through the clamped index.
+void aux_moduli(const h2r_ctx *c, const void *n, u32 flags, u64 off, AuxArgs &aa) {
+    if (keyed(flags)) {
+        const KeyedView kv = keyed_view(c, n, off);
+        aa.n = kv.raw; aa.n_stride = kv.raw_stride / (c->layout.limb_width / 32); aa.key_idx = kv.idx; aa.num_keys = kv.num_keys;
+    } else { aa.n = n; aa.n_stride = shared(flags) ? 0 : c->L; aa.key_idx = nullptr; aa.num_keys = 0; }
+}
 
 // The exponent of a pow call: one fixed exponent for the whole call (RSAPubE::Fix, BigIntChip::pow_mod_fixed_exp) or per-element
 // limbs (RSAPubE::Var, BigIntChip::pow_mod, chip.rs:664-696).
@@ -291,6 +332,7 @@ struct PowCall {
     void *workspace = nullptr;            // nullable in a plain stream-ordered call: stream-ordered scratch
     // where the shared modulus' Barrett constants / the elements' moduli go when `workspace` is a slice of a larger call's plan (slice())
     void *shared_pre = nullptr, *n_copy_at = nullptr;
+    u64 key_off = 0;                      // keyed moduli (flags; `n` is the caller's h2r_keyed_moduli): the first element's position in key_idx
 
     // x ^ exponent, an element of layout `pl_` every `stride` bytes of the trace (the pow element itself, or one inside a verify element)
     void pow(const Exponent &e_, const h2r_pow_layout &pl_, u64 stride) {
@@ -303,7 +345,8 @@ struct PowCall {
         PowCall s = *this;
         s.batch = nb;
         s.a = static_cast<const u8 *>(a) + off * in_bytes;
-        s.n = static_cast<const u8 *>(n) + (shared(flags) ? 0 : off * in_bytes);
+        if (keyed(flags)) s.key_off = key_off + off;   // (n stays the caller's h2r_keyed_moduli)
+        else s.n = static_cast<const u8 *>(n) + (shared(flags) ? 0 : off * in_bytes);
         s.e = e.at(off, c->layout.limb_bytes);
         s.trace = static_cast<u8 *>(trace) + off * elem_stride;
         s.out = out ? static_cast<u8 *>(out) + off * in_bytes : nullptr;
@@ -355,6 +398,11 @@ int32_t run_path(const h2r_ctx *c, const PowCall &call, const PowIssue &how) {
     ca.a = static_cast<const u32 *>(call.a); ca.b = static_cast<const u32 *>(call.b); ca.n = static_cast<const u32 *>(call.n);
     ca.e_limbs = static_cast<const u32 *>(call.e.limbs);
     ca.n_stride = shared(flags) ? 0 : c->K;
+    if (keyed(flags)) {   // (checked by the export: moduli_guard)
+        const KeyedView kv = keyed_view(c, call.n, call.key_off);
+        ca.n = nullptr; ca.n_stride = 0;
+        ca.key_idx = kv.idx; ca.key_raw = kv.raw; ca.key_pre = kv.pre; ca.num_keys = kv.num_keys; ca.key_raw_stride = kv.raw_stride;
+    }
     ca.batch = batch; ca.kreal = c->K; ca.mode = call.mode; ca.T = T ? T : 1;
     ca.e_num_limbs = call.e.num_limbs; ca.exp_limb_bits = call.e.limb_bits; ca.digits_per_limb = lo.limb_width / 32;
     ca.check_in_field = call.check_in_field;
@@ -368,7 +416,8 @@ int32_t run_path(const h2r_ctx *c, const PowCall &call, const PowIssue &how) {
     }
     ca.e = call.e.bits;
     if (how.seg) { ca.state = reinterpret_cast<u32 *>(ws + wp.off_state); ca.bit_lo = how.seg->bit_lo; ca.bit_hi = how.seg->bit_hi; ca.t_base = how.seg->t_lo; }
-    u8 *n_copy = records ? (call.n_copy_at ? static_cast<u8 *>(call.n_copy_at) : ws + wp.off_n) : nullptr;
+    // (a keyed call always leaves the elements' moduli in the workspace: whatever follows the call finds them there, not behind an index)
+    u8 *n_copy = (records || keyed(flags)) ? (call.n_copy_at ? static_cast<u8 *>(call.n_copy_at) : ws + wp.off_n) : nullptr;
     ca.n_copy = reinterpret_cast<u32 *>(n_copy);
     // 128-digit chains (RSA-4096 at 64-bit limbs) are the longer leg next to their record kernel: their waves get issue
     // priority there (1.00 -> 1.05 M assigns/s; no effect measured for the shorter chains)
@@ -550,6 +599,40 @@ int32_t verify_layout(const h2r_ctx *ctx, const Exponent &e, h2r_verify_layout *
 extern "C" {
 
 uint32_t h2r_abi_version(void) { return H2R_VERSION; }
+
+// ---- keyed moduli: the key table ---------------------------------------------------------------------------------------------
+uint64_t h2r_key_table_bytes(const h2r_ctx *ctx, uint64_t num_keys) try {
+    if (!ctx || num_keys >= 0xffffffffull) return 0;
+    return key_table_plan(ctx, num_keys).total;
+} H2R_CATCH_ZERO
+
+int32_t h2r_key_table_build(const h2r_ctx *ctx, const void *n_keys, uint64_t num_keys, void *table, uint8_t *key_status, h2r_stream_t stream) try {
+    if (!ctx || !table || (!n_keys && num_keys)) return H2R_E_NULL;
+    if (ctx->params.device < 0 || num_keys >= 0xffffffffull || ctx->K > 128) return H2R_E_UNSUPPORTED;
+    if (reinterpret_cast<u64>(table) & 255) return H2R_E_SHAPE;
+    const KeyTablePlan t = key_table_plan(ctx, num_keys);
+    H2R_ON_DEVICE(ctx->params.device);
+    u8 *tab = static_cast<u8 *>(table);
+    HIP_TRY(launch_key_table_shape(static_cast<const u32 *>(n_keys), ctx->K, num_keys, reinterpret_cast<u32 *>(tab), t.raw_stride,
+                                   reinterpret_cast<u32 *>(tab + t.off_pre), key_status, static_cast<hipStream_t>(stream)));
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_key_table_expand(const h2r_ctx *ctx, const void *table, uint64_t num_keys, const uint32_t *key_idx, uint64_t batch, void *n_out,
+                             h2r_stream_t stream) try {
+    if (!ctx || !table || !key_idx || !n_out) return H2R_E_NULL;
+    if (ctx->params.device < 0 || num_keys >= 0xffffffffull) return H2R_E_UNSUPPORTED;
+    if (reinterpret_cast<u64>(table) & 255) return H2R_E_SHAPE;
+    if (batch == 0) return H2R_OK;
+    const u64 digits = batch * ctx->K;
+    if (digits >= (1ull << 39)) return H2R_E_UNSUPPORTED;   // (the grid is 32-bit)
+    const KeyTablePlan t = key_table_plan(ctx, num_keys);
+    H2R_ON_DEVICE(ctx->params.device);
+    hipLaunchKernelGGL(key_expand_kernel, dim3((unsigned)((digits + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const u32 *>(table), t.raw_stride, (u32)num_keys, key_idx, batch, ctx->K, static_cast<u32 *>(n_out));
+    HIP_TRY(hipGetLastError());
+    return H2R_OK;
+} H2R_CATCH_STATUS
 
 int32_t h2r_ctx_create(const h2r_params *params, h2r_ctx **out) try { return h2r_ctx_create_ex(params, nullptr, out); } H2R_CATCH_STATUS
 
@@ -1414,7 +1497,7 @@ AuxArgs verify_aux_args(const h2r_ctx *ctx, const void *sig, const void *n, cons
                         void *trace, const h2r_verify_layout &vl, void *powed_out, uint8_t *is_valid_out, uint8_t *status) {
     AuxArgs aa;
     std::memset(&aa, 0, sizeof aa);
-    aa.x = sig; aa.n = n; aa.n_stride = shared(flags) ? 0 : ctx->L;
+    aa.x = sig; aux_moduli(ctx, n, flags, 0, aa);
     aa.hashed = hashed; aa.powed = powed_out; aa.batch = batch; aa.L = ctx->L;
     aa.trace = static_cast<u8 *>(trace); aa.elem_stride = vl.elem_stride; aa.off_in_field = vl.off_in_field; aa.off_em = vl.off_em;
     aa.is_valid = is_valid_out; aa.status = status;
@@ -1424,7 +1507,9 @@ AuxArgs verify_aux_args(const h2r_ctx *ctx, const void *sig, const void *n, cons
 int32_t launch_verify_aux(const h2r_ctx *ctx, const AuxArgs &aa, hipStream_t st) {
     ProfScope ps(H2R_KERNEL_AUX, st, true);   // dispatch-stamped events: no marker packets on the caller's stream
     const AuxGeom ag(ctx->L, 64);
-    hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)aa.batch), dim3(64), (unsigned)(ag.in_field_sz() + ag.em_sz()), st, ps.a, ps.b, 0, aa);
+    const unsigned lds = (unsigned)(ag.in_field_sz() + ag.em_sz());
+    if (aa.key_idx) hipExtLaunchKernelGGL((aux_kernel<64, true>), dim3((unsigned)aa.batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
+    else hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)aa.batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
     HIP_TRY(hipGetLastError());
     return H2R_OK;
 }
@@ -1435,7 +1520,7 @@ int32_t in_field_args(const h2r_ctx *ctx, const void *x, const void *n, uint64_t
     const int32_t rc = h2r_fresh_op_layout(ctx, FRESH_IS_IN_FIELD, &es, nullptr, nullptr);
     if (rc) return rc;
     std::memset(aa, 0, sizeof *aa);
-    aa->x = x; aa->n = n; aa->n_stride = shared(flags) ? 0 : ctx->L;
+    aa->x = x; aux_moduli(ctx, n, flags, 0, *aa);
     aa->batch = batch; aa->L = ctx->L;
     aa->trace = static_cast<u8 *>(in_field_trace); aa->elem_stride = es; aa->off_in_field = 0;
     const AuxGeom ag(ctx->L, ctx->layout.limb_width);
@@ -1449,7 +1534,10 @@ int32_t launch_in_field(const h2r_ctx *ctx, const void *x, const void *n, uint64
     if (rc) return rc;
     H2R_ON_DEVICE(ctx->params.device);
     ProfScope ps(H2R_KERNEL_AUX, st, true);
-    if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
+    if (aa.key_idx) {
+        if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64, true>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
+        else hipExtLaunchKernelGGL((aux_kernel<32, true>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
+    } else if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
     else hipExtLaunchKernelGGL((aux_kernel<32>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
     HIP_TRY(hipGetLastError());
     return H2R_OK;
@@ -1585,7 +1673,8 @@ int32_t issue_as_steps(h2r_pipeline *p, const PowCall &call, hipStream_t st, con
             AuxArgs va;
             if (fold_verify) {   // the slice of the call this launch's chains cover
                 va = *verify_aux;
-                va.x = sub.a; va.n = sub.n;
+                va.x = sub.a;
+                if (va.key_idx) va.key_idx = verify_aux->key_idx + off; else va.n = sub.n;
                 va.hashed = verify_aux->hashed + off * 4;
                 va.powed = static_cast<const u8 *>(verify_aux->powed) + off * ((u64)ctx->K * 4);
                 va.batch = nb;
@@ -1931,6 +2020,7 @@ int32_t h2r_pipeline_join(h2r_pipeline *p, h2r_stream_t stream) try {
 int32_t h2r_mul_mod_batch(const h2r_ctx *ctx, const void *a, const void *b, const void *n, uint64_t batch,
                           uint32_t flags, void *trace, void *r_out, uint8_t *status, void *workspace,
                           h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!ctx || !b) return H2R_E_NULL;
     PowCall call = pow_buffers(a, n, batch, flags, trace, r_out, status, workspace);   // (one mul_mod per element: PowCall's defaults)
     call.b = b; call.elem_stride = ctx->layout.record_stride;
@@ -1945,6 +2035,7 @@ int32_t h2r_square_mod_batch(const h2r_ctx *ctx, const void *a, const void *n, u
 int32_t h2r_pow_mod_fixed_exp_batch(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le,
                                     size_t e_len, uint64_t batch, uint32_t flags, void *trace, void *out,
                                     uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!ctx) return H2R_E_NULL;
     return pow_impl(ctx, Exponent::fixed(e_le, e_len), pow_buffers(x, n, batch, flags, trace, out, status, workspace), static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
@@ -1952,6 +2043,7 @@ int32_t h2r_pow_mod_fixed_exp_batch(const h2r_ctx *ctx, const void *x, const voi
 int32_t h2r_pow_mod_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs,
                           uint32_t exp_limb_bits, const void *n, uint64_t batch, uint32_t flags, void *trace,
                           void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!ctx || !e_limbs) return H2R_E_NULL;
     return pow_impl(ctx, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), pow_buffers(x, n, batch, flags, trace, out, status, workspace),
                     static_cast<hipStream_t>(stream));
@@ -1960,6 +2052,7 @@ int32_t h2r_pow_mod_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs
 int32_t h2r_modpow_public_key_batch(const h2r_ctx *ctx, const void *x, const void *n, const uint8_t *e_le,
                                     size_t e_len, uint64_t batch, uint32_t flags, void *trace, void *in_field_trace,
                                     void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!ctx) return H2R_E_NULL;
     return modpow_public_key_impl(ctx, Exponent::fixed(e_le, e_len), pow_buffers(x, n, batch, flags, trace, out, status, workspace), in_field_trace,
                                   static_cast<hipStream_t>(stream));
@@ -1968,6 +2061,7 @@ int32_t h2r_modpow_public_key_batch(const h2r_ctx *ctx, const void *x, const voi
 int32_t h2r_modpow_public_key_var_batch(const h2r_ctx *ctx, const void *x, const void *e_limbs, uint32_t e_num_limbs,
                                         uint32_t exp_limb_bits, const void *n, uint64_t batch, uint32_t flags, void *trace,
                                         void *in_field_trace, void *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!ctx || !e_limbs) return H2R_E_NULL;
     return modpow_public_key_impl(ctx, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits),
                                   pow_buffers(x, n, batch, flags, trace, out, status, workspace), in_field_trace, static_cast<hipStream_t>(stream));
@@ -1985,6 +2079,7 @@ int32_t h2r_verify_layout_var(const h2r_ctx *ctx, uint32_t e_num_limbs, uint32_t
 int32_t h2r_verify_pkcs1v15_batch(const h2r_ctx *ctx, const void *sig, const void *n, const uint8_t *e_le, size_t e_len,
                                   const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace, void *powed_out,
                                   uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     return verify_impl(ctx, sig, n, Exponent::fixed(e_le, e_len), hashed, batch, flags, trace, powed_out, is_valid_out, status, workspace,
                        static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
@@ -1992,6 +2087,7 @@ int32_t h2r_verify_pkcs1v15_batch(const h2r_ctx *ctx, const void *sig, const voi
 int32_t h2r_verify_pkcs1v15_var_batch(const h2r_ctx *ctx, const void *sig, const void *n, const void *e_limbs, uint32_t e_num_limbs,
                                       uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace,
                                       void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!e_limbs) return H2R_E_NULL;
     return verify_impl(ctx, sig, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), hashed, batch, flags, trace, powed_out, is_valid_out,
                        status, workspace, static_cast<hipStream_t>(stream));
@@ -2033,6 +2129,7 @@ int32_t h2r_signature_verifier_batch(const h2r_ctx *ctx, const uint8_t *msgs, co
                                      const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch, uint32_t flags, void *trace,
                                      void *hm_trace, uint64_t hm_stride, uint8_t *digest_out, uint64_t *hashed_out, void *powed_out,
                                      uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!hashed_out) return H2R_E_NULL;
     if (ctx && (ctx->layout.limb_width != 64 || ctx->L < 9)) return H2R_E_SHAPE;   // before any launch: RSAChip::LIMB_WIDTH
     const int32_t rc = h2r_sha256_hashed_msg_batch(ctx, msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, stream);
@@ -2043,6 +2140,7 @@ int32_t h2r_signature_verifier_batch(const h2r_ctx *ctx, const uint8_t *msgs, co
 int32_t h2r_pipeline_modpow_public_key(h2r_pipeline *p, const void *x, const void *n, const uint8_t *e_le, size_t e_len,
                                        uint64_t batch, uint32_t flags, void *trace, void *in_field_trace, void *out,
                                        uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     return pipeline_modpow_public_key(p, x, n, Exponent::fixed(e_le, e_len), batch, flags, trace, in_field_trace, out, status, workspace,
                                       static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
@@ -2051,6 +2149,7 @@ int32_t h2r_pipeline_modpow_public_key(h2r_pipeline *p, const void *x, const voi
 int32_t h2r_pipeline_modpow_public_key_var(h2r_pipeline *p, const void *x, const void *e_limbs, uint32_t e_num_limbs, uint32_t exp_limb_bits,
                                            const void *n, uint64_t batch, uint32_t flags, void *trace, void *in_field_trace, void *out,
                                            uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!e_limbs) return H2R_E_NULL;
     return pipeline_modpow_public_key(p, x, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), batch, flags, trace, in_field_trace, out,
                                       status, workspace, static_cast<hipStream_t>(stream));
@@ -2059,6 +2158,7 @@ int32_t h2r_pipeline_modpow_public_key_var(h2r_pipeline *p, const void *x, const
 int32_t h2r_pipeline_verify_pkcs1v15(h2r_pipeline *p, const void *sig, const void *n, const uint8_t *e_le, size_t e_len,
                                      const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace, void *powed_out,
                                      uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     return pipeline_verify(p, sig, n, Exponent::fixed(e_le, e_len), hashed, batch, flags, trace, powed_out, is_valid_out, status, workspace,
                            /*sha=*/nullptr, static_cast<hipStream_t>(stream));
 } H2R_CATCH_STATUS
@@ -2067,6 +2167,7 @@ int32_t h2r_pipeline_verify_pkcs1v15(h2r_pipeline *p, const void *sig, const voi
 int32_t h2r_pipeline_verify_pkcs1v15_var(h2r_pipeline *p, const void *sig, const void *n, const void *e_limbs, uint32_t e_num_limbs,
                                          uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *trace,
                                          void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!e_limbs) return H2R_E_NULL;
     return pipeline_verify(p, sig, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), hashed, batch, flags, trace, powed_out, is_valid_out,
                            status, workspace, /*sha=*/nullptr, static_cast<hipStream_t>(stream));
@@ -2079,6 +2180,7 @@ int32_t h2r_pipeline_signature_verifier(h2r_pipeline *p, const uint8_t *msgs, co
                                         const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch, uint32_t flags, void *trace,
                                         void *hm_trace, uint64_t hm_stride, uint8_t *digest_out, uint64_t *hashed_out, void *powed_out,
                                         uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!p || !sig || !n || !hashed_out || !trace || !powed_out || !status || !workspace || (!msgs && (msg_off || fixed_len))) return H2R_E_NULL;
     Sha256Args sa;
     const int32_t rc = sha_args(msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, &sa);
@@ -2102,6 +2204,7 @@ int32_t h2r_fresh_op_layout(const h2r_ctx *ctx, uint32_t op, uint64_t *elem_stri
 
 int32_t h2r_fresh_op_batch(const h2r_ctx *ctx, uint32_t op, const void *a, const void *b, const void *n, uint64_t batch,
                            uint32_t flags, void *trace, void *value_out, uint8_t *flag_out, uint8_t *status, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !a || !trace || !status) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     u64 es; u32 vl;
@@ -2837,6 +2940,7 @@ int32_t launch_cells(const h2r_ctx *ctx, CellsArgs &ca, hipStream_t st) {
 
 int32_t h2r_mul_mod_emit_advice(const h2r_ctx *ctx, const void *a, const void *b, const void *n, uint32_t flags, const void *trace,
                                 uint64_t batch, const uint8_t *status, void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !a || !b || !n || !trace || !advice_out) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     AdviceDst dst;
@@ -2922,6 +3026,7 @@ int32_t pow_emit_advice(const h2r_ctx *ctx, const h2r_pow_layout *pl, const void
 int32_t h2r_pow_trace_emit_advice(const h2r_ctx *ctx, const h2r_pow_layout *pl, const void *n, uint32_t flags, const void *trace,
                                   uint64_t elem_stride, const void *workspace, uint64_t batch, const uint8_t *status,
                                   void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !pl || !n || !workspace || !advice_out) return H2R_E_NULL;
     AdviceDst dst;
     if (const int32_t rc = advice_dst(ctx, advice_out, out_stride, h2r_pow_advice_rows(ctx, pl), batch, &dst)) return rc;
@@ -3179,6 +3284,7 @@ int32_t fresh_emit_advice(const h2r_ctx *ctx, uint32_t op, uint32_t flags, const
 int32_t h2r_fresh_op_emit_advice(const h2r_ctx *ctx, uint32_t op, uint32_t flags, const void *a, const void *b, const void *n,
                                  const void *trace, uint64_t first_off, uint64_t elem_stride, uint64_t batch, const uint8_t *status,
                                  void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     return fresh_emit_advice(ctx, op, flags, a, b, n, trace, first_off, elem_stride, batch, status, nullptr, advice_out, out_stride, stream);
 } H2R_CATCH_STATUS
 
@@ -3254,6 +3360,7 @@ int32_t h2r_verify_row_kinds(const h2r_ctx *ctx, const h2r_verify_layout *vl, ui
 int32_t h2r_verify_emit_advice(const h2r_ctx *ctx, const h2r_verify_layout *vl, const void *sig, const void *n, const uint64_t *hashed,
                                const void *powed, uint32_t flags, const void *trace, const void *workspace, uint64_t batch,
                                const uint8_t *status, void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !vl || !sig || !n || !hashed || !powed || !trace || !workspace || !advice_out) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     const h2r_ctx::RowProg *pre, *inf, *em;
@@ -3408,6 +3515,7 @@ uint64_t h2r_modpow_public_key_advice_rows(const h2r_ctx *ctx, const h2r_pow_lay
 int32_t h2r_modpow_public_key_emit_advice(const h2r_ctx *ctx, const h2r_pow_layout *pl, const void *x, const void *n, uint32_t flags,
                                           const void *in_field_trace, const void *trace, const void *workspace, uint64_t batch,
                                           const uint8_t *status, void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !pl || !x || !n || !in_field_trace || !workspace || !advice_out) return H2R_E_NULL;
     u64 sec[2];
     const u64 rows = h2r_modpow_public_key_advice_rows(ctx, pl, sec);
@@ -3482,6 +3590,7 @@ int32_t pipeline_modpow_public_key_advice(h2r_pipeline *p, const PowCall &call, 
 int32_t h2r_pipeline_modpow_public_key_advice(h2r_pipeline *p, const void *x, const void *n, const uint8_t *e_le, size_t e_len, uint64_t batch,
                                               uint32_t flags, void *in_field_trace, void *out, uint8_t *status, void *workspace,
                                               void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!p || !x || !n || !e_le || !in_field_trace || !status || !workspace || !advice_out) return H2R_E_NULL;
     const Exponent e = Exponent::fixed(e_le, e_len);
     h2r_pow_layout pl;
@@ -3575,6 +3684,7 @@ int32_t h2r_pipeline_verify_pkcs1v15_advice(h2r_pipeline *p, const void *sig, co
                                             const uint64_t *hashed, uint64_t batch, uint32_t flags, void *witness, void *powed_out,
                                             uint8_t *is_valid_out, uint8_t *status, void *workspace, void *advice_out, uint64_t out_stride,
                                             h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!e_le) return H2R_E_NULL;
     return pipeline_verify_advice(p, sig, n, Exponent::fixed(e_le, e_len), hashed, batch, flags, witness, powed_out, is_valid_out, status, workspace,
                                   advice_out, out_stride, static_cast<hipStream_t>(stream));
@@ -3585,6 +3695,7 @@ int32_t h2r_pipeline_verify_pkcs1v15_var_advice(h2r_pipeline *p, const void *sig
                                                 uint32_t exp_limb_bits, const uint64_t *hashed, uint64_t batch, uint32_t flags, void *witness,
                                                 void *powed_out, uint8_t *is_valid_out, uint8_t *status, void *workspace, void *advice_out,
                                                 uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!e_limbs) return H2R_E_NULL;
     return pipeline_verify_advice(p, sig, n, Exponent::per_element(e_limbs, e_num_limbs, exp_limb_bits), hashed, batch, flags, witness, powed_out,
                                   is_valid_out, status, workspace, advice_out, out_stride, static_cast<hipStream_t>(stream));
@@ -3612,6 +3723,7 @@ int32_t h2r_pow_layout_compact(const h2r_ctx *ctx, const h2r_pow_layout *full, h
 int32_t h2r_pipeline_modpow_public_key_var_advice(h2r_pipeline *p, const void *x, const void *e_limbs, uint32_t e_num_limbs, uint32_t exp_limb_bits,
                                                   const void *n, uint64_t batch, uint32_t flags, void *in_field_trace, void *witness, void *out,
                                                   uint8_t *status, void *workspace, void *advice_out, uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!p || !x || !e_limbs || !n || !in_field_trace || !witness || !status || !workspace || !advice_out) return H2R_E_NULL;
     if (reinterpret_cast<u64>(witness) & 15) return H2R_E_SHAPE;
     const h2r_ctx *ctx = p->ctx;
@@ -3712,6 +3824,7 @@ int32_t h2r_advice_check(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const
                          const void *image, uint64_t out_stride, uint64_t batch, const uint8_t *status, const h2r_copy *copies_dev, uint64_t n_copies,
                          const void *src_a, const void *src_b, const void *src_n, uint32_t flags, uint32_t *bad_out, uint64_t *first_bad_out,
                          h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, src_n, /*keyed_export=*/false)) return g;
     if (!ctx || !kinds_dev || !image || !bad_out || !first_bad_out || (n_copies && !copies_dev)) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     if (flags & ~H2R_F_SHARED_MODULUS) return H2R_E_UNSUPPORTED;
@@ -3833,6 +3946,7 @@ int32_t launch_check(const h2r_ctx *ctx, CheckArgs &ca, const uint8_t *status, u
 
 int32_t h2r_mul_mod_trace_check(const h2r_ctx *ctx, const void *a, const void *b, const void *n, uint32_t flags, const void *trace,
                                 uint64_t batch, const uint8_t *status, uint32_t *bad_out, uint32_t *first_bad_out, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !a || !b || !n || !trace || !bad_out) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
@@ -3847,6 +3961,7 @@ int32_t h2r_mul_mod_trace_check(const h2r_ctx *ctx, const void *a, const void *b
 int32_t h2r_pow_trace_check(const h2r_ctx *ctx, const h2r_pow_layout *pl, const void *x, const void *n, const uint8_t *e_le,
                             size_t e_len, uint32_t flags, const void *trace, uint64_t elem_stride, const void *workspace,
                             uint64_t batch, const uint8_t *status, uint32_t *bad_out, uint32_t *first_bad_out, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
     if (!ctx || !pl || !x || !n || !trace || !workspace || !bad_out) return H2R_E_NULL;
     if (pl->off_records == UINT64_MAX) return H2R_E_SHAPE;   // a witness-only layout (h2r_pow_layout_compact) holds no records to audit
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;

@@ -3,8 +3,9 @@
 // The library is compiled as several translation units so that a forced build stays under a minute (the device
 // compile of the template kernel families is what a build costs; each family is instantiated in exactly one unit):
 //   h2r_tu_trace.hip   trace_kernel<LW, L>         (one record per mul_mod; every supported shape)
-//   h2r_tu_chain.hip   recip / chain / chain_dual / chain_wave kernels (the dependent mul_mod chain per element)
+//   h2r_tu_chain.hip   recip / key_table / chain / chain_dual / chain_wave kernels (the dependent mul_mod chain per element)
 //   h2r_tu_step.hip    step_kernel<K, NW, LW, L>   (records of call k + chains of call k+1 in one launch)
+//   h2r_tu_chain_keyed.hip, h2r_tu_step_keyed.hip   the same two families' builds for keyed calls (H2R_F_KEYED_MODULI)
 //   h2r_tu_cells.hip   cells_kernel<LW, ABL, MONT, NWV> (the advice image directly from the operands)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
@@ -88,9 +89,16 @@ inline const StepShape *step_shape_of(u32 w, u32 L, u32 K) {
 hipError_t launch_trace_shape(u32 w, u32 L, u32 lds_per_cu, const TraceArgs &ta, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 // h2r_tu_chain.hip.  co_running: the call's record kernel of the PREVIOUS batch runs next to this chain kernel (pipeline mode)
 hipError_t launch_chain_shape(u32 num_cus, const ChainArgs &ca, bool co_running, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_chain_shape_keyed(u32 num_cus, const ChainArgs &ca, bool co_running, hipStream_t st, hipEvent_t ea, hipEvent_t eb);   // h2r_tu_chain_keyed.hip
+// The key table of keyed moduli: K of the chain build for `kreal` digits (what the entries are computed for), and the kernel that fills
+// the table's two planes (raw digits, raw_stride per entry; chain_pre_words(K) words of Barrett constants per entry) plus the sentinel entry.
+u32 chain_digits(u32 kreal);
+hipError_t launch_key_table_shape(const u32 *n_keys, u32 kreal, u64 num_keys, u32 *raw, u32 raw_stride, u32 *pre, u8 *key_status, hipStream_t st);
 // h2r_tu_step.hip.  One step: the records described by `ta` (an earlier sub-batch) and the chains described by `ca`, one launch on `st`.
 hipError_t launch_step_shape(const StepShape &s, u32 num_cus, const ChainArgs &ca, const TraceArgs &ta, const AuxArgs *aa, const AuxArgs *va,
                              const Sha256Args *sha, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_step_shape_keyed(const StepShape &s, u32 num_cus, const ChainArgs &ca, const TraceArgs &ta, const AuxArgs *aa, const AuxArgs *va,
+                                   const Sha256Args *sha, hipStream_t st, hipEvent_t ea, hipEvent_t eb);   // h2r_tu_step_keyed.hip
 u32 step_shared_bytes_shape(const StepShape &s);
 // h2r_tu_cells.hip.  `lds` = the dynamic LDS request (residency rule applied by the caller); nwv = waves per workgroup (Montgomery, long shapes).
 hipError_t launch_cells_shape(u32 w, bool mont, u32 nwv, u32 lds, const CellsArgs &ca, hipStream_t st, hipEvent_t ea, hipEvent_t eb);

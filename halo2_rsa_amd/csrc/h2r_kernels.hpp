@@ -90,6 +90,12 @@ struct ChainArgs {
     // [bit_lo, bit_hi) of every element, its first mul_mod is item t_base of the element, and the running (squared, acc) pair
     // crosses launches in state[elem][2][kreal].  The record kernel of a segment then runs next to the chains of the next one.
     u32 *state; u32 bit_lo, bit_hi, t_base;
+    u32 num_keys;        // (keyed moduli, below)
+    // KEYED moduli (nullable `key_idx`, H2R_F_KEYED_MODULI): element e uses key key_idx[e] of a table built once by key_table_kernel --
+    // key_raw[slot][key_raw_stride] the keys' raw digits, key_pre[slot][chain_pre_words(K)] their Barrett constants in recip_kernel's
+    // format.  slot = min(key_idx[e], num_keys): entry num_keys is the table's sentinel (a zero modulus, status H2R_E_SHAPE), so an
+    // index out of range reads inside the table.  `n`, `n_stride` and `pre` are unused then.
+    const u32 *key_idx, *key_raw, *key_pre; u32 key_raw_stride;
     ExpBits e;
 };
 
@@ -692,7 +698,10 @@ namespace h2r {
 // SEG = false (the step launches' chain role, whose register budget is tight): the code for segments of a long exponent is compiled out.
 // WAVE (K <= 32, NW = 1): the element belongs to ONE wavefront of a workgroup of independent waves -- `s` is that wave's own LDS, the
 // mul_mods run register-resident (h2r_chain_wave.hpp) and nothing below synchronises beyond the wave (a wave may leave early).
-template <int K, int NW, bool DEEP, bool SEG = true, bool WAVE = false>
+// KEYED: the build of a keyed call (ChainArgs::key_idx) -- the modulus and its constants come from the key's table entry and neither
+// chain_modulus_setup nor wave_modulus_setup is compiled in.  A build of its own, so that the calls without keys keep the code, the
+// registers and the scratch they had (the 64-digit throughput build is sized to 80 VGPRs; the step launches sit at their limit).
+template <int K, int NW, bool DEEP, bool SEG = true, bool WAVE = false, bool KEYED = false>
 __device__ __forceinline__ void chain_element(const ChainArgs &args, ChainLds<K, NW> &s, const u64 elem) {
     using G = Geo<K, NW>;
     constexpr int V = G::V;
@@ -701,8 +710,16 @@ __device__ __forceinline__ void chain_element(const ChainArgs &args, ChainLds<K,
     const int tid = WAVE ? lane : (int)threadIdx.x;   // this element's thread index among its NT threads
     constexpr int NT = WAVE ? 64 : 64 * NW;
     const bool w0 = wave == 0;
-    const u32 *n_g = args.n + elem * args.n_stride;
     const u32 KR = args.kreal;   // digits in memory; digits [KR, K) are zero
+    const u32 *n_g, *pre = args.pre;
+    bool key_oob = false;
+    if constexpr (KEYED) {   // the modulus and its constants come from the key's table entry (wave-uniform: scalar registers)
+        const u32 k = (u32)__builtin_amdgcn_readfirstlane((int)args.key_idx[elem]);
+        key_oob = k >= args.num_keys;
+        const u64 slot = key_oob ? args.num_keys : k;
+        n_g = args.key_raw + slot * args.key_raw_stride;
+        pre = args.key_pre + slot * chain_pre_words(K);
+    } else n_g = args.n + elem * args.n_stride;
     u32 nraw[V];
 #pragma unroll
     for (int m = 0; m < V; ++m) nraw[m] = ((u32)(lane + 64 * m) < KR) ? n_g[lane + 64 * m] : 0;
@@ -715,6 +732,7 @@ __device__ __forceinline__ void chain_element(const ChainArgs &args, ChainLds<K,
 #pragma unroll
         for (int m = 0; m < V; ++m) nz = nz || __ballot(nraw[m] != 0) != 0;
         if (!nz) status = H2R_E_ZERO_MODULUS;
+        if (KEYED && key_oob) status = H2R_E_SHAPE;   // a key index outside the table
     }
     // operands of the first step (all waves load x so that the in-field predicate is block-uniform)
     u32 cur[V], acc[V], bop[V];
@@ -758,17 +776,17 @@ __device__ __forceinline__ void chain_element(const ChainArgs &args, ChainLds<K,
     u32 shift;
     u32 nn[V];
     u32 mu_w = 0;     // WAVE: mu' in registers (lanes 0..K-1)
-    if (args.pre) {   // shared modulus: constants computed once by recip_kernel
-        shift = args.pre[0];
+    if (KEYED || pre) {   // shared modulus: constants computed once by recip_kernel; keyed moduli: once per key by key_table_kernel
+        shift = pre[0];
 #pragma unroll
-        for (int m = 0; m < V; ++m) nn[m] = (lane + 64 * m < K) ? args.pre[CHAIN_PRE_HDR + lane + 64 * m] : 0;
-        if constexpr (WAVE) mu_w = lane < K ? args.pre[CHAIN_PRE_HDR + K + lane] : 0u;
+        for (int m = 0; m < V; ++m) nn[m] = (lane + 64 * m < K) ? pre[CHAIN_PRE_HDR + lane + 64 * m] : 0;
+        if constexpr (WAVE) mu_w = lane < K ? pre[CHAIN_PRE_HDR + K + lane] : 0u;
         else {
             __syncthreads();   // the zero fill above is complete
-            for (int i = tid; i < K; i += NT) { s.nnpad[K + i] = args.pre[CHAIN_PRE_HDR + i]; s.mupad[K + i] = args.pre[CHAIN_PRE_HDR + K + i]; }
+            for (int i = tid; i < K; i += NT) { s.nnpad[K + i] = pre[CHAIN_PRE_HDR + i]; s.mupad[K + i] = pre[CHAIN_PRE_HDR + K + i]; }
             __syncthreads();
         }
-    } else {
+    } else if constexpr (!KEYED) {
         if constexpr (WAVE) {
             const int rs = wave_modulus_setup<K>(s, nraw[0], lane, shift, nn[0], mu_w);   // (n != 0 was established above: only the developer check can fail)
             if (rs != H2R_OK) { if (tid == 0) args.status[elem] = (u8)rs; return; }
@@ -880,26 +898,26 @@ __device__ __forceinline__ void chain_element(const ChainArgs &args, ChainLds<K,
 #endif
 // SEG: the build that can walk a segment of a long exponent (ChainArgs::state); the calls without one keep the build whose registers are
 // what they were (the 64-digit throughput build: 80 VGPRs, no scratch).
-template <int K, int NW, bool DEEP, bool SEG = false>
+template <int K, int NW, bool DEEP, bool SEG = false, bool KEYED = false>
 __global__ __launch_bounds__(64 * NW, DEEP ? 2 : (K <= 64 ? H2R_CHAIN_MINB : H2R_CHAIN_MINB_BIG)) void chain_kernel(ChainArgs args) {
     __shared__ ChainLds<K, NW> s;
     if (args.prio) __builtin_amdgcn_s_setprio(3);
     for (u64 elem = blockIdx.x; elem < args.batch; elem += gridDim.x) {
         if (elem != blockIdx.x) __syncthreads();   // every wave is done with the previous element's LDS
-        chain_element<K, NW, DEEP, SEG>(args, s, elem);
+        chain_element<K, NW, DEEP, SEG, false, KEYED>(args, s, elem);
     }
 }
 
 // The one-wave form (K <= 32, h2r_chain_wave.hpp): a workgroup is CHAIN_WAVE_WPB independent waves, one element each; no workgroup barrier
 // anywhere.  Workgroup b walks the elements (b * WPB + wave) + k * gridDim.x * WPB.
 constexpr int CHAIN_WAVE_WPB = 4;
-template <int K, bool SEG = false>
+template <int K, bool SEG = false, bool KEYED = false>
 __global__ __launch_bounds__(64 * CHAIN_WAVE_WPB) void chain_wave_kernel(ChainArgs args) {
     __shared__ ChainLds<K, 1> s[CHAIN_WAVE_WPB];
     const int wv = threadIdx.x >> 6;
     if (args.prio) __builtin_amdgcn_s_setprio(3);
     for (u64 elem = (u64)blockIdx.x * CHAIN_WAVE_WPB + wv; elem < args.batch; elem += (u64)gridDim.x * CHAIN_WAVE_WPB)
-        chain_element<K, 1, false, SEG, true>(args, s[wv], elem);
+        chain_element<K, 1, false, SEG, true, KEYED>(args, s[wv], elem);
 }
 
 // ---- two chains per element, side by side (round 3) -----------------------------------------------------------------
@@ -1080,6 +1098,50 @@ __global__ __launch_bounds__(64 * NW) void recip_kernel(const u32 *n, u32 kreal,
     if (status == H2R_OK)
         for (int i = threadIdx.x; i < K; i += 64 * NW) { pre[CHAIN_PRE_HDR + i] = s.nnpad[K + i]; pre[CHAIN_PRE_HDR + K + i] = s.mupad[K + i]; }
 }
+
+// The key table of keyed moduli (h2r_key_table_build): for every key its raw digits (plane `raw`, raw_stride digits per entry: what
+// the kernels next to the chain read) and its Barrett constants in recip_kernel's format (plane `pre_plane`, chain_pre_words(K)
+// words per entry: what chain_element reads instead of running the modulus set-up).  One key per workgroup, the grid walks the keys.
+// Entry num_keys is the sentinel every reader clamps an out-of-range index to: a zero modulus whose status is H2R_E_SHAPE.
+template <int K, int NW>
+__global__ __launch_bounds__(64 * NW) void key_table_kernel(const u32 *n_keys, u32 kreal, u64 num_keys, u32 *raw, u32 raw_stride, u32 *pre_plane,
+                                                            u8 *key_status) {
+    constexpr int V = Geo<K, NW>::V;
+    __shared__ ChainLds<K, NW> s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (u64 key = blockIdx.x; key <= num_keys; key += gridDim.x) {
+        if (key != blockIdx.x) __syncthreads();   // every thread is done with the previous key's LDS
+        const bool sentinel = key == num_keys;
+        const u32 *n = n_keys + key * kreal;      // (never read for the sentinel)
+        u32 nraw[V], nn[V];
+#pragma unroll
+        for (int m = 0; m < V; ++m) nraw[m] = (!sentinel && (u32)(lane + 64 * m) < kreal) ? n[lane + 64 * m] : 0;
+        for (int i = threadIdx.x; i < 3 * K; i += 64 * NW) { s.bpad[i] = 0; s.nnpad[i] = 0; s.mupad[i] = 0; }
+        if (threadIdx.x == 0) { s.dbg = nullptr; s.dbg_n = 0; }
+        __syncthreads();
+        u32 shift;
+        int status = chain_modulus_setup<K, NW>(s, nraw, lane, wave, shift, nn);   // (a zero key returns at once: block-uniform)
+        if (sentinel) status = H2R_E_SHAPE;
+        u32 *pre = pre_plane + key * chain_pre_words(K);
+        for (u32 i = threadIdx.x; i < raw_stride; i += 64 * NW) raw[key * raw_stride + i] = (!sentinel && i < kreal) ? n[i] : 0;
+        if (threadIdx.x == 0) {
+            pre[0] = shift; pre[1] = (u32)status; pre[2] = 0; pre[3] = 0;
+            if (key_status && !sentinel) key_status[key] = (u8)status;
+        }
+        // (a zero key and the sentinel: the zero fill above is what lands here)
+        for (int i = threadIdx.x; i < K; i += 64 * NW) { pre[CHAIN_PRE_HDR + i] = s.nnpad[K + i]; pre[CHAIN_PRE_HDR + K + i] = s.mupad[K + i]; }
+    }
+}
+// h2r_key_table_expand: n_out[e] = the raw digits of key key_idx[e] (the sentinel's zeros for an index out of range); one thread per digit
+#ifdef H2R_TU_API   // a plain (non-template) kernel: defined in the one translation unit that launches it
+__global__ void key_expand_kernel(const u32 *raw, u32 raw_stride, u32 num_keys, const u32 *key_idx, u64 batch, u32 kreal, u32 *n_out) {
+    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= batch * kreal) return;
+    const u64 e = i / kreal;
+    const u32 d = (u32)(i % kreal), k = key_idx[e];
+    n_out[i] = raw[(u64)(k < num_keys ? k : num_keys) * raw_stride + d];
+}
+#endif
 
 // ================================================================================================
 // K1: trace kernel
@@ -1610,9 +1672,11 @@ struct AuxArgs {
     const u64 *hashed;                 // [elem][4] 64-bit limbs of the SHA-256 digest (nullable: no EM check)
     const void *powed;                 // [elem][L] result of the pow path
     u64 batch; u32 L;
+    u32 num_keys;                      // keyed moduli (key_idx, below)
     u8 *trace; u64 elem_stride, off_in_field, off_em;
     u8 *is_valid;                      // [elem] (nullable)
     const u8 *status;                  // [elem]: EM check skipped (is_valid = 0) when nonzero
+    const u32 *key_idx;                // keyed moduli (nullable): `n` is the key table's raw plane, element e reads row min(key_idx[e], num_keys)
 };
 
 constexpr int AUX_V = 3;  // positions per lane: L + 2 <= 192
@@ -1766,18 +1830,20 @@ __device__ __forceinline__ bool aux_less_than(u8 *&sec, const AuxGeom &g, const 
 
 // OWN: powed[elem] and status[elem] were stored by THIS wave a moment ago (the step launch's chain role): they are read back with
 // agent-scope loads, i.e. from the L2 the stores went to, not from a possibly older L1 line.
-template <int LW, bool OWN = false>
+template <int LW, bool OWN = false, bool KEYED = false>
 __device__ __forceinline__ void aux_wave(const AuxArgs &a, const u64 elem, const int lane, uint4 *aux_stage) {
     using X = AuxW<LW>;
     using limb_t = typename LimbT<LW>::type;
     const u32 L = a.L;
     const AuxGeom g(L, LW);
     u64 Xv[AUX_V], Nv[AUX_V];
+    u64 nrow = elem;
+    if constexpr (KEYED) { const u32 k = a.key_idx[elem]; nrow = k < a.num_keys ? k : a.num_keys; }
 #pragma unroll
     for (int m = 0; m < AUX_V; ++m) {
         const u32 p = lane + 64 * m;
         Xv[m] = p < L ? (u64) reinterpret_cast<const limb_t *>(a.x)[elem * L + p] : 0;
-        Nv[m] = p < L ? (u64) reinterpret_cast<const limb_t *>(a.n)[elem * a.n_stride + p] : 0;
+        Nv[m] = p < L ? (u64) reinterpret_cast<const limb_t *>(a.n)[nrow * a.n_stride + p] : 0;
     }
     u8 *et = a.trace + elem * a.elem_stride;
     // Both regions are assembled in LDS and leave as 16-byte streaming stores: written in place, their 4/8-byte stores
@@ -1838,10 +1904,10 @@ __device__ __forceinline__ void aux_wave(const AuxArgs &a, const u64 elem, const
         for (u32 k = lane; k < em_u4; k += 64) { const uint4 v = aux_stage[if_u4 + k]; st16(et + a.off_em + 16ull * k, ((u64)v.y << 32) | v.x, ((u64)v.w << 32) | v.z); }
 }
 // one wave per element; dynamic LDS: AuxGeom::in_field_sz() + em_sz() bytes
-template <int LW>
+template <int LW, bool KEYED = false>
 __global__ __launch_bounds__(64) void aux_kernel(AuxArgs a) {
     extern __shared__ uint4 aux_stage_dyn[];
-    aux_wave<LW>(a, blockIdx.x, threadIdx.x, aux_stage_dyn);
+    aux_wave<LW, false, KEYED>(a, blockIdx.x, threadIdx.x, aux_stage_dyn);
 }
 
 // ONE launch per pipeline step, three roles: workgroups [0, n_chain) run the chains of call k+1 (each walks elements b,
@@ -1878,7 +1944,8 @@ union StepShared {
 // launches of modpow_public_key calls keep the build without it, whose registers and scratch are what they were.
 // WAVE (K <= 32): the chain role's workgroup is NW independent one-wave chains (chain_element<.., WAVE>) -- workgroup b of the role walks the
 // elements (b * NW + wave) + k * n_chain * NW; the record role is unchanged.  The verifier's folded witness (va) is not built in this form.
-template <int K, int NW, int LW, int L, bool FOLD, bool WAVE = false>
+// KEYED: the launch of a keyed call (chain_element<.., KEYED>; the witness roles read the key table's raw plane through the clamped index).
+template <int K, int NW, int LW, int L, bool FOLD, bool WAVE = false, bool KEYED = false>
 __global__ __launch_bounds__(64 * NW, H2R_CHAIN_MINB) void step_kernel(ChainArgs ca, TraceArgs ta, AuxArgs aa, AuxArgs va, Sha256Args sa, u32 n_sha, u32 n_chain, u32 n_rec) {
     static_assert((64 * NW) % TraceGeo<L>::TPI == 0, "the record role's items tile the chain role's workgroup");
     __shared__ StepShared<K, NW, LW, L, WAVE> sh;
@@ -1894,14 +1961,14 @@ __global__ __launch_bounds__(64 * NW, H2R_CHAIN_MINB) void step_kernel(ChainArgs
         if (b < n_chain) {
             const int wv = threadIdx.x >> 6;
             for (u64 elem = (u64)b * NW + wv; elem < ca.batch; elem += (u64)n_chain * NW)
-                chain_element<(WAVE ? K : 2), 1, false, false, true>(ca, sh.chainw[wv], elem);
+                chain_element<(WAVE ? K : 2), 1, false, false, true, KEYED>(ca, sh.chainw[wv], elem);
             return;
         }
     }
     if (b < n_chain) {
         for (u64 elem = b; elem < ca.batch; elem += n_chain) {
             if (elem != b) __syncthreads();   // every wave is done with the previous element's LDS
-            chain_element<K, NW, false, false>(ca, sh.chain, elem);
+            chain_element<K, NW, false, false, false, KEYED>(ca, sh.chain, elem);
             if (FOLD && va.batch) {
                 // the verifier's assert_in_field + encoded-message witness of THIS element (src/chip.rs:106, 136-198), by the wave that
                 // has just stored its result and status: no kernel of its own behind the launch.  Wave 0 reads its own stores back
@@ -1922,7 +1989,7 @@ __global__ __launch_bounds__(64 * NW, H2R_CHAIN_MINB) void step_kernel(ChainArgs
                         // agent-scope loads (aux_wave<.., OWN>)
                         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
                     }
-                    if (ready) aux_wave<LW, true>(va, elem, (int)threadIdx.x, reinterpret_cast<uint4 *>(&sh));
+                    if (ready) aux_wave<LW, true, KEYED>(va, elem, (int)threadIdx.x, reinterpret_cast<uint4 *>(&sh));
                     else if (threadIdx.x == 0) { ca.status[elem] = (u8)H2R_E_HIP; if (va.is_valid) va.is_valid[elem] = 0; }
                 }
             }
@@ -1934,7 +2001,7 @@ __global__ __launch_bounds__(64 * NW, H2R_CHAIN_MINB) void step_kernel(ChainArgs
     } else if (b - n_chain - n_rec < aa.batch) {
         // last in dispatch order: these short workgroups fill the slots the record role's tail leaves (in front of the record
         // role they cost the step 3-5 us)
-        if (threadIdx.x < 64) aux_wave<LW>(aa, b - n_chain - n_rec, (int)threadIdx.x, sh.aux);
+        if (threadIdx.x < 64) aux_wave<LW, false, KEYED>(aa, b - n_chain - n_rec, (int)threadIdx.x, sh.aux);
     }
 }
 

@@ -10,7 +10,7 @@ import numpy as np
 import torch
 
 from ._lib import H2R_ADVICE_DIRECT, H2R_HASHED_MSG_STREAM_BYTES, H2RVerifyLayout, check, lib
-from .big_integer import AssignedInteger, BatchResult, BigIntChip, UnassignedInteger, _e_bytes
+from .big_integer import AssignedInteger, BatchResult, BigIntChip, KeyedModuli, UnassignedInteger, _e_bytes, _plain_moduli
 
 
 @dataclass
@@ -27,7 +27,9 @@ class Var:
 
 @dataclass
 class RSAPublicKey:
-    n: Union[UnassignedInteger, AssignedInteger]
+    """n: one modulus per element (or one for the whole batch) -- or, for many signatures under a few keys, a KEYED key set:
+    `chip.key_table(moduli).select(key_idx)` (big_integer.KeyTable), accepted by modpow_public_key, both verifiers and the Pipeline."""
+    n: Union[UnassignedInteger, AssignedInteger, KeyedModuli]
     e: Union[Fix, Var]
 
 
@@ -64,7 +66,7 @@ class RSAChip:
             if isinstance(ev, UnassignedInteger):
                 import numpy as np
                 import torch
-                t = torch.from_numpy(np.ascontiguousarray(ev.limbs).view(np.int64)).to(n.limbs_dev.device)
+                t = torch.from_numpy(np.ascontiguousarray(ev.limbs).view(np.int64)).to("cuda:%d" % self._bigint.device)
                 ev = AssignedInteger(t.contiguous(), self.LIMB_WIDTH)
             e = Var(ev)
         return RSAPublicKey(n, e)
@@ -284,6 +286,7 @@ class VerifyResult:
         region of src/lib.rs:220-241 -- the hashed-message limb composition rows (h2r_hashed_msg_emit_advice) in front.
         direct=True (H2R_ADVICE_DIRECT): the pow rows are written from the operands, the records are not read."""
         sig, n, hashed = self.inputs
+        n = _plain_moduli(n)   # (the emitters take per-element moduli: a keyed result expands for itself)
         batch = sig.batch
         total, _ = self.advice_sections()
         pre = int(lib().h2r_hashed_msg_advice_rows(self.chip._ctx)) if with_hashed_msg else 0

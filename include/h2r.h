@@ -46,7 +46,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define H2R_VERSION 4
+#define H2R_VERSION 5
 
 /* ---- status codes (function return values and per-element status bytes) ---------------------- */
 enum {
@@ -75,6 +75,9 @@ enum {
 
 /* flags for the batch calls */
 #define H2R_F_SHARED_MODULUS 1u /* `n` holds ONE modulus used by every element */
+#define H2R_F_KEYED_MODULI 2u   /* `n` points to a HOST h2r_keyed_moduli: every element names a key of a key table (below).
+                                 * Only the exports listed there take it; every other export that has `n` and `flags` answers
+                                 * H2R_E_UNSUPPORTED before it looks at `n`.  Together with H2R_F_SHARED_MODULUS: H2R_E_UNSUPPORTED. */
 
 typedef struct h2r_ctx h2r_ctx;
 typedef void *h2r_stream_t; /* hipStream_t */
@@ -233,6 +236,51 @@ int32_t h2r_pow_var_layout(const h2r_ctx *ctx, uint32_t e_num_limbs, uint32_t ex
 
 /* Scratch needed by one batch call that runs `num_mul_mods` mul_mods per element. */
 uint64_t h2r_workspace_bytes(const h2r_ctx *ctx, uint64_t batch, uint32_t num_mul_mods);
+
+/* ---- keyed moduli: many elements, few keys ----------------------------------------------------- */
+/* A caller that verifies many signatures under a few public keys builds a KEY TABLE once -- per key the modulus and the
+ * constants of its Barrett reduction (normalisation shift, n' = n << shift, the reciprocal mu'), which a call with
+ * per-element moduli recomputes for every element -- and then hands every call a per-element index into it.
+ *
+ * h2r_key_table_bytes: bytes of a table of num_keys keys for this ctx's shape (a host-only query: works on a device-less
+ *   ctx; 0 for a NULL ctx or a num_keys the library cannot index, 2^32 - 1 and above).  A multiple of 256.
+ * h2r_key_table_build: n_keys = [num_keys][num_limbs] limbs on the device; `table` = caller-owned device memory, 256-byte
+ *   aligned, at least h2r_key_table_bytes() (H2R_E_SHAPE for a misaligned one); key_status (nullable, device, [num_keys]):
+ *   H2R_OK or H2R_E_ZERO_MODULUS per key.  Enqueues on `stream`, never synchronises.  The table is opaque and
+ *   position-independent (it may be copied device to device with a plain memcpy), and valid for any ctx of the same
+ *   (limb_width, bits_len) and the same h2r_build_id().
+ * h2r_key_table_expand: n_out[e] = the modulus of key key_idx[e] ([batch][num_limbs] limbs; zero for an index that is out of
+ *   range) -- per-element moduli for the exports that are not keyed (the audits, the emitters), which take them with flags 0. */
+uint64_t h2r_key_table_bytes(const h2r_ctx *ctx, uint64_t num_keys);
+int32_t h2r_key_table_build(const h2r_ctx *ctx, const void *n_keys, uint64_t num_keys, void *table,
+                            uint8_t *key_status, h2r_stream_t stream);
+int32_t h2r_key_table_expand(const h2r_ctx *ctx, const void *table, uint64_t num_keys, const uint32_t *key_idx,
+                             uint64_t batch, void *n_out, h2r_stream_t stream);
+
+/* What `n` points to when flags has H2R_F_KEYED_MODULI.  A HOST struct, read inside the call and not retained (like
+ * e_le_bytes).  Element e uses the modulus of key key_idx[e], with exactly the results, statuses and trace bytes of the same
+ * call given that modulus per element:
+ *   - an element of a zero key gets H2R_E_ZERO_MODULUS;
+ *   - an element whose key_idx is >= num_keys gets H2R_E_SHAPE -- no kernel reads outside the table for it (the table ends
+ *     with a sentinel entry every reader clamps such an index to) and its neighbours are unaffected.
+ * Keyed exports: h2r_mul_mod_batch, h2r_square_mod_batch, h2r_pow_mod_fixed_exp_batch, h2r_pow_mod_batch,
+ * h2r_modpow_public_key_batch, h2r_modpow_public_key_var_batch, h2r_verify_pkcs1v15_batch, h2r_verify_pkcs1v15_var_batch,
+ * h2r_signature_verifier_batch, and the pipelined record forms h2r_pipeline_modpow_public_key[_var],
+ * h2r_pipeline_verify_pkcs1v15[_var], h2r_pipeline_signature_verifier.  h2r_workspace_bytes is the same with and without keys.
+ * Nothing is launched in front of the chain kernel of a keyed call: the chain kernel takes the element's modulus and constants
+ * from the key's entry, whichever of its builds serves the call -- except the two-chains-per-element build for latency-bound
+ * batches of dense exponents, which does not read the table: a keyed call is routed past it to the four-wave builds (same
+ * values, same items, same statuses).
+ * Lifetime: key_idx is read in `stream` order inside the call that is given it, in the pipelined forms too -- a producer may
+ * refill it (in stream order) as soon as that call has returned; the record kernels read the call's own copy of the moduli in
+ * its workspace.  The TABLE must stay unchanged while calls that name it are queued or in flight. */
+typedef struct h2r_keyed_moduli {
+    uint32_t struct_size;    /* sizeof(h2r_keyed_moduli); anything else: H2R_E_UNSUPPORTED */
+    uint32_t reserved;
+    uint64_t num_keys;
+    const void *table;       /* device: h2r_key_table_build's output */
+    const uint32_t *key_idx; /* device: [batch] */
+} h2r_keyed_moduli;
 
 /* ---- the hot path ------------------------------------------------------------------------------ */
 

@@ -65,15 +65,35 @@ struct UnassignedInteger {
 };
 
 // reference src/big_integer/mod.rs:306-382 (range type Fresh): a batch of limb vectors in HBM
+// ... or, as the MODULI of a call, KEYED (KeyTable::select, H2R_F_KEYED_MODULI): one key index per element into a key table instead of
+// limbs -- accepted as `n` by mul_mod / square_mod, the pow and modpow_public_key forms, both verifiers and the Pipeline's record forms;
+// the exports that are not keyed (the emitters, the records-free pipelines, the Fresh ops) take KeyTable::expand's per-element moduli.
 class AssignedInteger {
   public:
     AssignedInteger(DeviceBuffer d, size_t batch, size_t num_limbs) : dev_(std::move(d)), batch_(batch), num_limbs_(num_limbs) {}
+    // keyed moduli: `key_idx` = [batch] uint32 on the device; `table` / num_keys: a KeyTable that outlives the calls
+    static AssignedInteger keyed(DeviceBuffer key_idx, size_t batch, size_t num_limbs, const void *table, uint64_t num_keys) {
+        AssignedInteger a(std::move(key_idx), batch, num_limbs);
+        a.keyed_ = true; a.table_ = table; a.num_keys_ = num_keys;
+        return a;
+    }
     size_t num_limbs() const { return num_limbs_; }
     size_t batch() const { return batch_; }
-    const void *data() const { return dev_.get(); }
-    std::vector<uint64_t> limbs() const { std::vector<uint64_t> h(batch_ * num_limbs_); dev_.download(h.data(), h.size() * 8); return h; }
+    bool is_keyed() const { return keyed_; }
+    // what an export takes as `n`: the limbs on the device -- keyed: the HOST h2r_keyed_moduli (read inside the call, not retained)
+    const void *data() const {
+        if (!keyed_) return dev_.get();
+        km_ = h2r_keyed_moduli{(uint32_t)sizeof(h2r_keyed_moduli), 0, num_keys_, table_, static_cast<const uint32_t *>(dev_.get())};
+        return &km_;
+    }
+    const uint32_t *key_idx() const { return keyed_ ? static_cast<const uint32_t *>(dev_.get()) : nullptr; }
+    std::vector<uint64_t> limbs() const {
+        if (keyed_) throw std::invalid_argument("AssignedInteger::limbs: keyed moduli hold indices (KeyTable::expand gives the limbs)");
+        std::vector<uint64_t> h(batch_ * num_limbs_); dev_.download(h.data(), h.size() * 8); return h;
+    }
   private:
     DeviceBuffer dev_; size_t batch_, num_limbs_;
+    bool keyed_ = false; const void *table_ = nullptr; uint64_t num_keys_ = 0; mutable h2r_keyed_moduli km_{};
 };
 
 class BigIntChip;
@@ -373,8 +393,13 @@ class BigIntChip {
         return v;
     }
 
+    // the flags a call gives the moduli `n` with: keyed (KeyTable::select), one modulus for the whole batch, or one per element
+    static uint32_t flags(const AssignedInteger &n, size_t batch) {
+        if (n.is_keyed()) return H2R_F_KEYED_MODULI;
+        return (n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u;
+    }
+
   private:
-    static uint32_t flags(const AssignedInteger &n, size_t batch) { return (n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u; }
     FreshResult fresh(uint32_t op, const AssignedInteger &a, const AssignedInteger *b, const AssignedInteger *n) const {
         FreshResult r; uint32_t vl = 0;
         check(h2r_fresh_op_layout(ctx_, op, &r.elem_stride, &r.stream_bytes, &vl), "h2r_fresh_op_layout");
@@ -442,6 +467,42 @@ class BigIntChip {
     friend class Trace;
     friend class RSAChip;
     friend class RSASignatureVerifier;
+};
+
+// Many elements, few keys: per key the modulus and the constants of its Barrett reduction, built once on the device
+// (h2r_key_table_build); select() names a key per element.  The table must outlive -- and stay unchanged under -- the calls that name it.
+class KeyTable {
+  public:
+    KeyTable(const BigIntChip &chip, const UnassignedInteger &moduli) : chip_(&chip), num_keys_(moduli.batch) {
+        if (moduli.num_limbs != chip.num_limbs()) throw Error(H2R_E_SHAPE, "KeyTable");
+        const uint64_t bytes = h2r_key_table_bytes(chip.ctx(), num_keys_);
+        if (!bytes) throw Error(H2R_E_UNSUPPORTED, "h2r_key_table_bytes");
+        table_ = DeviceBuffer(bytes);
+        AssignedInteger keys = chip.assign_integer(moduli);
+        DeviceBuffer st(num_keys_ ? num_keys_ : 1);
+        check(h2r_key_table_build(chip.ctx(), keys.data(), num_keys_, table_.get(), static_cast<uint8_t *>(st.get()), nullptr), "h2r_key_table_build");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        status_.resize(num_keys_);
+        if (num_keys_) st.download(status_.data(), num_keys_);
+    }
+    uint64_t num_keys() const { return num_keys_; }
+    const std::vector<uint8_t> &status() const { return status_; }   // H2R_OK or H2R_E_ZERO_MODULUS per key
+    // the moduli of a keyed call: element e uses key key_idx[e] (>= num_keys: that element gets H2R_E_SHAPE)
+    AssignedInteger select(const std::vector<uint32_t> &key_idx) const {
+        DeviceBuffer d(key_idx.size() * 4);
+        if (!key_idx.empty()) d.upload(key_idx.data(), key_idx.size() * 4);
+        return AssignedInteger::keyed(std::move(d), key_idx.size(), chip_->num_limbs(), table_.get(), num_keys_);
+    }
+    // per-element moduli of a keyed `n` (h2r_key_table_expand): for the exports that are not keyed
+    AssignedInteger expand(const AssignedInteger &n) const {
+        if (!n.is_keyed()) throw Error(H2R_E_SHAPE, "KeyTable::expand");
+        DeviceBuffer out(n.batch() * chip_->num_limbs() * 8);
+        check(h2r_key_table_expand(chip_->ctx(), table_.get(), num_keys_, n.key_idx(), n.batch(), out.get(), nullptr), "h2r_key_table_expand");
+        hip_check(hipDeviceSynchronize(), "hipDeviceSynchronize");
+        return AssignedInteger(std::move(out), n.batch(), chip_->num_limbs());
+    }
+  private:
+    const BigIntChip *chip_; uint64_t num_keys_; DeviceBuffer table_; std::vector<uint8_t> status_;
 };
 
 inline std::vector<uint8_t> Trace::flatten(size_t elem) const {
@@ -701,7 +762,7 @@ class Pipeline {
         const size_t batch = sig.c.batch();
         check(h2r_pipeline_verify_pkcs1v15(p_, sig.c.data(), pk.n.data(), f->e_le.data(), f->e_le.size(),
                                            static_cast<const uint64_t *>(hashed_msg.data()), batch,
-                                           (pk.n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u, b.trace.get(), b.powed.get(),
+                                           BigIntChip::flags(pk.n, batch), b.trace.get(), b.powed.get(),
                                            static_cast<uint8_t *>(b.is_valid.get()), static_cast<uint8_t *>(b.status.get()),
                                            b.workspace.get(), stream), "h2r_pipeline_verify_pkcs1v15");
     }
@@ -715,7 +776,7 @@ class Pipeline {
         const size_t batch = sig.c.batch();
         check(h2r_pipeline_signature_verifier(p_, static_cast<const uint8_t *>(msgs.get()), static_cast<const uint64_t *>(msg_off.get()), 0,
                                               sig.c.data(), pk.n.data(), f->e_le.data(), f->e_le.size(), batch,
-                                              (pk.n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u, b.trace.get(), nullptr, 0,
+                                              BigIntChip::flags(pk.n, batch), b.trace.get(), nullptr, 0,
                                               static_cast<uint8_t *>(digest.get()), static_cast<uint64_t *>(hashed.get()), b.powed.get(),
                                               static_cast<uint8_t *>(b.is_valid.get()), static_cast<uint8_t *>(b.status.get()),
                                               b.workspace.get(), stream), "h2r_pipeline_signature_verifier");
@@ -729,7 +790,7 @@ class Pipeline {
         if (!f) throw Error(H2R_E_UNSUPPORTED, "Pipeline::modpow_public_key (takes RSAPubE::Fix)");
         const size_t batch = x.batch();
         check(h2r_pipeline_modpow_public_key(p_, x.data(), pk.n.data(), f->e_le.data(), f->e_le.size(), batch,
-                                             (pk.n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u, b.trace.get(),
+                                             BigIntChip::flags(pk.n, batch), b.trace.get(),
                                              in_field ? in_field->get() : nullptr, b.powed.get(),
                                              static_cast<uint8_t *>(b.status.get()), b.workspace.get(), stream), "h2r_pipeline_modpow_public_key");
     }
@@ -743,7 +804,7 @@ class Pipeline {
         if (!f) throw Error(H2R_E_UNSUPPORTED, "Pipeline::modpow_public_key_advice (takes RSAPubE::Fix)");
         const size_t batch = x.batch();
         check(h2r_pipeline_modpow_public_key_advice(p_, x.data(), pk.n.data(), f->e_le.data(), f->e_le.size(), batch,
-                                                    (pk.n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u, in_field.get(), b.powed.get(),
+                                                    BigIntChip::flags(pk.n, batch), in_field.get(), b.powed.get(),
                                                     static_cast<uint8_t *>(b.status.get()), b.workspace.get(), advice.get(), advice_stride, stream),
               "h2r_pipeline_modpow_public_key_advice");
     }
@@ -761,7 +822,7 @@ class Pipeline {
         if (!v) throw Error(H2R_E_UNSUPPORTED, "Pipeline::modpow_public_key_var_advice (takes RSAPubE::Var)");
         const size_t batch = x.batch();
         check(h2r_pipeline_modpow_public_key_var_advice(p_, x.data(), v->data(), (uint32_t)v->num_limbs(), chip_.exp_limb_bits(), pk.n.data(), batch,
-                                                        (pk.n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u, in_field.get(), witness.get(),
+                                                        BigIntChip::flags(pk.n, batch), in_field.get(), witness.get(),
                                                         b.powed.get(), static_cast<uint8_t *>(b.status.get()), b.workspace.get(), advice.get(),
                                                         advice_stride, stream), "h2r_pipeline_modpow_public_key_var_advice");
     }
@@ -783,7 +844,7 @@ class Pipeline {
         const size_t batch = sig.c.batch();
         check(h2r_pipeline_verify_pkcs1v15_advice(p_, sig.c.data(), pk.n.data(), f->e_le.data(), f->e_le.size(),
                                                   static_cast<const uint64_t *>(hashed_msg.data()), batch,
-                                                  (pk.n.batch() == 1 && batch != 1) ? H2R_F_SHARED_MODULUS : 0u, witness.get(), b.powed.get(),
+                                                  BigIntChip::flags(pk.n, batch), witness.get(), b.powed.get(),
                                                   static_cast<uint8_t *>(b.is_valid.get()), static_cast<uint8_t *>(b.status.get()), b.workspace.get(),
                                                   advice.get(), advice_stride, stream), "h2r_pipeline_verify_pkcs1v15_advice");
     }
