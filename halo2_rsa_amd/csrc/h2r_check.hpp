@@ -63,7 +63,6 @@ __global__ __launch_bounds__(256) void advice_check_rows_kernel(AdviceCheckArgs 
 #pragma unroll
     for (u32 k = 0; k < 5; ++k) canon = canon && !ge_p(c[k].v, a.f.p);
     if (!canon) { achk_fail(a, elem, r, ACHK_RANGE); return; }
-    if ((ck.nz & (1u << 7)) && !has_next) { achk_fail(a, elem, r, ACHK_GATE); return; }   // a row that refers to a next row the image does not have
     // ---- the lookups: on the canonical integers ----
     if (ck.comp_bits | ck.ov_bits) {
         bool ok = true;
@@ -77,6 +76,7 @@ __global__ __launch_bounds__(256) void advice_check_rows_kernel(AdviceCheckArgs 
         if (!ok) achk_fail(a, elem, r, ACHK_LOOKUP);
     }
     // ---- the gate, in the Montgomery domain ----
+    if ((ck.nz & (1u << 7)) && !has_next) { achk_fail(a, elem, r, ACHK_GATE); return; }   // a row that refers to a next row the image does not have
     Fe m[6];
 #pragma unroll
     for (u32 k = 0; k < 6; ++k) m[k] = a.img.mont ? c[k] : fe_to_mont(c[k], a.f);

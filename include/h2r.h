@@ -960,7 +960,18 @@ int32_t h2r_advice_apply_layout(const h2r_ctx *ctx, const h2r_advice_layout *lay
  * operand, num_limbs limbs per element, src_n shared with H2R_F_SHARED_MODULUS in flags) for equality, and that every cell is a
  * canonical representative.  The image is read in the ctx's representation.  kinds_dev: the rows' kinds on the device (h2r_*_row_kinds
  * uploaded once); bad_out[elem] (zeroed by the call) = violated checks, first_bad_out[elem] = (row << 8) | code of one of them
- * (1 gate, 2 lookup, 3 copy, 4 a kind without a fixed row, 5 a cell >= p); elements with a nonzero status byte are skipped.
+ * (1 gate, 2 lookup, 3 copy, 4 a kind without a fixed row, 5 a cell >= p); elements with a nonzero status byte are skipped
+ * (bad_out = first_bad_out = 0).  What counts as ONE violated check (tests/mockprover_ref.py is the plain model the kernels are
+ * compared with, cell by cell).  Per row, in this order:
+ *   - a kind without a fixed row (h2r_advice_fixed_row refuses it under `cfg`): one violation, code 4, and nothing else for the row;
+ *   - otherwise any of the row's five cells >= p: one violation, code 5, and nothing else for the row;
+ *   - otherwise one code 2 if the composition lookup fails on any of the cells a..d or the overflow lookup fails on cell a (at most
+ *     one per row, however many cells fail), and one code 1 if the gate's residual is nonzero; e(next row) is physical column 4 of the
+ *     next row, and a row whose se_next is nonzero while it is the image's last row is a gate violation.
+ * Per copy pair: one code 3, reported with the pair's `row`, if the pair names a row or column outside the image, if its two cells
+ * differ, or -- H2R_COPY_SRC_* -- if the cell is not the operand limb (or that operand pointer is NULL).  So a cell that is the source
+ * of k pairs and sits in one gate counts k + 1 when it is wrong.  cfg = NULL: no row has a lookup (every gate is still checked).
+ * A cell >= p is only reported on its own row: what the row before it (se_next) and the copy pairs make of such a cell is unspecified.
  * h2r_pow_copy_map: the pairs of one fixed-exponent pow element (every record's h2r_advice_copy_map pairs + its operand limbs tied to
  * the cells pow_mod_fixed_exp takes them from: h2r_pow_operand_sources; H2R_COPY_SRC_A = the assigned base x, _N = the modulus), rows
  * counted from row_offset (the pow section's first row in a larger element image); returns the number of pairs (out NULL / cap 0 to ask). */
