@@ -1135,6 +1135,47 @@ class LookupArgument:
         self._keep = (th_dev, ws)   # alive until the stream has run the kernels
         return a_perm, s_perm, status
 
+    def _challenges(self, values: Sequence[int], batch: int, dev) -> torch.Tensor:
+        w = np.array([[(int(t) >> (64 * k)) & (2 ** 64 - 1) for k in range(4)] for t in values], dtype=np.uint64)
+        assert w.shape == (batch, 4)
+        return torch.from_numpy(w.view(np.int64)).to(dev)
+
+    def input_columns(self, kinds, image: torch.Tensor, batch: int, thetas: Sequence[int], usable_rows: int, status: Optional[torch.Tensor] = None,
+                      layout=None, first_row: int = 0, arg_mask: int = 31, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A: uint8 [batch, 5, usable_rows, 32], the compressed lookup inputs of an advice image in ORIGINAL row order (h2r_lookup_input_columns);
+        the image's rows sit at first_row, every other usable row is 0.  thetas and A in the ctx's representation."""
+        kd = kinds if isinstance(kinds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(kinds, dtype=np.uint8)).to(image.device)
+        stride = image.shape[1] if image.dim() > 1 else image.numel() // batch
+        th_dev = self._challenges(thetas, batch, image.device)
+        a_in = out if out is not None else torch.empty((batch, self.ARGS, usable_rows, 32), dtype=torch.uint8, device=image.device)
+        check(lib().h2r_lookup_input_columns(self.chip._ctx, ctypes.byref(self.cfg), ctypes.byref(layout) if layout is not None else None, kd.data_ptr(),
+                                             kd.numel(), image.data_ptr(), stride, batch, status.data_ptr() if status is not None else None,
+                                             th_dev.data_ptr(), usable_rows, first_row, arg_mask, a_in.data_ptr(), self.ARGS * usable_rows * 32,
+                                             self.chip._stream()), "h2r_lookup_input_columns")
+        self._keep_in = (kd, th_dev)   # alive until the stream has run the kernel
+        return a_in
+
+    def product_columns(self, a_in: torch.Tensor, a_perm: torch.Tensor, s_perm: torch.Tensor, thetas: Sequence[int], betas: Sequence[int],
+                        gammas: Sequence[int], usable_rows: int, arg_mask: int = 31, out=None):
+        """(Z, status): Z uint8 [batch, 5, usable_rows + 1, 32], halo2's lookup grand product (h2r_lookup_product_columns) in the ctx's
+        representation; status H2R_E_ASSERTION where a denominator is zero or Z[usable_rows] != 1, H2R_E_SHAPE where a challenge is not canonical.
+        out: (z, status) to write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        batch, dev = a_in.shape[0], a_in.device
+        ch = [self._challenges(v, batch, dev) for v in (thetas, betas, gammas)]
+        if out is None:
+            z = torch.empty((batch, self.ARGS, usable_rows + 1, 32), dtype=torch.uint8, device=dev)
+            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        else:
+            z, status = out
+        ws = torch.empty(int(lib().h2r_lookup_product_workspace_bytes(usable_rows, batch)), dtype=torch.uint8, device=dev)
+        col = (usable_rows + 1) * 32
+        check(lib().h2r_lookup_product_columns(self.chip._ctx, ctypes.byref(self.cfg), a_in.data_ptr(), a_perm.data_ptr(), s_perm.data_ptr(),
+                                               self.ARGS * usable_rows * 32, ch[0].data_ptr(), ch[1].data_ptr(), ch[2].data_ptr(), batch, usable_rows,
+                                               arg_mask, z.data_ptr(), self.ARGS * col, col, status.data_ptr(), ws.data_ptr(), self.chip._stream()),
+              "h2r_lookup_product_columns")
+        self._keep_prod = (ch, ws)   # alive until the stream has run the kernels
+        return z, status
+
 
 @dataclass
 class FreshResult:

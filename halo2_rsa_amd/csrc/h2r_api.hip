@@ -23,6 +23,7 @@
 #include "h2r_copymap.hpp"
 #include "h2r_layout.hpp"
 #include "h2r_lookup.hpp"
+#include "h2r_lookup_product.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -3883,6 +3884,120 @@ int32_t h2r_lookup_hist_advice(const h2r_ctx *ctx, const h2r_lookup_config *cfg,
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
     hipLaunchKernelGGL(advice_hist_kernel, dim3((unsigned)blocks), dim3(256), 5u * cfg->n_rows * sizeof(u32), static_cast<hipStream_t>(stream), ha);
     HIP_TRY(hipGetLastError());
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the lookup argument's input columns A and grand-product columns Z (h2r_lookup_product.hpp, h2r_tu_lookup_product.hip) ------------
+namespace {
+// The table's rows all lie in the first tile of a column: the product kernels' table branch (and the timing tool's product counts) rest on it.
+static_assert(LOOKUP_MAX_ROWS <= (int)LOOKUP_PRODUCT_TILE, "the compressed table must fit one tile of the grand product");
+constexpr u32 kLookupMaxUsableRows = 1u << 28;   // (the kernels' row arithmetic is 32-bit; halo2 circuits end far below)
+// a configuration as h2r_lookup_config_default / _custom build it: row 0 = (0, 0), then 2^bit_len rows per length, back to back
+bool lookup_cfg_valid(const h2r_lookup_config *cfg) {
+    if (cfg->n_rows == 0 || cfg->n_rows > (u32)LOOKUP_MAX_ROWS || cfg->n_lens == 0 || cfg->n_lens > H2R_LOOKUP_MAX_LENS) return false;
+    u32 off = 1;
+    for (u32 i = 0; i < cfg->n_lens; ++i) {
+        if (cfg->bit_len[i] > 10 || cfg->row_off[i] != off) return false;
+        off += 1u << cfg->bit_len[i];
+    }
+    return off == cfg->n_rows;
+}
+// Circuits per launch: grid.z holds at most 65,535, and a launch's global size (threads) stays below 2^32.  0: even one circuit is too large.
+u64 lookup_launch_elems(u64 blocks_per_elem, u32 threads) {
+    const u64 per = ((1ull << 32) - 1) / (blocks_per_elem * threads);
+    return per < 65535 ? per : 65535;
+}
+}  // namespace
+
+int32_t h2r_lookup_input_columns(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const h2r_advice_layout *layout, const uint8_t *kinds_dev,
+                                 uint64_t rows, const void *image, uint64_t image_stride, uint64_t batch, const uint8_t *status,
+                                 const uint64_t *theta, uint32_t usable_rows, uint32_t first_row, uint32_t arg_mask, void *a_in_out,
+                                 uint64_t out_elem_stride, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !kinds_dev || !image || !theta || !a_in_out) return H2R_E_NULL;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (!lookup_cfg_valid(cfg)) return H2R_E_SHAPE;
+    h2r_advice_layout ident;
+    if (!layout) { h2r_advice_layout_default(&ident); layout = &ident; }
+    else if (const int32_t rc = layout_lookup_valid(layout)) return rc;
+    if (!usable_rows || usable_rows > kLookupMaxUsableRows) return H2R_E_SHAPE;
+    if ((u64)first_row + rows > usable_rows) return H2R_E_SHAPE;   // the image's rows occupy [first_row, first_row + rows) of the usable rows
+    if (out_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 || (out_elem_stride & 15) || (reinterpret_cast<u64>(a_in_out) & 15)) return H2R_E_SHAPE;
+    LookupInputArgs ia;
+    std::memset(static_cast<void *>(&ia), 0, sizeof ia);
+    if (const int32_t rc = advice_dst(ctx, const_cast<void *>(image), image_stride, rows, batch, &ia.img)) return rc;
+    if (!batch || !(arg_mask & 31u)) return H2R_OK;
+    // the tags of every row kind (those of h2r_advice_fixed_row; a layout permutes cells, never tags), as indices into the configuration
+    for (u32 k = 0; k < 256; ++k) {
+        h2r_fixed_row f;
+        if (fixed_row_repr(ctx, cfg, k, false, &f)) continue;   // (an unknown kind, or one whose lookup the configuration has no table for: h2r_advice_check flags its rows)
+        auto idx = [&](u32 tag) -> u32 { if (tag) for (u32 i = 0; i < cfg->n_lens; ++i) if (cfg->tag[i] == tag) return i + 1; return 0; };
+        ia.ktab[k] = (u8)(idx(f.tag_composition) | (idx(f.tag_overflow) << 4));
+    }
+    ia.kinds = kinds_dev; ia.rows = rows; ia.usable_rows = usable_rows; ia.first_row = first_row; ia.arg_mask = arg_mask & 31u;
+    ia.n_lens = cfg->n_lens;
+    for (u32 i = 0; i < cfg->n_lens; ++i) ia.tag[i] = cfg->tag[i];
+    for (int k = 0; k < 4; ++k) ia.p[k] = ctx->fc.p[k];
+    ia.out_elem_stride = out_elem_stride;
+    const u64 per = lookup_launch_elems((u64)LOOKUP_ARGS * ((usable_rows + 255) / 256), 256);
+    if (!per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (u64 e0 = 0; e0 < batch; e0 += per) {
+        const u64 ne = std::min(per, batch - e0);
+        ia.img.base = static_cast<u8 *>(const_cast<void *>(image)) + e0 * ia.img.elem_stride;
+        ia.status = status ? status + e0 : nullptr; ia.theta = theta + 4 * e0;
+        ia.out = static_cast<u8 *>(a_in_out) + e0 * out_elem_stride;
+        ProfScope ps(H2R_KERNEL_LOOKUP_INPUT, st, true);
+        HIP_TRY(launch_lookup_input(ia, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
+    }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+uint64_t h2r_lookup_product_workspace_bytes(uint32_t usable_rows, uint64_t num_elems) try {
+    return num_elems ? num_elems * LOOKUP_ARGS * lookup_product_slot_bytes(usable_rows) + 256 : 0;
+} H2R_CATCH_ZERO
+
+int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const void *a_in, const void *a_perm, const void *s_perm,
+                                   uint64_t in_elem_stride, const uint64_t *theta, const uint64_t *beta, const uint64_t *gamma,
+                                   uint64_t num_elems, uint32_t usable_rows, uint32_t arg_mask, void *z_out, uint64_t z_elem_stride,
+                                   uint64_t z_col_stride, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !a_in || !a_perm || !s_perm || !theta || !beta || !gamma || !z_out || !workspace) return H2R_E_NULL;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (!lookup_cfg_valid(cfg)) return H2R_E_SHAPE;
+    if (!usable_rows || usable_rows > kLookupMaxUsableRows || in_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 || (in_elem_stride & 15) || (reinterpret_cast<u64>(a_in) & 15) ||
+        (reinterpret_cast<u64>(a_perm) & 15) || (reinterpret_cast<u64>(s_perm) & 15)) return H2R_E_SHAPE;
+    const u64 zcol = ((u64)usable_rows + 1) * 32;
+    if (z_col_stride < zcol || (z_col_stride & 31) || (z_elem_stride & 15) || (reinterpret_cast<u64>(z_out) & 15)) return H2R_E_SHAPE;
+    if (num_elems > 65535) return H2R_E_UNSUPPORTED;
+    // [element][argument] (z_elem_stride covers the five columns) or [argument][element] (z_col_stride covers every element)
+    const bool elem_major = z_elem_stride >= (LOOKUP_ARGS - 1) * z_col_stride + zcol;
+    const bool col_major = num_elems == 0 || (z_elem_stride >= zcol && z_col_stride >= (num_elems - 1) * z_elem_stride + zcol);
+    if (!elem_major && !col_major) return H2R_E_SHAPE;
+    if (num_elems == 0 || !(arg_mask & 31u)) return H2R_OK;
+    LookupProductArgs pa;
+    std::memset(static_cast<void *>(&pa), 0, sizeof pa);
+    pa.in_elem_stride = in_elem_stride; pa.usable_rows = usable_rows; pa.n_tiles = lookup_product_tiles(usable_rows); pa.arg_mask = arg_mask & 31u;
+    pa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;
+    pa.n_rows = cfg->n_rows; pa.n_lens = cfg->n_lens;
+    for (u32 i = 0; i < cfg->n_lens; ++i) { pa.tag[i] = cfg->tag[i]; pa.row_off[i] = cfg->row_off[i]; }
+    pa.f = ctx->fc; pa.z_elem_stride = z_elem_stride; pa.z_col_stride = z_col_stride;
+    const u64 per = lookup_launch_elems((u64)LOOKUP_ARGS * pa.n_tiles, 256);
+    if (!per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    for (u64 e0 = 0; e0 < num_elems; e0 += per) {
+        const u64 ne = std::min(per, num_elems - e0);
+        pa.a_in = static_cast<const u8 *>(a_in) + e0 * in_elem_stride; pa.a_perm = static_cast<const u8 *>(a_perm) + e0 * in_elem_stride;
+        pa.s_perm = static_cast<const u8 *>(s_perm) + e0 * in_elem_stride;
+        pa.theta = theta + 4 * e0; pa.beta = beta + 4 * e0; pa.gamma = gamma + 4 * e0;
+        pa.z = static_cast<u8 *>(z_out) + e0 * z_elem_stride; pa.status = status ? status + e0 : nullptr;
+        pa.ws = ws + e0 * LOOKUP_ARGS * lookup_product_slot_bytes(usable_rows);
+        for (u32 phase = 0; phase < 3; ++phase) {
+            ProfScope ps(H2R_KERNEL_LOOKUP_PRODUCT_TILES + phase, st, true);
+            HIP_TRY(launch_lookup_product(phase, pa, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
+        }
+    }
     return H2R_OK;
 } H2R_CATCH_STATUS
 

@@ -7,6 +7,7 @@
 //   h2r_tu_step.hip    step_kernel<K, NW, LW, L>   (records of call k + chains of call k+1 in one launch)
 //   h2r_tu_chain_keyed.hip, h2r_tu_step_keyed.hip   the same two families' builds for keyed calls (H2R_F_KEYED_MODULI)
 //   h2r_tu_cells.hip   cells_kernel<LW, ABL, MONT, NWV> (the advice image directly from the operands)
+//   h2r_tu_lookup_product.hip   the lookup argument's input columns and grand product (h2r_lookup_product.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -102,5 +103,10 @@ hipError_t launch_step_shape_keyed(const StepShape &s, u32 num_cus, const ChainA
 u32 step_shared_bytes_shape(const StepShape &s);
 // h2r_tu_cells.hip.  `lds` = the dynamic LDS request (residency rule applied by the caller); nwv = waves per workgroup (Montgomery, long shapes).
 hipError_t launch_cells_shape(u32 w, bool mont, u32 nwv, u32 lds, const CellsArgs &ca, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_lookup_product.hip (argument structs: h2r_lookup_product.hpp).  phase 0 = the tiles' products, 1 = the carry-ins per column, 2 = the scans that write Z.
+struct LookupInputArgs;
+struct LookupProductArgs;
+hipError_t launch_lookup_input(const LookupInputArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_lookup_product(u32 phase, const LookupProductArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

@@ -783,6 +783,43 @@ int32_t h2r_lookup_permuted_columns(const h2r_ctx *ctx, const h2r_lookup_config 
                                     uint64_t num_elems, uint32_t usable_rows, uint32_t arg_mask, void *a_perm_out,
                                     void *s_perm_out, uint64_t out_elem_stride, uint8_t *status, void *workspace,
                                     h2r_stream_t stream);
+/* ---- the lookup argument after the permuted columns: the input column A and the grand-product column Z ----
+ * THIRD-PARTY behaviour (halo2 plonk::lookup::prover::commit_product, not in the reference tree), restated in DESIGN.md section 2d;
+ * parity is pinned against a Python restatement (tests/test_lookup_product.py), not against upstream.  Per circuit (= element) its own
+ * challenges theta, beta, gamma; per lookup argument k, with u = usable_rows:
+ *    A[i]  = tag(i) * theta + cell(i, column of k): the compressed input of row i in ORIGINAL row order (0 where the lookup is off),
+ *    S[i]  = the compressed table column: the table's n_rows rows, then 0,
+ *    Z[0]  = 1,  Z[i+1] = Z[i] * (A[i] + beta)(S[i] + gamma) / ((A'[i] + beta)(S'[i] + gamma)),  i = 0 .. u - 1.
+ * Z has u + 1 elements (upstream's n - blinding_factors; the random tail is the caller's); a well-formed argument has Z[u] = 1 -- an
+ * end-to-end audit that A' / S' are a permutation of the circuit's inputs and table, computed from the image where the columns lie.
+ *  - h2r_lookup_input_columns: A of every usable row of every selected argument from an advice image, read exactly as
+ *    h2r_lookup_hist_advice reads it (any representation, any layout; composition tag on columns a..d, overflow tag on column a; cells are
+ *    canonical representatives).  The image's rows occupy [first_row, first_row + rows) of the usable rows, every other usable row is
+ *    written 0; H2R_E_SHAPE when first_row + rows > usable_rows.  Output in the ctx's representation (theta too), in the layout of
+ *    a_perm_out: element e, argument k at + e * out_elem_stride + k * usable_rows * 32.  Elements with a nonzero status byte (nullable)
+ *    or a theta that is not canonical are skipped, their columns left untouched.
+ *  - h2r_lookup_product_columns: Z of element e, argument k at z_out + e * z_elem_stride + k * z_col_stride, u + 1 elements of 32 bytes in
+ *    the ctx's representation (z_col_stride >= (u + 1) * 32 and a multiple of 32: a prover passes 2^k * 32).  a_in / a_perm / s_perm: the
+ *    columns in the layout above (in_elem_stride); S is computed from cfg and theta, not read.  theta / beta / gamma: [num_elems][4] uint64
+ *    on the device, the ctx's representation.  status (nullable, [num_elems]) is never cleared by the call: elements whose byte is nonzero
+ *    on entry are skipped; H2R_E_SHAPE where a challenge is not canonical or n_rows > usable_rows (nothing is written for that circuit);
+ *    H2R_E_ASSERTION where for a selected argument the product of the denominators is 0 (that argument's Z is left untouched) or
+ *    Z[u] != 1 (the column is written as computed).  One field inversion per column; three launches, no workgroup waits for another.
+ *    At most 65,535 circuits per call (launches are sliced internally below the 2^32 global size).
+ *    workspace: h2r_lookup_product_workspace_bytes(usable_rows, num_elems) bytes on the device (a host function; no device needed).
+ *  - Both exports return H2R_E_SHAPE for usable_rows = 0 or > 2^28, for a configuration that is not one h2r_lookup_config_default / _custom
+ *    builds, and for strides or pointers that are not 16-byte aligned.  Z columns must not overlap: either z_elem_stride covers an element's
+ *    five columns (>= 4 * z_col_stride + (u + 1) * 32: [element][argument]) or z_col_stride covers every element's column
+ *    (>= (num_elems - 1) * z_elem_stride + (u + 1) * 32 with z_elem_stride >= (u + 1) * 32: [argument][element]); anything else is H2R_E_SHAPE. */
+int32_t h2r_lookup_input_columns(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const struct h2r_advice_layout *layout, const uint8_t *kinds_dev,
+                                 uint64_t rows, const void *image, uint64_t image_stride, uint64_t batch, const uint8_t *status,
+                                 const uint64_t *theta, uint32_t usable_rows, uint32_t first_row, uint32_t arg_mask, void *a_in_out,
+                                 uint64_t out_elem_stride, h2r_stream_t stream);
+uint64_t h2r_lookup_product_workspace_bytes(uint32_t usable_rows, uint64_t num_elems);
+int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const void *a_in, const void *a_perm, const void *s_perm,
+                                   uint64_t in_elem_stride, const uint64_t *theta, const uint64_t *beta, const uint64_t *gamma,
+                                   uint64_t num_elems, uint32_t usable_rows, uint32_t arg_mask, void *z_out, uint64_t z_elem_stride,
+                                   uint64_t z_col_stride, uint8_t *status, void *workspace, h2r_stream_t stream);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1074,7 +1111,9 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_STEP = 5 /* a pipeline step as one launch: records of call k + chains of call k+1 */,
        H2R_KERNEL_LOOKUP = 6 /* lookup_fill_kernel: the permuted columns */, H2R_KERNEL_SHA256 = 7 /* sha256_kernel */,
        H2R_KERNEL_CELLS = 8 /* cells_kernel: the advice image written directly from the operands */,
-       H2R_KERNEL_COUNT = 9 };
+       H2R_KERNEL_LOOKUP_INPUT = 9 /* lookup_input_kernel: the input columns A */,
+       H2R_KERNEL_LOOKUP_PRODUCT_TILES = 10, H2R_KERNEL_LOOKUP_PRODUCT_CARRY = 11, H2R_KERNEL_LOOKUP_PRODUCT_SCAN = 12 /* the grand product's three launches */,
+       H2R_KERNEL_COUNT = 13 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
