@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void lookup_setup_kernel(LookupSetupArgs a) {
     u32 *gid = order + n;                                    // group of sorted position i (inclusive scan of the run heads, minus one)
     u32 *gm = gid + n, *gs = gm + n, *gr = gs + n;           // per group: inputs, table entries, non-empty flag
     u32 *part = gr + n;                                      // [256]
-    u32 &total_in = part[256];
+    u32 &total_in = part[256], &too_many = part[257];
     const u32 arg = blockIdx.x % LOOKUP_ARGS;
     const u64 elem = blockIdx.x / LOOKUP_ARGS;
     if (!((a.arg_mask >> arg) & 1u)) return;
@@ -189,10 +189,10 @@ __global__ __launch_bounds__(256) void lookup_setup_kernel(LookupSetupArgs a) {
     const bool theta_ok = !ge_p(theta.v, a.f.p);
     if (a.mont && theta_ok) theta = fe_from_mont(theta, a.f);
     if (tid < a.n_lens) tagth[tid] = fe_mul_small(theta, a.tag[tid], a.f.p);
-    if (tid == 0) total_in = 0;
+    if (tid == 0) { total_in = 0; too_many = 0; }
     __syncthreads();
     // 1. compress: T[0] = 0 (the (0, 0) row), T[row_off[i] + v] = tag_i * theta + v
-    u32 my_in = 0;
+    u64 my_in = 0;   // (the counts are caller data: two of 2^31 must not add up to "no inputs")
     for (u32 r = tid; r < n; r += 256) {
         Fe t = fe_zero();
         if (r) {
@@ -203,10 +203,13 @@ __global__ __launch_bounds__(256) void lookup_setup_kernel(LookupSetupArgs a) {
         T[r] = t;
         my_in += h[r];
     }
-    atomicAdd(&total_in, my_in);
-    __syncthreads();
     const u32 usable = a.usable_rows;
-    const bool fits = total_in <= usable && n <= usable && theta_ok;   // (a challenge that is not a canonical element is refused too)
+    // the total stays below 2^32 or the circuit is refused: a thread's share above usable_rows, or an add whose running total wraps
+    // (the atomic returns the exact total before it), sets too_many
+    if (my_in > usable) too_many = 1;
+    else if (my_in) { const u32 before = atomicAdd(&total_in, (u32)my_in); if (before + (u32)my_in < before) too_many = 1; }
+    __syncthreads();
+    const bool fits = !too_many && total_in <= usable && n <= usable && theta_ok;   // (a challenge that is not a canonical element is refused too)
     if (!fits) {   // more lookup inputs (or table rows) than usable rows: no such circuit.  G = 0 tells the fill kernel to leave the columns alone
         if (tid == 0) {
             if (a.status) a.status[elem] = (u8)H2R_E_SHAPE;

@@ -724,7 +724,10 @@ int32_t h2r_trace_lookup_permutation_hist(const h2r_ctx *ctx, const void *trace,
  *    in a_perm_out and in s_perm_out (planar already: one contiguous vector per argument).
  *    At most 65,535 circuits per call.  theta: [num_elems][4] uint64 on the device, canonical (< p) little-endian (every proof has its own challenge).  status
  *    (nullable, [num_elems]): H2R_E_SHAPE where the lookup inputs or the table do not fit usable_rows or theta is not canonical
- *    (that circuit's columns are left untouched).  arg_mask: bit k = produce argument k. */
+ *    (that circuit's columns are left untouched).  arg_mask: bit k = produce argument k.
+ *    The counts are the caller's 32-bit words and are summed WITHOUT wrapping: an argument whose counts add up to more than
+ *    usable_rows is refused with H2R_E_SHAPE also where the sum passes 2^32 (two counts of 2^31, or 2^32 - 1 next to 2, are not
+ *    "0" or "1" inputs); every count of an accepted argument is therefore at most usable_rows. */
 #define H2R_LOOKUP_ARGS 5u
 #define H2R_LOOKUP_MAX_LENS 8u
 enum { H2R_LOOKUP_COMPOSITION_A = 0, H2R_LOOKUP_COMPOSITION_B, H2R_LOOKUP_COMPOSITION_C, H2R_LOOKUP_COMPOSITION_D, H2R_LOOKUP_OVERFLOW_A };
