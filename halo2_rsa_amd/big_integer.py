@@ -1177,6 +1177,59 @@ class LookupArgument:
         return z, status
 
 
+class PermutationArgument:
+    """halo2's permutation (copy-constraint) argument: the grand-product columns Z of permutation::prover::commit for per-circuit
+    challenges beta, gamma (h2r_permutation_product_columns).  Third-party behaviour restated in DESIGN.md section 2e.  The sigma columns
+    belong to the proving key and are the caller's.  column_src: per permutation column 0..4 = physical advice column, 5 + j = extra
+    column j; chunk_len = cs_degree - 2; delta, omega: integers in the chip's representation."""
+
+    def __init__(self, chip: BigIntChip, column_src: Sequence[int], chunk_len: int, delta: int, omega: int):
+        self.chip = chip
+        self.cfg = cfg = _lib.H2RPermutationConfig()
+        cfg.struct_size = ctypes.sizeof(cfg)
+        cfg.num_columns, cfg.chunk_len = len(column_src), chunk_len
+        if len(column_src) > _lib.H2R_PERM_MAX_COLUMNS:
+            check(_lib.H2R_E_SHAPE, "PermutationArgument")
+        cfg.n_extra = max([int(s) - 4 for s in column_src if int(s) >= 5] + [0])
+        for c, s in enumerate(column_src):
+            cfg.column_src[c] = int(s)
+        for k in range(4):
+            cfg.delta[k] = (int(delta) >> (64 * k)) & (2 ** 64 - 1)
+            cfg.omega[k] = (int(omega) >> (64 * k)) & (2 ** 64 - 1)
+        self.sets = int(lib().h2r_permutation_sets(ctypes.byref(cfg)))
+        if self.sets == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_permutation_sets")
+
+    _challenges = LookupArgument._challenges
+
+    def product_columns(self, image: torch.Tensor, batch: int, rows: int, sigma: torch.Tensor, betas: Sequence[int], gammas: Sequence[int],
+                        usable_rows: int, first_row: int = 0, extra: Optional[torch.Tensor] = None, out=None):
+        """(Z, status): Z uint8 [batch, S, usable_rows + 1, 32] in the chip's representation; status H2R_E_ASSERTION where a set's
+        denominators multiply to zero or the last Z does not end at 1, H2R_E_SHAPE where a challenge is not canonical.
+        image: the advice image of `rows` rows per circuit, at first_row of the usable rows; sigma: uint8 [m, >= usable_rows, 32] shared by
+        every circuit; extra: uint8 [batch, n_extra, >= usable_rows, 32]; betas / gammas: integers in the chip's representation.
+        out: (z, status) to write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        dev = image.device
+        ch = [self._challenges(v, batch, dev) for v in (betas, gammas)]
+        if out is None:
+            z = torch.empty((batch, self.sets, usable_rows + 1, 32), dtype=torch.uint8, device=dev)
+            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        else:
+            z, status = out
+        assert sigma.dim() == 3 and sigma.stride(2) == 1 and sigma.stride(1) == 32 and sigma.shape[0] == self.cfg.num_columns
+        if extra is not None:
+            assert extra.dim() == 4 and extra.stride(3) == 1 and extra.stride(2) == 32
+        ws = torch.empty(int(lib().h2r_permutation_product_workspace_bytes(ctypes.byref(self.cfg), usable_rows, batch)), dtype=torch.uint8, device=dev)
+        stride = image.shape[1] if image.dim() > 1 else image.numel() // max(batch, 1)
+        check(lib().h2r_permutation_product_columns(self.chip._ctx, ctypes.byref(self.cfg), image.data_ptr(), stride, rows, first_row, batch,
+                                                    extra.data_ptr() if extra is not None else None, extra.stride(0) if extra is not None else 0,
+                                                    extra.stride(1) if extra is not None else 0, sigma.data_ptr(), sigma.stride(0),
+                                                    ch[0].data_ptr(), ch[1].data_ptr(), usable_rows, z.data_ptr(), z.stride(0), z.stride(1),
+                                                    status.data_ptr(), ws.data_ptr(), self.chip._stream()), "h2r_permutation_product_columns")
+        self._keep_prod = (ch, ws, sigma, extra, image)   # alive until the stream has run the kernels
+        return z, status
+
+
 @dataclass
 class FreshResult:
     value: Optional[AssignedInteger]

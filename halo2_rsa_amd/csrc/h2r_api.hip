@@ -24,6 +24,7 @@
 #include "h2r_layout.hpp"
 #include "h2r_lookup.hpp"
 #include "h2r_lookup_product.hpp"
+#include "h2r_permutation_product.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -3996,6 +3997,100 @@ int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *
         for (u32 phase = 0; phase < 3; ++phase) {
             ProfScope ps(H2R_KERNEL_LOOKUP_PRODUCT_TILES + phase, st, true);
             HIP_TRY(launch_lookup_product(phase, pa, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
+        }
+    }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the permutation argument's grand-product columns Z (h2r_permutation_product.hpp, h2r_tu_permutation_product.hip) ------------------------
+namespace {
+static_assert(H2R_PERM_MAX_COLUMNS == PERM_MAX_COLUMNS, "h2r.h and the kernels' argument struct");
+// what h2r_permutation_sets answers 0 for: the parts of a configuration that need no ctx (delta and omega are compared with the ctx's p)
+bool perm_cfg_valid(const h2r_permutation_config *cfg) {
+    if (cfg->struct_size != sizeof(h2r_permutation_config)) return false;
+    if (cfg->num_columns == 0 || cfg->num_columns > H2R_PERM_MAX_COLUMNS || cfg->chunk_len == 0 || cfg->n_extra > H2R_PERM_MAX_EXTRA) return false;
+    u32 seen = 0;
+    for (u32 c = 0; c < cfg->num_columns; ++c) {
+        const u32 src = cfg->column_src[c];
+        if (src >= 5 + cfg->n_extra || ((seen >> src) & 1u)) return false;
+        seen |= 1u << src;
+    }
+    return true;
+}
+u32 perm_sets(const h2r_permutation_config *cfg) {
+    const u32 chunk = std::min<u32>(cfg->chunk_len, cfg->num_columns);   // (a chunk beyond m is one set)
+    return (cfg->num_columns + chunk - 1) / chunk;
+}
+}  // namespace
+
+uint32_t h2r_permutation_sets(const h2r_permutation_config *cfg) try {
+    return cfg && perm_cfg_valid(cfg) ? perm_sets(cfg) : 0;
+} H2R_CATCH_ZERO
+
+uint64_t h2r_permutation_product_workspace_bytes(const h2r_permutation_config *cfg, uint32_t usable_rows, uint64_t num_elems) try {
+    if (!cfg || !perm_cfg_valid(cfg) || !num_elems) return 0;
+    return num_elems * perm_product_slot_bytes(usable_rows, perm_sets(cfg)) + 256;
+} H2R_CATCH_ZERO
+
+int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutation_config *cfg, const void *image, uint64_t image_stride,
+                                        uint64_t rows, uint32_t first_row, uint64_t batch, const void *extra, uint64_t extra_elem_stride,
+                                        uint64_t extra_col_stride, const void *sigma, uint64_t sigma_col_stride, const uint64_t *beta,
+                                        const uint64_t *gamma, uint32_t usable_rows, void *z_out, uint64_t z_elem_stride,
+                                        uint64_t z_col_stride, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !image || !sigma || !beta || !gamma || !z_out || !workspace) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_permutation_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->n_extra && cfg->n_extra <= H2R_PERM_MAX_EXTRA && !extra) return H2R_E_NULL;
+    if (!perm_cfg_valid(cfg)) return H2R_E_SHAPE;
+    if (ge_p(cfg->delta, ctx->fc.p) || ge_p(cfg->omega, ctx->fc.p)) return H2R_E_SHAPE;
+    if (!usable_rows || usable_rows > kLookupMaxUsableRows) return H2R_E_SHAPE;
+    if ((u64)first_row + rows > usable_rows) return H2R_E_SHAPE;   // the image's rows occupy [first_row, first_row + rows) of the usable rows
+    auto misaligned = [](const void *p, u64 s0, u64 s1) { return ((reinterpret_cast<u64>(p) | s0 | s1) & 15) != 0; };
+    if (misaligned(image, image_stride, 0) || misaligned(sigma, sigma_col_stride, 0) || misaligned(z_out, z_elem_stride, z_col_stride)) return H2R_E_SHAPE;
+    if (cfg->n_extra && misaligned(extra, extra_elem_stride, extra_col_stride)) return H2R_E_SHAPE;
+    if (sigma_col_stride < (u64)usable_rows * 32) return H2R_E_SHAPE;
+    const u32 S = perm_sets(cfg);
+    const u64 zcol = ((u64)usable_rows + 1) * 32;
+    if (z_col_stride < zcol || (z_col_stride & 31)) return H2R_E_SHAPE;
+    // [element][set] (z_elem_stride covers the S columns) or [set][element] (z_col_stride covers every element)
+    const bool elem_major = z_elem_stride >= (S - 1) * z_col_stride + zcol;
+    const bool col_major = batch == 0 || (z_elem_stride >= zcol && z_col_stride >= (batch - 1) * z_elem_stride + zcol);
+    if (!elem_major && !col_major) return H2R_E_SHAPE;
+    PermProductArgs pa;
+    std::memset(static_cast<void *>(&pa), 0, sizeof pa);
+    if (const int32_t rc = advice_dst(ctx, const_cast<void *>(image), image_stride, rows, batch, &pa.img)) return rc;
+    if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    const FieldConsts &f = ctx->fc;
+    pa.mont = pa.img.mont;
+    pa.rows = rows; pa.first_row = first_row; pa.usable_rows = usable_rows; pa.n_tiles = perm_product_tiles(usable_rows);
+    pa.m = cfg->num_columns; pa.chunk_len = std::min<u32>(cfg->chunk_len, cfg->num_columns); pa.n_sets = S;
+    for (u32 c = 0; c < cfg->num_columns; ++c) pa.src[c] = cfg->column_src[c];
+    // delta^c and omega^(2^b) in Montgomery form, whichever form the configuration holds them in
+    Fe delta, omega;
+    for (int k = 0; k < 4; ++k) { delta.v[k] = cfg->delta[k]; omega.v[k] = cfg->omega[k]; pa.dpow[0].v[k] = f.one[k]; }
+    if (!pa.mont) { delta = fe_to_mont(delta, f); omega = fe_to_mont(omega, f); }
+    for (u32 c = 1; c < PERM_MAX_COLUMNS; ++c) pa.dpow[c] = fe_mont_mul(pa.dpow[c - 1], delta, f);
+    pa.wpow[0] = omega;
+    for (u32 b = 1; b < PERM_OMEGA_BITS; ++b) pa.wpow[b] = fe_mont_mul(pa.wpow[b - 1], pa.wpow[b - 1], f);
+    pa.f = f;
+    pa.extra_elem_stride = cfg->n_extra ? extra_elem_stride : 0; pa.extra_col_stride = cfg->n_extra ? extra_col_stride : 0;
+    pa.sigma = static_cast<const u8 *>(sigma); pa.sigma_col_stride = sigma_col_stride;
+    pa.z_elem_stride = z_elem_stride; pa.z_col_stride = z_col_stride;
+    const u64 per = lookup_launch_elems((u64)S * pa.n_tiles, 256);
+    if (!per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    for (u64 e0 = 0; e0 < batch; e0 += per) {
+        const u64 ne = std::min(per, batch - e0);
+        pa.img.base = static_cast<u8 *>(const_cast<void *>(image)) + e0 * pa.img.elem_stride;
+        pa.extra = cfg->n_extra ? static_cast<const u8 *>(extra) + e0 * extra_elem_stride : nullptr;
+        pa.beta = beta + 4 * e0; pa.gamma = gamma + 4 * e0;
+        pa.z = static_cast<u8 *>(z_out) + e0 * z_elem_stride; pa.status = status ? status + e0 : nullptr;
+        pa.ws = ws + e0 * perm_product_slot_bytes(usable_rows, S);
+        for (u32 phase = 0; phase < 3; ++phase) {
+            ProfScope ps(H2R_KERNEL_PERM_PRODUCT_TILES + phase, st, true);
+            HIP_TRY(launch_perm_product(phase, pa, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
         }
     }
     return H2R_OK;

@@ -18,7 +18,8 @@
 // All arithmetic is in the Montgomery domain (fe_mont_mul); a canonical ctx converts on load and on store, a Montgomery ctx nothing.
 //   lookup_input_kernel           A: one workgroup per dense 256-row window of one column, one row per lane, lanes exchange halves so
 //                                 that each 16-byte non-temporal store instruction covers whole 128-byte lines (lookup_fill_kernel's geometry).
-// The kernels are defined in the one translation unit that launches them (h2r_tu_lookup_product.hip, H2R_TU_LOOKUP_PRODUCT).
+// The kernels are defined in the one translation unit that launches them (h2r_tu_lookup_product.hip, H2R_TU_LOOKUP_PRODUCT); the lp_*
+// device helpers are shared with the permutation argument's product (h2r_permutation_product.hpp, H2R_TU_PERM_PRODUCT).
 #pragma once
 
 #include "h2r_field.hpp"
@@ -57,7 +58,7 @@ struct LookupProductArgs {
     u8 *ws;                        // [elem][5] slots of lookup_product_slot_bytes
 };
 
-#ifdef H2R_TU_LOOKUP_PRODUCT
+#if defined(H2R_TU_LOOKUP_PRODUCT) || defined(H2R_TU_PERM_PRODUCT)
 
 __device__ __forceinline__ Fe lp_load(const u8 *p) {
     const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(p)[0], hi = reinterpret_cast<const ulonglong2 *>(p)[1];
@@ -66,6 +67,7 @@ __device__ __forceinline__ Fe lp_load(const u8 *p) {
 }
 __device__ __forceinline__ Fe lp_words(const u64 *w) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = w[k]; return r; }
 
+#ifdef H2R_TU_LOOKUP_PRODUCT
 __global__ __launch_bounds__(256) void lookup_input_kernel(LookupInputArgs a) {
     __shared__ Fe tagth[8];
     __shared__ u8 ktab[256];
@@ -103,13 +105,22 @@ __global__ __launch_bounds__(256) void lookup_input_kernel(LookupInputArgs a) {
     }
 }
 
+#endif  // H2R_TU_LOOKUP_PRODUCT
+
 // ---- the grand product ---------------------------------------------------------------------------------------------------------
 struct LpChallenges { Fe theta, beta, gamma; bool ok; };   // Montgomery form; ok: all three were canonical elements
+// one challenge (four words in the ctx's representation) in Montgomery form; clears ok when it is not a canonical element
+__device__ __forceinline__ Fe lp_challenge(const u64 *w, const FieldConsts &f, u32 mont, bool &ok) {
+    Fe c = lp_words(w);
+    if (ge_p(c.v, f.p)) ok = false;
+    else if (!mont) c = fe_to_mont(c, f);
+    return c;
+}
 __device__ __forceinline__ LpChallenges lp_challenges(const LookupProductArgs &a, u64 elem) {
     LpChallenges c;
-    c.theta = lp_words(a.theta + elem * 4); c.beta = lp_words(a.beta + elem * 4); c.gamma = lp_words(a.gamma + elem * 4);
-    c.ok = !ge_p(c.theta.v, a.f.p) && !ge_p(c.beta.v, a.f.p) && !ge_p(c.gamma.v, a.f.p);
-    if (c.ok && !a.mont) { c.theta = fe_to_mont(c.theta, a.f); c.beta = fe_to_mont(c.beta, a.f); c.gamma = fe_to_mont(c.gamma, a.f); }
+    c.ok = true;
+    c.theta = lp_challenge(a.theta + elem * 4, a.f, a.mont, c.ok); c.beta = lp_challenge(a.beta + elem * 4, a.f, a.mont, c.ok);
+    c.gamma = lp_challenge(a.gamma + elem * 4, a.f, a.mont, c.ok);
     return c;
 }
 __device__ __forceinline__ Fe lp_one(const LookupProductArgs &a) { return lp_words(a.f.one); }
@@ -152,6 +163,7 @@ __device__ __forceinline__ u8 *lp_slot(const LookupProductArgs &a, u64 elem, u32
     return a.ws + (elem * 5 + arg) * lookup_product_slot_bytes(a.usable_rows);
 }
 
+#ifdef H2R_TU_LOOKUP_PRODUCT
 __global__ __launch_bounds__(256) void lookup_product_tiles_kernel(LookupProductArgs a) {
     __shared__ Fe tagth[8];
     __shared__ Fe wtot[2][4];
@@ -281,5 +293,7 @@ __global__ __launch_bounds__(256) void lookup_product_scan_kernel(LookupProductA
 }
 
 #endif  // H2R_TU_LOOKUP_PRODUCT
+
+#endif  // H2R_TU_LOOKUP_PRODUCT || H2R_TU_PERM_PRODUCT
 
 }  // namespace h2r

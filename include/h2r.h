@@ -823,6 +823,56 @@ int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *
                                    uint64_t in_elem_stride, const uint64_t *theta, const uint64_t *beta, const uint64_t *gamma,
                                    uint64_t num_elems, uint32_t usable_rows, uint32_t arg_mask, void *z_out, uint64_t z_elem_stride,
                                    uint64_t z_col_stride, uint8_t *status, void *workspace, h2r_stream_t stream);
+/* ---- the permutation (copy-constraint) argument: the grand-product columns Z ----
+ * THIRD-PARTY behaviour (halo2 plonk::permutation::prover::commit, not in the reference tree), restated in DESIGN.md section 2e; parity is
+ * pinned against a Python restatement (tests/permutation_ref.py, tests/test_permutation_product.py), not against upstream.  The sigma columns
+ * belong to the proving key and stay the caller's; Z is built per proof.  Per circuit (= element) its own challenges beta, gamma; with
+ * u = usable_rows, m = num_columns permutation columns in S = ceil(m / chunk_len) sets (chunk_len = upstream's cs_degree - 2; set s holds
+ * the columns [s * chunk_len, min(m, (s + 1) * chunk_len))):
+ *    v_c(i)     = the value of permutation column c at usable row i.  column_src[c] = 0..4: the PHYSICAL column of the advice image, whose
+ *                 rows occupy [first_row, first_row + rows) of the usable rows, every other usable row reads 0 (no row kinds, no
+ *                 h2r_advice_layout: sigma is the caller's and already in physical terms); 5 + j: the caller's extra column j (an instance
+ *                 column, a fixed column enabled for equality), a planar vector of u elements,
+ *    label_c(i) = delta^c * omega^i with c the GLOBAL column index (delta = F::DELTA, omega = the domain's generator: the caller's),
+ *    sigma_c(i) = element i of the caller's sigma column c: the label of the cell that (c, i) maps to,
+ *    n_s(i)     = prod_{c in set s} (v_c(i) + beta * label_c(i) + gamma),   d_s(i) = prod_{c in set s} (v_c(i) + beta * sigma_c(i) + gamma),
+ *    Z_0[0] = 1,  Z_s[0] = Z_{s-1}[u],  Z_s[i+1] = Z_s[i] * n_s(i) / d_s(i),  i = 0 .. u - 1.
+ * Every Z_s has u + 1 elements (the random blinding tail stays the caller's, as for the lookup Z); a satisfied circuit has Z_{S-1}[u] = 1 --
+ * an end-to-end audit of the copy constraints by another route than h2r_advice_check's pair-by-pair comparison.
+ *  - h2r_permutation_sets: S of a configuration; 0 for one the call would refuse (struct_size, num_columns, chunk_len, n_extra, column_src).
+ *  - h2r_permutation_product_columns: Z of element e, set s at z_out + e * z_elem_stride + s * z_col_stride, u + 1 elements of 32 bytes
+ *    (z_col_stride >= (u + 1) * 32 and a multiple of 32: a prover passes 2^k * 32).  Everything is in the ctx's representation: the image
+ *    (h2r_advice_repr), the extra columns (element e, extra j at extra + e * extra_elem_stride + j * extra_col_stride, u elements; NULL iff
+ *    n_extra == 0), sigma ([m] columns of u elements at sigma + c * sigma_col_stride, SHARED by every element), delta, omega, beta, gamma
+ *    ([batch][4] uint64 on the device) and Z.  omega need not be a root of unity as far as this export is concerned.  The call enqueues and
+ *    never synchronises.  status (nullable, [batch]) is never cleared by the call: elements whose byte is nonzero on entry are skipped and
+ *    nothing is written for them; H2R_E_SHAPE where beta or gamma is not canonical (nothing is written for that circuit); H2R_E_ASSERTION
+ *    where the product of a set's denominators is 0 (the sets before it are written, that set and every later one are left untouched) or
+ *    Z_{S-1}[u] != 1 (every column is written as computed).  One field inversion per set; three launches, no workgroup waits for another.
+ *    At most 65,535 circuits per call (launches are sliced internally below the 2^32 global size).
+ *    workspace: h2r_permutation_product_workspace_bytes(cfg, usable_rows, num_elems) bytes on the device (a host function; no device
+ *    needed; 0 for no elements or a configuration the call would refuse).
+ *  - H2R_E_NULL for a NULL required pointer (status is optional; extra is required exactly when n_extra > 0), H2R_E_UNSUPPORTED for another
+ *    struct_size, a host-only ctx or more than 65,535 circuits, H2R_E_SHAPE for usable_rows = 0 or > 2^28, first_row + rows > usable_rows,
+ *    num_columns = 0 or > 8, chunk_len = 0, n_extra > 3, a column_src that is out of range or repeated, delta or omega >= p, a pointer or
+ *    stride that is not 16-byte aligned, sigma_col_stride < u * 32, and Z columns that overlap: either z_elem_stride covers an element's S
+ *    columns (>= (S - 1) * z_col_stride + (u + 1) * 32: [element][set]) or z_col_stride covers every element's column
+ *    (>= (batch - 1) * z_elem_stride + (u + 1) * 32 with z_elem_stride >= (u + 1) * 32: [set][element]). */
+#define H2R_PERM_MAX_COLUMNS 8u
+#define H2R_PERM_MAX_EXTRA 3u
+typedef struct h2r_permutation_config {
+    uint32_t struct_size;              /* sizeof; anything else: H2R_E_UNSUPPORTED */
+    uint32_t num_columns, chunk_len, n_extra;
+    uint8_t  column_src[H2R_PERM_MAX_COLUMNS]; /* per permutation column: 0..4 = physical advice column, 5 + j = extra column j */
+    uint64_t delta[4], omega[4];       /* the ctx's representation; canonical (< p) */
+} h2r_permutation_config;
+uint32_t h2r_permutation_sets(const h2r_permutation_config *cfg);
+uint64_t h2r_permutation_product_workspace_bytes(const h2r_permutation_config *cfg, uint32_t usable_rows, uint64_t num_elems);
+int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutation_config *cfg, const void *image, uint64_t image_stride,
+                                        uint64_t rows, uint32_t first_row, uint64_t batch, const void *extra, uint64_t extra_elem_stride,
+                                        uint64_t extra_col_stride, const void *sigma, uint64_t sigma_col_stride, const uint64_t *beta,
+                                        const uint64_t *gamma, uint32_t usable_rows, void *z_out, uint64_t z_elem_stride,
+                                        uint64_t z_col_stride, uint8_t *status, void *workspace, h2r_stream_t stream);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1116,7 +1166,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_CELLS = 8 /* cells_kernel: the advice image written directly from the operands */,
        H2R_KERNEL_LOOKUP_INPUT = 9 /* lookup_input_kernel: the input columns A */,
        H2R_KERNEL_LOOKUP_PRODUCT_TILES = 10, H2R_KERNEL_LOOKUP_PRODUCT_CARRY = 11, H2R_KERNEL_LOOKUP_PRODUCT_SCAN = 12 /* the grand product's three launches */,
-       H2R_KERNEL_COUNT = 13 };
+       H2R_KERNEL_PERM_PRODUCT_TILES = 13, H2R_KERNEL_PERM_PRODUCT_CARRY = 14, H2R_KERNEL_PERM_PRODUCT_SCAN = 15 /* the permutation argument's grand product, likewise */,
+       H2R_KERNEL_COUNT = 16 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 

@@ -1,0 +1,321 @@
+"""h2r_permutation_product_columns: the grand-product columns Z of halo2's permutation argument (plonk::permutation::prover::commit [3P,
+restated in DESIGN.md section 2e]) against the plain model of tests/permutation_ref.py, byte for byte.
+
+Images are the modpow_public_key elements of tests/test_lookup_product.py ([assert_in_field rows][pow rows], three circuits); the copy pairs
+are h2r_pow_copy_map's, the sigma columns the model's (union-find over the pairs), and h2r_advice_check must accept the same pairs on the
+same image.  The kernels work in tiles of PERM_PRODUCT_TILE rows (read from csrc/h2r_permutation_product.hpp); the usable rows are chosen
+against it: under one tile (1,018), eight tiles with a ragged last one (8,186), exactly two tiles (Z[u] behind the last tile), and for the
+carry wave 65 tiles + 3 rows (a lane of the carry wave holds two tiles) and 129 tiles - 1 row (three tiles per lane, and lanes without any)."""
+import os
+import random
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+import permutation_ref as PR
+from test_lookup_product import _P, bytes_of, in_repr, rand_modulus, usable_for
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R256 = 1 << 256
+SENTINEL = 0xAB
+with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_permutation_product.hpp")) as _f:
+    TILE = int(re.search(r"PERM_PRODUCT_TILE = (\d+);", _f.read()).group(1))
+
+
+@pytest.fixture(scope="module")
+def H():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import halo2_rsa_amd as H_
+    return H_
+
+
+def domain_k(u):
+    """The smallest k with 2^k >= u + 6 (halo2's blinding rows + 1 behind the usable ones)."""
+    return (u + 5).bit_length()
+
+
+def decode(chip, elem_host, rows, P):
+    """One element's image bytes -> [[5 canonical integers]] in any representation (planar: packed or with the chip's column stride)."""
+    a = np.ascontiguousarray(elem_host, dtype=np.uint8)
+    if chip.columns:
+        cs = chip.col_stride or rows * 32
+        a = a.reshape(5, cs)[:, :rows * 32].reshape(5, rows, 32).transpose(1, 0, 2)
+    else:
+        a = a.reshape(rows, 5, 32)
+    w = np.ascontiguousarray(a).view("<u8").reshape(rows * 5, 4).tolist()
+    cells = [x0 | x1 << 64 | x2 << 128 | x3 << 192 for x0, x1, x2, x3 in w]
+    assert all(v < P for v in cells)
+    if chip.montgomery:
+        rinv = pow(R256, -1, P)
+        cells = [v * rinv % P if v else 0 for v in cells]
+    return [cells[5 * r:5 * r + 5] for r in range(rows)]
+
+
+def columns_tensor(cols, u, P, montgomery):
+    """[[u integers]] -> uint8 [len(cols), u, 32] on the device, in the ctx's representation."""
+    return torch.from_numpy(np.stack([bytes_of(c[:u], P, montgomery) for c in cols])).cuda()
+
+
+class Case:
+    """A batch of modpow_public_key elements on the GPU, its copy pairs, and everything the model needs of it."""
+
+    def __init__(self, H, w, L, e, field, B=3, seed=1, **repr_kw):
+        import ctypes
+        from halo2_rsa_amd import _lib
+        from halo2_rsa_amd._lib import lib
+        self.H, self.P, self.B = H, _P(field), B
+        self.chip = chip = H.BigIntChip(w, w * L, field=field, **repr_kw)
+        rng = random.Random(seed)
+        N = [rand_modulus(rng, w * L) for _ in range(B)]
+        X = [rng.randrange(n) for n in N]
+        self.x, self.n = chip.assign_integer(X), chip.assign_integer(N)
+        res = chip.pow_mod_fixed_exp(self.x, e, self.n, check_in_field=True)
+        assert not res.status.cpu().numpy().any()
+        pl = res.trace.pow_layout
+        k_if = chip.fresh_op_row_kinds(_lib.FRESH_OPS.index("is_in_field"), assert_one=True)
+        k_pow = np.zeros(int(lib().h2r_pow_advice_rows(chip._ctx, ctypes.byref(pl))), dtype=np.uint8)
+        assert lib().h2r_pow_row_kinds(chip._ctx, ctypes.byref(pl), k_pow.ctypes.data) == 0
+        self.kinds = np.concatenate([k_if, k_pow])
+        self.rows = len(self.kinds)
+        self.image = res.emit_modpow_advice()
+        torch.cuda.synchronize()
+        self.copies = chip.pow_copy_map(pl, e, row_offset=len(k_if))                   # rows counted inside the image
+        self.pairs = [(c.row, c.col, c.src_row, c.src_col) for c in self.copies]
+        assert any(p[2] not in PR.H2R_COPY_SRC for p in self.pairs) and all(p[1] < 5 and (p[3] < 5 or p[2] in PR.H2R_COPY_SRC) for p in self.pairs)
+        self.cells = self.decode(self.image)
+
+    def decode(self, image):
+        host = image.cpu().numpy().reshape(self.B, -1)
+        return [decode(self.chip, host[b], self.rows, self.P) for b in range(self.B)]
+
+    def advice_check(self, image):
+        bad, _ = self.chip.advice_check(self.kinds, image, self.B, copies=self.copies, src_a=self.x, src_n=self.n)
+        return bad.cpu().tolist()
+
+    def copy_violations(self, image):
+        """h2r_advice_check's code-3 count per circuit: every violated copy pair counts once, so it is what the pairs add to the violations."""
+        without, _ = self.chip.advice_check(self.kinds, image, self.B, src_a=self.x, src_n=self.n)
+        return [a - b for a, b in zip(self.advice_check(image), without.cpu().tolist())]
+
+    def sigma(self, column_src, u, delta, omega, first_row=0):
+        """The model's sigma columns [m][u] of the image's copy pairs, the image's rows placed at first_row."""
+        column_of = {src: c for c, src in enumerate(column_src) if src < 5}
+        shifted = [(r + first_row, c, sr if sr in PR.H2R_COPY_SRC else sr + first_row, sc) for r, c, sr, sc in self.pairs]
+        return PR.sigma_from_pairs(shifted, len(column_src), u, delta, omega, self.P, column_of=column_of)
+
+    def argument(self, column_src, chunk, delta, omega):
+        d, o = in_repr([delta, omega], self.P, self.chip.montgomery)
+        return self.H.PermutationArgument(self.chip, column_src, chunk, d, o)
+
+    def run(self, pa, sigma_dev, betas, gammas, u, first_row=0, extra=None, image=None, out=None):
+        m, P = self.chip.montgomery, self.P
+        z, st = pa.product_columns(self.image if image is None else image, self.B, self.rows, sigma_dev, in_repr(betas, P, m), in_repr(gammas, P, m),
+                                   u, first_row=first_row, extra=extra, out=out)
+        torch.cuda.synchronize()
+        return z, st.cpu().tolist()
+
+    def assert_columns(self, z_b, want, what=None):
+        """z_b: the device's [S, >= u + 1, 32] of one circuit; want: the model's S columns."""
+        zh = z_b.cpu().numpy()
+        assert zh.shape[0] == len(want)
+        for s, col in enumerate(want):
+            assert np.array_equal(zh[s, :len(col)], bytes_of(col, self.P, self.chip.montgomery)), (what, s)
+
+
+def random_domain(P, m, u, rng):
+    """omega, delta for a field without a 2^k subgroup: random elements whose labels delta^c * omega^i are pairwise distinct."""
+    omega, delta = rng.randrange(2, P), rng.randrange(2, P)
+    lab = PR.labels(m, u, delta, omega, P)
+    assert len({x for col in lab for x in col}) == m * u
+    return omega, delta
+
+
+def true_domain(P, u):
+    k = domain_k(u)
+    omega, delta = PR.domain(P, k)
+    assert pow(omega, 1 << k, P) == 1 and pow(omega, 1 << (k - 1), P) != 1 and (1 << k) >= u + 6
+    return omega, delta
+
+
+def challenges(P, seed, B=3):
+    """beta, gamma per circuit: random, circuit 0 with gamma = P - 1."""
+    rng = random.Random(seed)
+    return [rng.randrange(1, P) for _ in range(B)], [P - 1] + [rng.randrange(P) for _ in range(B - 1)]
+
+
+# ---- 1. parity ---------------------------------------------------------------------------------------------------------------------
+PARITY = [  # (w, L, e, field, true domain, usable_rows (None: 2^k - 6 for the smallest k that fits), first_row, column_src, chunks)
+    (64, 4, 1, "bn254_fq", False, None, 0, (0, 1, 2, 3, 4), (2,)),                    # 746 rows in 1,018: under one tile; the last set is one column
+    (64, 4, 65537, "bn254_fr", True, None, 0, (2, 0, 5, 1, 4, 3), (1, 2, 3, 6)),      # 4,996 rows in 8,186: ragged last tile; one extra column
+    (32, 8, 0b1011, "pasta_fp", True, None, 7, (0, 1, 2, 3, 4), (3,)),                # 4,560 rows from row 7 of 8,186
+    (64, 4, 1, "bn254_fq", False, 2 * TILE, 7, (0, 1, 2, 3, 4), (2,)),                # Z[usable_rows] lies behind the last tile
+]
+
+
+@pytest.mark.parametrize("w,L,e,field,domain,usable,first_row,column_src,chunks", PARITY)
+def test_parity_with_the_plain_model(H, w, L, e, field, domain, usable, first_row, column_src, chunks):
+    c = Case(H, w, L, e, field, seed=w + L + e)
+    P, m = c.P, len(column_src)
+    u = usable or usable_for(c.rows + first_row)
+    tiles = (u + TILE - 1) // TILE
+    print("rows %d usable %d tiles %d pairs %d" % (c.rows, u, tiles, len(c.pairs)))
+    if e == 65537:
+        assert tiles >= 3 and u % TILE
+    if e == 1:
+        assert u < TILE or u == 2 * TILE
+    assert c.advice_check(c.image) == [0, 0, 0]                                        # the pairs hold on this image
+    rng = random.Random(u + m)
+    omega, delta = true_domain(P, u) if domain else random_domain(P, m, u, rng)
+    sigma = c.sigma(column_src, u, delta, omega, first_row)
+    sigma_dev = columns_tensor(sigma, u, P, c.chip.montgomery)
+    extra_vals = [[[rng.randrange(P) for _ in range(u)]] for _ in range(3)] if m > 5 else None
+    extra_dev = torch.stack([columns_tensor(x, u, P, c.chip.montgomery) for x in extra_vals]) if m > 5 else None
+    betas, gammas = challenges(P, u)
+    for chunk in chunks:
+        pa = c.argument(column_src, chunk, delta, omega)
+        S = (m + chunk - 1) // chunk
+        assert pa.sets == S
+        z, st = c.run(pa, sigma_dev, betas, gammas, u, first_row, extra=extra_dev)
+        assert st == [0, 0, 0], chunk
+        assert z.shape == (3, S, u + 1, 32)
+        for b in range(3):
+            want = PR.product(c.cells[b], extra_vals[b] if m > 5 else None, sigma, column_src, chunk, delta, omega, betas[b], gammas[b], u, P, first_row)
+            assert want[0][0] == 1 and want[-1][u] == 1 and all(want[s][0] == want[s - 1][u] for s in range(1, S))
+            c.assert_columns(z[b], want, (chunk, b))
+            for s in range(1, S):                                                      # Z_s[0] == Z_{s-1}[u] on the device's own bytes
+                assert torch.equal(z[b, s, 0], z[b, s - 1, u])
+
+
+# ---- 2. the carry wave: more tiles than lanes, fewer tiles than lanes -----------------------------------------------------------------
+@pytest.mark.parametrize("u", [65 * TILE + 3, 129 * TILE - 1])
+def test_carry_wave_with_several_tiles_per_lane(H, u):
+    P = _P("bn254_fr")
+    chip = H.BigIntChip(64, 256, field="bn254_fr")
+    rng = random.Random(u)
+    omega, delta = PR.domain(P, domain_k(u))
+    v, pairs = PR.satisfying_cells(rng, 2, u, 300, P)
+    sigma = PR.sigma_from_pairs(pairs, 2, u, delta, omega, P)
+    img = np.zeros((u, 5, 32), dtype=np.uint8)                                         # a row-major image of u rows, columns a and b assigned
+    img[:, 0], img[:, 1] = bytes_of(v[0], P, False), bytes_of(v[1], P, False)
+    image = torch.from_numpy(img.reshape(1, -1)).cuda()
+    beta, gamma = rng.randrange(1, P), rng.randrange(P)
+    pa = H.PermutationArgument(chip, (0, 1), 1, delta, omega)
+    guard = 3
+    z = torch.full((1, 2, u + 1 + guard, 32), SENTINEL, dtype=torch.uint8, device="cuda")
+    st = torch.zeros(1, dtype=torch.uint8, device="cuda")
+    pa.product_columns(image, 1, u, columns_tensor(sigma, u, P, False), [beta], [gamma], u, out=(z, st))
+    torch.cuda.synchronize()
+    assert st.cpu().tolist() == [0]
+    cells = [[a, b, 0, 0, 0] for a, b in zip(v[0], v[1])]
+    want = PR.product(cells, None, sigma, (0, 1), 1, delta, omega, beta, gamma, u, P)
+    assert want[1][0] == want[0][u] != 1 and want[1][u] == 1
+    zh = z[0].cpu().numpy()
+    for s in range(2):
+        assert np.array_equal(zh[s, :u + 1], bytes_of(want[s], P, False)), s
+        assert (zh[s, u + 1:] == SENTINEL).all(), s                                    # the guard behind the column
+
+
+# ---- 3. representations ------------------------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def small(H):
+    """The (64, 4, 1) case in the default representation with its domain, sigma and model (m = 5, chunk 2), shared by the tests below (never modified)."""
+    c = Case(H, 64, 4, 1, "bn254_fq", seed=11)
+    u = usable_for(c.rows)
+    src = (0, 1, 2, 3, 4)
+    omega, delta = random_domain(c.P, 5, u, random.Random(3))
+    sigma = c.sigma(src, u, delta, omega)
+    betas, gammas = challenges(c.P, 77)
+    want = [PR.product(c.cells[b], None, sigma, src, 2, delta, omega, betas[b], gammas[b], u, c.P) for b in range(3)]
+    return dict(c=c, u=u, src=src, omega=omega, delta=delta, sigma=sigma, betas=betas, gammas=gammas, want=want)
+
+
+@pytest.mark.parametrize("repr_kw", [dict(), dict(montgomery=True), dict(columns=True, col_stride=1 << 15),
+                                     dict(columns=True, montgomery=True, col_stride=1 << 15), dict(columns=True, montgomery=True)],
+                         ids=["row-major", "row-major-montgomery", "planar-2^k", "planar-2^k-montgomery", "planar-packed-montgomery"])
+def test_representations(H, small, repr_kw):
+    s = small
+    c = Case(H, 64, 4, 1, "bn254_fq", seed=11, **repr_kw)
+    assert c.cells == s["c"].cells and c.rows * 32 <= (1 << 15)                        # the same witness, whatever the representation
+    assert c.advice_check(c.image) == [0, 0, 0]
+    pa = c.argument(s["src"], 2, s["delta"], s["omega"])                               # delta, omega, sigma, beta, gamma: the ctx's representation
+    z, st = c.run(pa, columns_tensor(s["sigma"], s["u"], c.P, c.chip.montgomery), s["betas"], s["gammas"], s["u"])
+    assert st == [0, 0, 0]
+    for b in range(3):
+        c.assert_columns(z[b], s["want"][b], b)                                        # Montgomery: the canonical value * 2^256 mod p
+
+
+# ---- 4. red cases: only circuit 1 of three is damaged ---------------------------------------------------------------------------------
+def test_red_cases(H, small):
+    from halo2_rsa_amd import _lib
+    s = small
+    c, u, P, src, want = s["c"], s["u"], s["c"].P, s["src"], s["want"]
+    betas, gammas, sigma = s["betas"], s["gammas"], s["sigma"]
+    pa = c.argument(src, 2, s["delta"], s["omega"])
+    sigma_dev = columns_tensor(sigma, u, P, False)
+    S = 3
+    sentinel = torch.full((S, u + 1, 32), SENTINEL, dtype=torch.uint8, device="cuda")
+
+    def product(betas=betas, gammas=gammas, image=None, status=None, set_major=False):
+        shape = (S, 3, u + 1, 32) if set_major else (3, S, u + 1, 32)
+        z = torch.full(shape, SENTINEL, dtype=torch.uint8, device="cuda")
+        st = torch.zeros(3, dtype=torch.uint8, device="cuda") if status is None else status
+        zz, stl = c.run(pa, sigma_dev, betas, gammas, u, image=image, out=(z.permute(1, 0, 2, 3) if set_major else z, st))
+        return zz, stl
+
+    def others_green(z, st):
+        assert st[0] == 0 and st[2] == 0
+        for b in (0, 2):
+            c.assert_columns(z[b], want[b], b)
+
+    z, st = product()                                                                  # the undamaged batch
+    assert st == [0, 0, 0]
+    others_green(z, st)
+    c.assert_columns(z[1], want[1])
+    good = z.clone()
+    # both accepted arrangements give the same columns: [element][set] above, [set][element] here
+    z2, st = product(set_major=True)
+    assert st == [0, 0, 0] and z2.stride(1) == 3 * (u + 1) * 32 and torch.equal(z2, good)
+    # a cell that is the source of a copy pair, changed in circuit 1
+    row, col = next((sr, sc) for (_, _, sr, sc) in c.pairs if sr not in PR.H2R_COPY_SRC)
+    host = c.image.cpu().numpy().copy().reshape(3, c.rows, 5, 32)
+    cell = host[1, row, col].view("<u8")
+    v = (int(cell[0]) | int(cell[1]) << 64 | int(cell[2]) << 128 | int(cell[3]) << 192) + 1
+    assert v < P
+    host[1, row, col] = bytes_of([v], P, False)[0]
+    damaged = torch.from_numpy(host.reshape(3, -1)).cuda()
+    cv = c.copy_violations(damaged)
+    assert cv[0] == 0 and cv[2] == 0 and cv[1] >= 1                                    # h2r_advice_check reports it: code 3, once per violated pair
+    z, st = product(image=damaged)
+    assert st == [0, _lib.H2R_E_ASSERTION, 0]
+    others_green(z, st)
+    cells1 = c.decode(damaged)[1]
+    assert cells1[row][col] == v
+    bad = PR.product(cells1, None, sigma, src, 2, s["delta"], s["omega"], betas[1], gammas[1], u, P)
+    assert bad[-1][u] != 1
+    c.assert_columns(z[1], bad)                                                        # written as computed
+    # a zero denominator in set 1: gamma = -(v + beta * sigma) of one of its cells
+    r0, c0 = 5, 2
+    g1 = -(c.cells[1][r0][src[c0]] + betas[1] * sigma[c0][r0]) % P
+    z, st = product(gammas=[gammas[0], g1, gammas[2]])
+    assert st == [0, _lib.H2R_E_ASSERTION, 0]
+    others_green(z, st)
+    first = PR.product(c.cells[1], None, sigma, src, 2, s["delta"], s["omega"], betas[1], g1, u, P)
+    assert first[0] is not None and first[1] is None and first[2] is None
+    c.assert_columns(z[1, :1], first[:1])                                              # set 0 is written
+    assert torch.equal(z[1, 1:], sentinel[1:])                                         # sets 1 and 2 are left untouched
+    # beta = p: not a canonical element
+    z, st = product(betas=[betas[0], P, betas[2]])
+    assert st == [0, _lib.H2R_E_SHAPE, 0] and torch.equal(z[1], sentinel)
+    others_green(z, st)
+    # a circuit whose status byte is nonzero on entry is skipped, and the byte is kept
+    z, st = product(status=torch.tensor([0, 7, 0], dtype=torch.uint8, device="cuda"))
+    assert st == [0, 7, 0] and torch.equal(z[1], sentinel)
+    others_green(z, st)
