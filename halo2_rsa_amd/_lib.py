@@ -97,6 +97,14 @@ class H2RPermutationConfig(ctypes.Structure):
                 ("column_src", ctypes.c_uint8 * H2R_PERM_MAX_COLUMNS), ("delta", ctypes.c_uint64 * 4), ("omega", ctypes.c_uint64 * 4)]
 
 
+H2R_NTT_INVERSE = 1
+
+
+class H2RNttConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("log_n_in", ctypes.c_uint32), ("log_n_out", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+                ("omega", ctypes.c_uint64 * 4), ("shift", ctypes.c_uint64 * 4)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -144,6 +152,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_lookup_hist_values", "h2r_lookup_hist_values_strided", "h2r_lookup_hist_verify", "h2r_lookup_hist_fresh_op", "h2r_lookup_workspace_bytes", "h2r_lookup_permuted_columns", "h2r_field_eval",
            "h2r_lookup_input_columns", "h2r_lookup_product_workspace_bytes", "h2r_lookup_product_columns",
            "h2r_permutation_sets", "h2r_permutation_product_workspace_bytes", "h2r_permutation_product_columns",
+           "h2r_ntt_workspace_bytes", "h2r_ntt_columns",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -153,6 +162,7 @@ H2R_ADVICE_DIRECT = 0x200
 KERNEL_CHAIN, KERNEL_TRACE, KERNEL_HIST, KERNEL_AUX, KERNEL_EMIT, KERNEL_STEP, KERNEL_LOOKUP, KERNEL_SHA256, KERNEL_CELLS = 0, 1, 2, 3, 4, 5, 6, 7, 8
 KERNEL_LOOKUP_INPUT, KERNEL_LOOKUP_PRODUCT_TILES, KERNEL_LOOKUP_PRODUCT_CARRY, KERNEL_LOOKUP_PRODUCT_SCAN = 9, 10, 11, 12
 KERNEL_PERM_PRODUCT_TILES, KERNEL_PERM_PRODUCT_CARRY, KERNEL_PERM_PRODUCT_SCAN = 13, 14, 15
+KERNEL_NTT_SETUP, KERNEL_NTT_PASS = 16, 17
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
 FRESH_OPS = ["add", "sub", "add_mod", "sub_mod", "is_zero", "is_equal_fresh", "is_less_than", "is_less_than_or_equal",
@@ -348,6 +358,10 @@ def lib():
     L.h2r_permutation_product_workspace_bytes.argtypes = [pperm, u32, u64]
     L.h2r_permutation_product_workspace_bytes.restype = u64
     L.h2r_permutation_product_columns.argtypes = [vp, pperm, vp, u64, u64, u32, u64, vp, u64, u64, vp, u64, vp, vp, u32, vp, u64, u64, vp, vp, vp]
+    pntt = ctypes.POINTER(H2RNttConfig)
+    L.h2r_ntt_workspace_bytes.argtypes = [pntt]
+    L.h2r_ntt_workspace_bytes.restype = u64
+    L.h2r_ntt_columns.argtypes = [vp, pntt, vp, u64, u64, vp, u64, u64, u32, u64, vp, vp]
     L.h2r_field_eval.argtypes = [vp, u32, pu64, pu64, pu64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]

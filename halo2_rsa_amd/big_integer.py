@@ -1230,6 +1230,84 @@ class PermutationArgument:
         return z, status
 
 
+class EvaluationDomain:
+    """halo2's poly::domain::EvaluationDomain on the device (h2r_ntt_columns; third-party behaviour restated in DESIGN.md section 2f):
+    the transforms between Lagrange, coefficient and extended (coset) form of columns of 2^k / 2^extended_k field elements.
+    omega_ext: a primitive 2^extended_k-th root of unity, zeta: the extended domain's coset shift (both integers in the chip's
+    representation); omega at k is omega_ext^(2^(extended_k - k)).  Columns are uint8 tensors [..., rows, 32] (up to two leading
+    dimensions: [batch, columns, rows, 32]) whose last two dimensions are contiguous, in the chip's representation."""
+
+    def __init__(self, chip: BigIntChip, k: int, extended_k: int, omega_ext: int, zeta: int):
+        if not 1 <= k <= extended_k:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain")
+        self.chip, self.k, self.extended_k, self.omega_ext, self.zeta = chip, int(k), int(extended_k), int(omega_ext), int(zeta)
+        self.one = self._field(6, 1) if chip.montgomery else 1
+        self.omega = self.omega_at(self.k)
+        self._keep = None
+
+    def _field(self, op: int, a: int, b: int = 0) -> int:
+        wa, wb, out = ((ctypes.c_uint64 * 4)(*[(int(v) >> (64 * i)) & (2 ** 64 - 1) for i in range(4)]) for v in (a, b, 0))
+        check(lib().h2r_field_eval(self.chip._ctx, op, wa, wb, out), "h2r_field_eval")
+        return sum(int(out[i]) << (64 * i) for i in range(4))
+
+    def omega_at(self, log_n: int) -> int:
+        """omega_ext^(2^(extended_k - log_n)): the generator of the 2^log_n domain, in the chip's representation."""
+        if not 0 < log_n <= self.extended_k:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.omega_at")
+        w = self._field(7, self.omega_ext) if self.chip.montgomery else self.omega_ext
+        for _ in range(self.extended_k - log_n):
+            w = self._field(2, w, w)
+        return self._field(6, w) if self.chip.montgomery else w
+
+    def ntt(self, cols: torch.Tensor, log_n_out: int, inverse: bool = False, shift: Optional[int] = None, out: Optional[torch.Tensor] = None):
+        """The raw transform: forward out[j] = sum_i cols[i] * (shift * omega^j)^i onto 2^log_n_out points (the input zero-padded), or the
+        inverse of it (log_n_out = the input's size).  shift: an integer in the chip's representation (None: 1, no coset).
+        out: a tensor of the input's leading shape with 2^log_n_out rows to write into (it must not overlap the input)."""
+        rows = cols.shape[-2]
+        if cols.dtype != torch.uint8 or cols.dim() < 2 or cols.dim() > 4 or cols.shape[-1] != 32 or rows & (rows - 1) or rows == 0:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.ntt")
+        assert cols.stride(-1) == 1 and cols.stride(-2) == 32
+        cfg = _lib.H2RNttConfig()
+        cfg.struct_size = ctypes.sizeof(cfg)
+        cfg.log_n_in, cfg.log_n_out, cfg.flags = rows.bit_length() - 1, log_n_out, _lib.H2R_NTT_INVERSE if inverse else 0
+        omega, shift = self.omega_at(log_n_out), self.one if shift is None else int(shift)
+        for i in range(4):
+            cfg.omega[i] = (omega >> (64 * i)) & (2 ** 64 - 1)
+            cfg.shift[i] = (shift >> (64 * i)) & (2 ** 64 - 1)
+        lead = tuple(cols.shape[:-2])
+        if out is None:
+            out = torch.empty(lead + (1 << log_n_out, 32), dtype=torch.uint8, device=cols.device)
+        assert tuple(out.shape) == lead + (1 << log_n_out, 32) and out.stride(-1) == 1 and out.stride(-2) == 32
+
+        def strides(t):   # (elements, element stride, columns, column stride) of [..., rows, 32]
+            col = t.shape[-2] * 32
+            if t.dim() == 2:
+                return 1, col, 1, col
+            if t.dim() == 3:
+                return 1, max(col, t.shape[0] * t.stride(0)), t.shape[0], t.stride(0)
+            return t.shape[0], t.stride(0), t.shape[1], t.stride(1)
+
+        batch, ies, ncols, ics = strides(cols)
+        _, oes, _, ocs = strides(out)
+        ws = torch.empty(max(int(lib().h2r_ntt_workspace_bytes(ctypes.byref(cfg))), 16), dtype=torch.uint8, device=cols.device)
+        check(lib().h2r_ntt_columns(self.chip._ctx, ctypes.byref(cfg), cols.data_ptr(), ies, ics, out.data_ptr(), oes, ocs, ncols, batch,
+                                    ws.data_ptr(), self.chip._stream()), "h2r_ntt_columns")
+        self._keep = (ws, cols, out)   # alive until the stream has run the kernels
+        return out
+
+    def lagrange_to_coeff(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """2^k evaluations over the domain -> the 2^k coefficients."""
+        return self.ntt(cols, self.k, inverse=True, out=out)
+
+    def coeff_to_extended(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """2^k coefficients -> the 2^extended_k evaluations over the coset zeta * <omega_ext>."""
+        return self.ntt(cols, self.extended_k, shift=self.zeta, out=out)
+
+    def extended_to_coeff(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """2^extended_k evaluations over the coset -> the 2^extended_k coefficients (truncation stays the caller's)."""
+        return self.ntt(cols, self.extended_k, inverse=True, shift=self.zeta, out=out)
+
+
 @dataclass
 class FreshResult:
     value: Optional[AssignedInteger]

@@ -25,6 +25,7 @@
 #include "h2r_lookup.hpp"
 #include "h2r_lookup_product.hpp"
 #include "h2r_permutation_product.hpp"
+#include "h2r_ntt.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4091,6 +4092,136 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
         for (u32 phase = 0; phase < 3; ++phase) {
             ProfScope ps(H2R_KERNEL_PERM_PRODUCT_TILES + phase, st, true);
             HIP_TRY(launch_perm_product(phase, pa, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
+        }
+    }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the evaluation domain's transforms (h2r_ntt.hpp, h2r_tu_ntt.hip) -------------------------------------------------------------------
+namespace {
+static_assert(H2R_KERNEL_NTT_PASS == H2R_KERNEL_NTT_SETUP + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_NTT_PASS + 1, "h2r.h: the launch classes");
+// what h2r_ntt_workspace_bytes answers 0 for: the parts of a configuration that need no ctx (omega and shift are compared with the ctx's p)
+int32_t ntt_cfg_status(const h2r_ntt_config *cfg) {
+    if (cfg->struct_size != sizeof(h2r_ntt_config) || (cfg->flags & ~H2R_NTT_INVERSE)) return H2R_E_UNSUPPORTED;
+    if (cfg->log_n_out == 0 || cfg->log_n_out > NTT_MAX_LOG || cfg->log_n_in > cfg->log_n_out) return H2R_E_SHAPE;
+    if ((cfg->flags & H2R_NTT_INVERSE) && cfg->log_n_in != cfg->log_n_out) return H2R_E_SHAPE;
+    if (!(cfg->shift[0] | cfg->shift[1] | cfg->shift[2] | cfg->shift[3])) return H2R_E_SHAPE;
+    return H2R_OK;
+}
+// num_cols x batch columns of `col` bytes: strides that hold a column, and columns that do not overlap each other
+bool ntt_columns_disjoint(u64 col, u64 elem_stride, u64 col_stride, u32 num_cols, u64 batch) {
+    if (elem_stride < col || col_stride < col) return false;
+    const u128 elem_major = (u128)(num_cols - 1) * col_stride + col, col_major = batch ? (u128)(batch - 1) * elem_stride + col : 0;
+    return elem_stride >= elem_major || col_stride >= col_major;
+}
+// bytes from the first column's first byte to the last column's last one
+u128 ntt_extent(u64 col, u64 elem_stride, u64 col_stride, u32 num_cols, u64 batch) {
+    return batch ? (u128)(batch - 1) * elem_stride + (u128)(num_cols - 1) * col_stride + col : 0;
+}
+}  // namespace
+
+uint64_t h2r_ntt_workspace_bytes(const h2r_ntt_config *cfg) try {
+    return cfg && ntt_cfg_status(cfg) == H2R_OK ? NTT_WORKSPACE_BYTES : 0;
+} H2R_CATCH_ZERO
+
+int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const void *in, uint64_t in_elem_stride, uint64_t in_col_stride,
+                        void *out, uint64_t out_elem_stride, uint64_t out_col_stride, uint32_t num_cols, uint64_t batch, void *workspace,
+                        h2r_stream_t stream) try {
+    if (!ctx || !cfg || !in || !out || !workspace) return H2R_E_NULL;
+    if (const int32_t rc = ntt_cfg_status(cfg)) return rc;
+    if (num_cols == 0) return H2R_E_SHAPE;
+    const FieldConsts &f = ctx->fc;
+    if (ge_p(cfg->omega, f.p) || ge_p(cfg->shift, f.p)) return H2R_E_SHAPE;
+    const bool mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0, inverse = (cfg->flags & H2R_NTT_INVERSE) != 0;
+    const u32 log_n = cfg->log_n_out, log_m = cfg->log_n_in;
+    const Fe one = [&] { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = f.one[k]; return r; }();
+    Fe omega, shift;   // Montgomery form from here on
+    for (int k = 0; k < 4; ++k) { omega.v[k] = cfg->omega[k]; shift.v[k] = cfg->shift[k]; }
+    if (!mont) { omega = fe_to_mont(omega, f); shift = fe_to_mont(shift, f); }
+    {   // a primitive 2^log_n-th root of unity: omega^(n / 2) = -1
+        Fe x = omega;
+        for (u32 b = 1; b < log_n; ++b) x = fe_mont_mul(x, x, f);
+        if (!fe_is_zero(fe_add(x, one, f.p))) return H2R_E_SHAPE;
+    }
+    auto misaligned = [](const void *p, u64 s0, u64 s1) { return ((reinterpret_cast<u64>(p) | s0 | s1) & 15) != 0; };
+    if (misaligned(in, in_elem_stride, in_col_stride) || misaligned(out, out_elem_stride, out_col_stride)) return H2R_E_SHAPE;
+    const u64 in_col = 32ull << log_m, out_col = 32ull << log_n;
+    if (!ntt_columns_disjoint(in_col, in_elem_stride, in_col_stride, num_cols, batch) ||
+        !ntt_columns_disjoint(out_col, out_elem_stride, out_col_stride, num_cols, batch)) return H2R_E_SHAPE;
+    {   // the passes after the first work in place in `out` while other workgroups still read `in`: the two ranges are disjoint
+        const u128 i0 = reinterpret_cast<u64>(in), o0 = reinterpret_cast<u64>(out);
+        const u128 i1 = i0 + ntt_extent(in_col, in_elem_stride, in_col_stride, num_cols, batch);
+        const u128 o1 = o0 + ntt_extent(out_col, out_elem_stride, out_col_stride, num_cols, batch);
+        if (i0 < o1 && o0 < i1) return H2R_E_SHAPE;
+    }
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+
+    const NttPlan pl = ntt_plan(log_n);
+    auto inv = [&](const Fe &x) { return fe_to_mont(fe_inv(fe_from_mont(x, f), f), f); };   // x is x * R: back to the integer, invert, forth
+    auto pow2k = [&](Fe x, u32 k) { for (u32 b = 0; b < k; ++b) x = fe_mont_mul(x, x, f); return x; };
+    const bool coset = !fe_eq(shift, one);
+    const Fe w = inverse ? inv(omega) : omega, g = inverse ? inv(shift) : shift;
+    NttSetupArgs sa;
+    std::memset(static_cast<void *>(&sa), 0, sizeof sa);
+    auto table = [&](u32 t, Fe base, const Fe &first, u64 count) {
+        sa.first[t] = first;
+        sa.count[t] = (u32)std::min<u64>(NTT_SPLIT, (count + 3) & ~3ull);
+        for (u32 b = 0; b < NTT_SPLIT_LOG; ++b) { sa.pow2[t][b] = base; base = fe_mont_mul(base, base, f); }
+    };
+    table(0, pow2k(w, log_n - pl.smax), one, 1ull << (pl.smax - 1));
+    if (pl.passes > 1) {
+        table(1, w, one, 1ull << log_n);
+        if (log_n > NTT_SPLIT_LOG) table(2, pow2k(w, NTT_SPLIT_LOG), one, 1ull << (log_n - NTT_SPLIT_LOG));
+    }
+    NttArgs na;
+    std::memset(static_cast<void *>(&na), 0, sizeof na);
+    // the first load and the last store: a canonical ctx converts there (x * R^2 -> the Montgomery form, x * 1 -> the integer), within the
+    // product that applies g^i (forward, on the load) or n^-1 * g^-i (inverse, on the store) where there is one
+    const Fe r2 = [&] { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = f.r2[k]; return r; }();
+    na.load_mode = mont ? NTT_F_NONE : NTT_F_CONST; na.load_const = r2;
+    na.store_mode = mont ? NTT_F_NONE : NTT_F_CONST; na.store_const = fe_small(1);
+    if (inverse) {
+        Fe ninv = inv(fe_to_mont(fe_small(1ull << log_n), f));
+        if (!mont) ninv = fe_from_mont(ninv, f);
+        na.store_mode = coset ? NTT_F_TABLE : NTT_F_CONST; na.store_const = ninv;
+        if (coset) {
+            table(3, g, ninv, 1ull << log_n);
+            if (log_n > NTT_SPLIT_LOG) table(4, pow2k(g, NTT_SPLIT_LOG), one, 1ull << (log_n - NTT_SPLIT_LOG));
+        }
+    } else if (coset) {
+        na.load_mode = NTT_F_TABLE;
+        table(3, g, mont ? one : fe_to_mont(one, f), 1ull << log_m);
+        if (log_m > NTT_SPLIT_LOG) table(4, pow2k(g, NTT_SPLIT_LOG), one, 1ull << (log_m - NTT_SPLIT_LOG));
+    }
+    sa.f = f; na.f = f;
+    na.log_n = log_n; na.log_m = log_m; na.passes = pl.passes; na.smax = pl.smax;
+    for (u32 q = 0; q < NTT_MAX_PASSES; ++q) na.s[q] = pl.s[q];
+    na.in_elem_stride = in_elem_stride; na.in_col_stride = in_col_stride; na.out_elem_stride = out_elem_stride; na.out_col_stride = out_col_stride;
+    // launches below the 2^32 global size and the 65,535 of a grid's y and z: slices of columns, then of elements
+    const u64 max_blocks = ((1ull << 32) - 1) / 256;
+    u64 tiles = 0;
+    for (u32 q = 0; q < pl.passes; ++q) tiles = std::max<u64>(tiles, ntt_pass_tiles(log_n, pl.s[q]));
+    const u64 cols_per = std::min<u64>({num_cols, 65535, max_blocks / tiles});
+    const u64 elems_per = std::min<u64>({batch, 65535, max_blocks / (tiles * cols_per)});
+    if (!cols_per || !elems_per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    sa.tab = reinterpret_cast<Fe *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    na.tab = sa.tab;
+    {
+        ProfScope ps(H2R_KERNEL_NTT_SETUP, st, true);
+        HIP_TRY(launch_ntt_setup(sa, st, ps.a, ps.on ? ps.b : nullptr));
+    }
+    for (u64 e0 = 0; e0 < batch; e0 += elems_per) {
+        for (u64 c0 = 0; c0 < num_cols; c0 += cols_per) {
+            na.in = static_cast<const u8 *>(in) + e0 * in_elem_stride + c0 * in_col_stride;
+            na.out = static_cast<u8 *>(out) + e0 * out_elem_stride + c0 * out_col_stride;
+            for (u32 q = 0; q < pl.passes; ++q) {
+                na.pass = q;
+                ProfScope ps(H2R_KERNEL_NTT_PASS, st, true);
+                HIP_TRY(launch_ntt_pass(na, (u32)std::min<u64>(cols_per, num_cols - c0), (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
+            }
         }
     }
     return H2R_OK;

@@ -9,6 +9,7 @@
 //   h2r_tu_cells.hip   cells_kernel<LW, ABL, MONT, NWV> (the advice image directly from the operands)
 //   h2r_tu_lookup_product.hip   the lookup argument's input columns and grand product (h2r_lookup_product.hpp)
 //   h2r_tu_permutation_product.hip   the permutation argument's grand product (h2r_permutation_product.hpp)
+//   h2r_tu_ntt.hip     the evaluation domain's transforms (h2r_ntt.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -112,5 +113,10 @@ hipError_t launch_lookup_product(u32 phase, const LookupProductArgs &a, u32 num_
 // h2r_tu_permutation_product.hip (argument struct: h2r_permutation_product.hpp).  The same three phases: per tile of a set, per element, per tile of a set.
 struct PermProductArgs;
 hipError_t launch_perm_product(u32 phase, const PermProductArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_ntt.hip (argument structs: h2r_ntt.hpp).  The twiddle tables of one call, then one pass (a.pass) over num_cols x num_elems columns.
+struct NttSetupArgs;
+struct NttArgs;
+hipError_t launch_ntt_setup(const NttSetupArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_ntt_pass(const NttArgs &a, u32 num_cols, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

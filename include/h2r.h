@@ -873,6 +873,41 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
                                         uint64_t extra_col_stride, const void *sigma, uint64_t sigma_col_stride, const uint64_t *beta,
                                         const uint64_t *gamma, uint32_t usable_rows, void *z_out, uint64_t z_elem_stride,
                                         uint64_t z_col_stride, uint8_t *status, void *workspace, h2r_stream_t stream);
+/* ---- the evaluation domain: transforms between Lagrange, coefficient and coset (extended) form ----
+ * THIRD-PARTY behaviour (halo2 poly::domain::EvaluationDomain, not in the reference tree), restated in DESIGN.md section 2f; parity is pinned
+ * against a Python restatement (tests/ntt_ref.py, tests/test_ntt_gpu.py), not against upstream.  A plain number-theoretic transform with a
+ * caller-supplied root and coset shift; with n = 2^log_n_out, m = 2^log_n_in, all arithmetic mod the ctx's p, natural index order on both sides:
+ *    forward:                 out[j] = sum_{i < m} in[i] * (g * omega^j)^i,  j < n   (the coefficients `in`, zero-padded to n, on the coset g <omega>)
+ *    inverse (H2R_NTT_INVERSE): out[i] = g^-i * n^-1 * sum_{j < n} in[j] * omega^(-i * j)   (log_n_in == log_n_out; the exact inverse of forward)
+ * Upstream's three functions are special cases: lagrange_to_coeff = inverse at k with g = 1, coeff_to_extended = forward from k to the extended
+ * k with g = zeta, extended_to_coeff = inverse at the extended k with g = zeta (truncation stays the caller's).
+ *  - Column c of element e lies at base + e * elem_stride + c * col_stride: 2^log_n_in (in) / 2^log_n_out (out) elements of 32 bytes in the
+ *    ctx's representation (for these planar vectors only H2R_ADVICE_MONTGOMERY matters; H2R_ADVICE_COLUMNS and its col_stride do not apply).
+ *    A canonical ctx converts on the first load and the last store, a Montgomery ctx converts nothing.  There is no status array: nothing
+ *    depends on the data (inputs >= p are the caller's error, as elsewhere).  The call enqueues on `stream` and never synchronises;
+ *    ceil(log_n_out / 10) launches over the columns after one small launch that fills the twiddle tables in the workspace; launches are
+ *    sliced internally below the 2^32 global size.  `out` is also the scratch of the passes: its contents are undefined until the last one.
+ *    workspace: h2r_ntt_workspace_bytes(cfg) bytes on the device, private to the call until the stream has run it (a host function; no
+ *    device and no ctx needed; 0 for a config the call would refuse whatever the ctx: struct_size, flags, log_n_in / log_n_out, shift = 0).
+ *  - H2R_E_NULL for a NULL ctx, cfg, in, out or workspace; H2R_E_UNSUPPORTED for another struct_size, unknown flag bits or a host-only ctx
+ *    (that one after every other check); H2R_E_SHAPE for log_n_out = 0 or > 24, log_n_in > log_n_out, inverse with log_n_in != log_n_out,
+ *    num_cols = 0, omega or shift >= p, shift = 0, omega^(2^(log_n_out - 1)) != -1 (what "primitive root" means here), a pointer or stride
+ *    that is not 16-byte aligned, a stride smaller than its column, columns that overlap each other (either elem_stride covers an element's
+ *    num_cols columns, >= (num_cols - 1) * col_stride + column, or col_stride covers every element's column, >= (batch - 1) * elem_stride +
+ *    column), and `in` and `out` ranges that overlap at all.  batch = 0 returns H2R_OK with no launch. */
+#define H2R_NTT_INVERSE 1u
+typedef struct h2r_ntt_config {
+    uint32_t struct_size;   /* sizeof; anything else: H2R_E_UNSUPPORTED */
+    uint32_t log_n_in;      /* the input column has 2^log_n_in elements */
+    uint32_t log_n_out;     /* the output column has 2^log_n_out elements, log_n_in <= log_n_out <= 24 */
+    uint32_t flags;         /* 0 = forward, H2R_NTT_INVERSE */
+    uint64_t omega[4];      /* a primitive 2^log_n_out-th root of unity, ctx's representation */
+    uint64_t shift[4];      /* the coset shift g != 0, ctx's representation; 1 = no coset */
+} h2r_ntt_config;
+uint64_t h2r_ntt_workspace_bytes(const h2r_ntt_config *cfg);
+int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const void *in, uint64_t in_elem_stride, uint64_t in_col_stride,
+                        void *out, uint64_t out_elem_stride, uint64_t out_col_stride, uint32_t num_cols, uint64_t batch, void *workspace,
+                        h2r_stream_t stream);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1167,7 +1202,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_LOOKUP_INPUT = 9 /* lookup_input_kernel: the input columns A */,
        H2R_KERNEL_LOOKUP_PRODUCT_TILES = 10, H2R_KERNEL_LOOKUP_PRODUCT_CARRY = 11, H2R_KERNEL_LOOKUP_PRODUCT_SCAN = 12 /* the grand product's three launches */,
        H2R_KERNEL_PERM_PRODUCT_TILES = 13, H2R_KERNEL_PERM_PRODUCT_CARRY = 14, H2R_KERNEL_PERM_PRODUCT_SCAN = 15 /* the permutation argument's grand product, likewise */,
-       H2R_KERNEL_COUNT = 16 };
+       H2R_KERNEL_NTT_SETUP = 16 /* ntt_setup_kernel: the twiddle tables of one call */, H2R_KERNEL_NTT_PASS = 17 /* ntt_pass_kernel: one launch per pass */,
+       H2R_KERNEL_COUNT = 18 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 

@@ -1,0 +1,320 @@
+"""h2r_ntt_columns / EvaluationDomain: the evaluation domain's transforms (halo2 poly::domain::EvaluationDomain [3P, restated in DESIGN.md
+section 2f]) against the plain model of tests/ntt_ref.py, byte for byte.
+
+Every output buffer is pre-filled with a sentinel and has guard rows behind every column, which must come back unchanged.  The kernel works
+in tiles of 2^T elements (T = NTT_TILE_LOG, read from csrc/h2r_ntt.hpp) and takes ceil(log n / T) passes; sizes are chosen against T: under
+one tile, one tile, just above it (two passes), 2T (two full passes) and 2T + 1 (three passes).  Up to 2^(T+1) points the whole output is
+compared with the model; at 2^(2T) and 2^(2T+1), where a Python transform has too many terms, with Horner at sampled points, with the
+closed form of geometric inputs, and with inputs whose inverse transform is known (two monomials)."""
+import os
+import random
+import re
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+import ntt_ref as NR
+from pyref import FIELD_MODULI
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+R256 = 1 << 256
+SENTINEL = 0xAB
+GUARD = 3                                # sentinel rows behind every output column
+with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_ntt.hpp")) as _f:
+    T = int(re.search(r"constexpr u32 NTT_TILE_LOG = (\d+);", _f.read()).group(1))
+
+
+@pytest.fixture(scope="module")
+def H():
+    if not torch.cuda.is_available():
+        pytest.skip("needs a GPU")
+    import halo2_rsa_amd as H_
+    return H_
+
+
+def to_bytes(vals, P, montgomery):
+    """canonical integers -> uint8 [n, 32] in the ctx's representation."""
+    if montgomery:
+        vals = [v * R256 % P for v in vals]
+    return np.frombuffer(b"".join(v.to_bytes(32, "little") for v in vals), dtype=np.uint8).reshape(len(vals), 32)
+
+
+def to_ints(host, P, montgomery):
+    """uint8 [n, 32] in the ctx's representation -> canonical integers (every element must be below P)."""
+    raw = np.ascontiguousarray(host).tobytes()
+    vals = [int.from_bytes(raw[i:i + 32], "little") for i in range(0, len(raw), 32)]
+    assert all(v < P for v in vals)
+    if montgomery:
+        rinv = pow(R256, -1, P)
+        vals = [v * rinv % P for v in vals]
+    return vals
+
+
+class Dom:
+    """A chip over `field`, its EvaluationDomain of 2^k_max points, and the model's view of both."""
+
+    def __init__(self, H, field, montgomery, k_max):
+        self.P, self.mont, self.k_max = FIELD_MODULI[field], montgomery, k_max
+        self.chip = H.BigIntChip(64, 256, field=field, montgomery=montgomery)
+        self.omega_max = NR.omega_of(self.P, k_max)
+        self.zeta = NR.cube_root_of_unity(self.P) if self.P % 3 == 1 else 1
+        self.dom = H.EvaluationDomain(self.chip, min(k_max, max(1, k_max - 2)), k_max, self.rep(self.omega_max), self.rep(self.zeta))
+
+    def rep(self, v):
+        return v * R256 % self.P if self.mont else v
+
+    def omega(self, k):
+        return pow(self.omega_max, 1 << (self.k_max - k), self.P)
+
+    def guarded(self, batch, cols, n, col_major=False):
+        """A sentinel-filled output of [batch, cols, n, 32] with GUARD rows behind every column: (the whole buffer, the view to write into)."""
+        full = torch.full((cols, batch, n + GUARD, 32) if col_major else (batch, cols, n + GUARD, 32), SENTINEL, dtype=torch.uint8, device="cuda")
+        view = full.permute(1, 0, 2, 3) if col_major else full
+        return view, view[:, :, :n]
+
+    def run(self, x, log_out, inverse=False, shift=1, col_major_in=False, col_major_out=False, pad_in=2):
+        """x: [batch][cols][m] canonical integers.  Returns the device's output as [batch][cols][n] canonical integers after checking the guards."""
+        B, C, m, n = len(x), len(x[0]), len(x[0][0]), 1 << log_out
+        host = np.full((C, B, m + pad_in, 32) if col_major_in else (B, C, m + pad_in, 32), 0xEE, dtype=np.uint8)
+        for b in range(B):
+            for c in range(C):
+                (host[c, b] if col_major_in else host[b, c])[:m] = to_bytes(x[b][c], self.P, self.mont)
+        dev = torch.from_numpy(host).cuda()
+        src = (dev.permute(1, 0, 2, 3) if col_major_in else dev)[:, :, :m]
+        full, out = self.guarded(B, C, n, col_major_out)
+        got = self.dom.ntt(src, log_out, inverse=inverse, shift=self.rep(shift), out=out)
+        torch.cuda.synchronize()
+        assert got.data_ptr() == out.data_ptr()
+        fh = full.cpu().numpy()
+        assert (fh[:, :, n:] == SENTINEL).all(), "guard rows behind a column were written"
+        assert np.array_equal(dev.cpu().numpy(), host), "the input was written"
+        return [[to_ints(fh[b, c, :n], self.P, self.mont) for c in range(C)] for b in range(B)]
+
+
+def shifts(d, rng):
+    return [1, d.zeta, rng.randrange(2, d.P)]
+
+
+# ---- 1. dense random inputs against the whole model ------------------------------------------------------------------------------------
+SIZES = sorted({1, 2, 6, T - 1, T, T + 1})
+PADDED = [(1, T + 1), (T, T + 1), (T - 1, T)]        # fewer coefficients than points
+
+
+@pytest.mark.parametrize("montgomery", [False, True], ids=["canonical", "montgomery"])
+@pytest.mark.parametrize("field", NR.FIELDS_WITH_DOMAINS)
+def test_dense_against_the_model(H, field, montgomery):
+    d = Dom(H, field, montgomery, T + 1)
+    P = d.P
+    rng = random.Random(field + str(montgomery))
+    for k in SIZES:
+        w = d.omega(k)
+        x = [[[rng.randrange(P) for _ in range(1 << k)] for _ in range(2)]]
+        x[0][1][0], x[0][1][-1] = P - 1, 0
+        for g in shifts(d, rng):
+            assert d.run(x, k, shift=g)[0] == [NR.forward(c, k, w, g, P) for c in x[0]], ("forward", k, g)
+            assert d.run(x, k, inverse=True, shift=g)[0] == [NR.inverse(c, k, w, g, P) for c in x[0]], ("inverse", k, g)
+    for (k_in, k_out) in PADDED:
+        w = d.omega(k_out)
+        x = [[[rng.randrange(P) for _ in range(1 << k_in)] for _ in range(2)]]
+        for g in shifts(d, rng):
+            assert d.run(x, k_out, shift=g)[0] == [NR.forward(c, k_out, w, g, P) for c in x[0]], ("forward", k_in, k_out, g)
+
+
+@pytest.mark.parametrize("montgomery", [False, True], ids=["canonical", "montgomery"])
+def test_three_elements_two_columns_in_both_stride_orders(H, montgomery):
+    d = Dom(H, "pasta_fq", montgomery, T + 1)
+    P = d.P
+    rng = random.Random(5 + montgomery)
+    for (k_in, k_out, inverse) in [(6, 6, False), (6, 6, True), (T - 1, T + 1, False), (T + 1, T + 1, True)]:
+        w, g = d.omega(k_out), rng.randrange(2, P)
+        x = [[[rng.randrange(P) for _ in range(1 << k_in)] for _ in range(2)] for _ in range(3)]
+        want = [[(NR.inverse if inverse else NR.forward)(c, k_out, w, g, P) for c in e] for e in x]
+        for (cm_in, cm_out) in [(False, False), (True, True), (False, True), (True, False)]:
+            assert d.run(x, k_out, inverse=inverse, shift=g, col_major_in=cm_in, col_major_out=cm_out, pad_in=4) == want, (k_in, k_out, inverse, cm_in, cm_out)
+
+
+def test_bn256_fq_has_the_domain_of_two_points(H):
+    for montgomery in (False, True):
+        d = Dom(H, "bn254_fq", montgomery, 1)
+        P = d.P
+        assert d.omega_max == P - 1
+        rng = random.Random(9)
+        x = [[[rng.randrange(P), rng.randrange(P)], [P - 1, 1]]]
+        for g in (1, rng.randrange(2, P)):
+            assert d.run(x, 1, shift=g)[0] == [[(a + g * b) % P, (a - g * b) % P] for a, b in x[0]]
+            assert d.run(x, 1, inverse=True, shift=g)[0] == [NR.inverse(c, 1, P - 1, g, P) for c in x[0]]
+        assert d.run([[[5]]], 1, shift=3)[0] == [[5, 5]]                                    # one coefficient: a constant polynomial
+
+
+# ---- 2. two full passes and three passes ----------------------------------------------------------------------------------------------
+def sample_indices(n, rng):
+    """Every index of the first and of the last tile, and 4,096 random ones."""
+    return sorted(set(range(1 << T)) | set(range(n - (1 << T), n)) | {rng.randrange(n) for _ in range(4096)})
+
+
+def rows_of(out, js):
+    """The rows js of a device column [n, 32] as host bytes."""
+    return out[torch.tensor(js, device=out.device)].cpu().numpy()
+
+
+BIG = [(2 * T, False), (2 * T + 1, True)]
+
+
+@pytest.mark.parametrize("k_out,montgomery", BIG, ids=["2T-canonical", "2T+1-montgomery"])
+def test_forward_of_one_tile_of_coefficients_onto_a_large_coset(H, k_out, montgomery):
+    """(T -> 2T) and (T -> 2T + 1): zero padding and every pass; the outputs are the polynomial's values at g * omega^j (Horner)."""
+    d = Dom(H, "bn254_fr", montgomery, k_out)
+    P, n = d.P, 1 << k_out
+    rng = random.Random(k_out)
+    coeffs = [rng.randrange(P) for _ in range(1 << T)]
+    g, w = rng.randrange(2, P), d.omega(k_out)
+    src = torch.from_numpy(to_bytes(coeffs, P, montgomery)).cuda().reshape(1, 1, 1 << T, 32)
+    full, out = d.guarded(1, 1, n)
+    d.dom.ntt(src, k_out, shift=d.rep(g), out=out)
+    torch.cuda.synchronize()
+    assert (full[0, 0, n:] == SENTINEL).all()
+    js = sample_indices(n, rng)
+    want = [NR.horner(coeffs, g * pow(w, j, P) % P, P) for j in js]
+    assert np.array_equal(rows_of(out[0, 0], js), to_bytes(want, P, montgomery))
+
+
+@pytest.fixture(scope="module")
+def geometric(H):
+    """in[i] = a^i + b^i at 2^(2T) points (canonical ctx, bn256 Fr), on the device; shared by the tests below, never modified."""
+    d = Dom(H, "bn254_fr", False, 2 * T)
+    P, n = d.P, 1 << (2 * T)
+    rng = random.Random(77)
+    a, b = rng.randrange(2, P), rng.randrange(2, P)
+    vals, pa, pb = [], 1, 1
+    for _ in range(n):
+        vals.append((pa + pb) % P)
+        pa, pb = pa * a % P, pb * b % P
+    return dict(d=d, a=a, b=b, x=torch.from_numpy(to_bytes(vals, P, False)).cuda().reshape(1, 1, n, 32))
+
+
+def test_forward_at_two_full_passes_has_the_closed_form(H, geometric):
+    """2T -> 2T: out[j] = ((a g)^n - 1) / (a g omega^j - 1) + the same in b."""
+    d, k = geometric["d"], 2 * T
+    P, n = d.P, 1 << k
+    rng = random.Random(78)
+    g, w = rng.randrange(2, P), d.omega(k)
+    full, out = d.guarded(1, 1, n)
+    d.dom.ntt(geometric["x"], k, shift=g, out=out)
+    torch.cuda.synchronize()
+    assert (full[0, 0, n:] == SENTINEL).all()
+    js = sample_indices(n, rng)
+    want = NR.geometric_forward([geometric["a"], geometric["b"]], js, k, w, g, P)
+    assert np.array_equal(rows_of(out[0, 0], js), to_bytes(want, P, False))
+    # ... and the device's inverse of that output is the input again, byte for byte
+    full2, back = d.guarded(1, 1, n)
+    d.dom.ntt(out, k, inverse=True, shift=g, out=back)
+    torch.cuda.synchronize()
+    assert torch.equal(back, geometric["x"]) and (full2[0, 0, n:] == SENTINEL).all()
+
+
+def test_inverse_of_forward_is_the_identity_at_two_full_passes(H, geometric):
+    """Dense random x at 2^(2T) points: inverse(forward(x)) == x on the device's own bytes (forward is pinned by the closed form above)."""
+    d, k = geometric["d"], 2 * T
+    n = 1 << k
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    x = torch.randint(0, 256, (1, 2, n, 32), dtype=torch.uint8, generator=gen)
+    x[:, :, :, 31] &= 0x0F                                                                 # below 2^252 < p
+    x = x.cuda()
+    g = random.Random(79).randrange(2, d.P)
+    _, mid = d.guarded(1, 2, n)
+    full, back = d.guarded(1, 2, n)
+    d.dom.ntt(x, k, shift=g, out=mid)
+    assert not torch.equal(mid, x)
+    d.dom.ntt(mid, k, inverse=True, shift=g, out=back)
+    torch.cuda.synchronize()
+    assert torch.equal(back, x) and (full[0, :, n:] == SENTINEL).all()
+
+
+@pytest.mark.parametrize("k,montgomery", BIG, ids=["2T-canonical", "2T+1-montgomery"])
+def test_inverse_of_two_monomials(H, k, montgomery):
+    """in[j] = c1 (g omega^j)^i1 + c2 (g omega^j)^i2 are the values of c1 X^i1 + c2 X^i2 on the coset: the inverse is c1 at i1, c2 at i2, 0 elsewhere."""
+    d = Dom(H, "pasta_fp", montgomery, k)
+    P, n = d.P, 1 << k
+    rng = random.Random(k + 1)
+    g, w = rng.randrange(2, P), d.omega(k)
+    i1, i2 = rng.randrange(1, 1 << T), n - 1
+    c1, c2 = rng.randrange(1, P), rng.randrange(1, P)
+    t1, t2, s1, s2 = c1 * pow(g, i1, P) % P, c2 * pow(g, i2, P) % P, pow(w, i1, P), pow(w, i2, P)
+    vals = []
+    for _ in range(n):
+        vals.append((t1 + t2) % P)
+        t1, t2 = t1 * s1 % P, t2 * s2 % P
+    src = torch.from_numpy(to_bytes(vals, P, montgomery)).cuda().reshape(1, 1, n, 32)
+    full, out = d.guarded(1, 1, n)
+    d.dom.ntt(src, k, inverse=True, shift=d.rep(g), out=out)
+    torch.cuda.synchronize()
+    want = torch.zeros((n + GUARD, 32), dtype=torch.uint8)
+    want[n:] = SENTINEL
+    want[i1] = torch.from_numpy(to_bytes([c1], P, montgomery)[0].copy())
+    want[i2] = torch.from_numpy(to_bytes([c2], P, montgomery)[0].copy())
+    assert torch.equal(full[0, 0], want.cuda())
+
+
+# ---- 3. halo2's three functions ---------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("montgomery", [False, True], ids=["canonical", "montgomery"])
+def test_extended_round_trip(H, montgomery):
+    """coeff_to_extended then extended_to_coeff returns the coefficients, zero-padded to the extended domain."""
+    field = "pasta_fq"
+    P = FIELD_MODULI[field]
+    chip = H.BigIntChip(64, 256, field=field, montgomery=montgomery)
+    k, ek = T - 1, T + 1
+    rep = (lambda v: v * R256 % P) if montgomery else (lambda v: v)
+    w_ext, zeta = NR.omega_of(P, ek), NR.cube_root_of_unity(P)
+    dom = H.EvaluationDomain(chip, k, ek, rep(w_ext), rep(zeta))
+    assert dom.omega == rep(NR.omega_of(P, k))
+    rng = random.Random(3)
+    coeffs = [[rng.randrange(P) for _ in range(1 << k)] for _ in range(2)]
+    src = torch.from_numpy(np.stack([to_bytes(c, P, montgomery) for c in coeffs])).cuda()          # [2, 2^k, 32]: two columns of one circuit
+    ext = dom.coeff_to_extended(src)
+    back = dom.extended_to_coeff(ext)
+    torch.cuda.synchronize()
+    assert ext.shape == (2, 1 << ek, 32) and back.shape == ext.shape
+    eh, bh = ext.cpu().numpy(), back.cpu().numpy()
+    for c in range(2):
+        assert to_ints(eh[c], P, montgomery) == NR.forward(coeffs[c], ek, w_ext, zeta, P)
+        assert np.array_equal(bh[c, :1 << k], to_bytes(coeffs[c], P, montgomery)) and not bh[c, 1 << k:].any()
+    # lagrange_to_coeff undoes the evaluation over the small domain
+    lag = [NR.forward(c, k, NR.omega_of(P, k), 1, P) for c in coeffs]
+    got = dom.lagrange_to_coeff(torch.from_numpy(np.stack([to_bytes(c, P, montgomery) for c in lag])).cuda())
+    torch.cuda.synchronize()
+    assert np.array_equal(got.cpu().numpy(), src.cpu().numpy())
+
+
+def test_lagrange_to_coeff_of_a_permutation_product_column(H):
+    """A device-produced Z column of the permutation argument (u under one tile; the rows behind Z[u] set to 0) goes to coefficient form on the
+    device; the model's evaluation of those coefficients at omega^i gives Z[i] back."""
+    from test_permutation_product import Case, challenges, columns_tensor, domain_k, true_domain
+    c = Case(H, 64, 4, 1, "bn254_fr", seed=4)
+    from test_lookup_product import usable_for
+    P, u, src = c.P, usable_for(c.rows), (0, 1, 2, 3, 4)
+    k = domain_k(u)
+    assert u < (1 << T) and (1 << k) >= u + 1
+    omega, delta = true_domain(P, u)
+    sigma = c.sigma(src, u, delta, omega)
+    betas, gammas = challenges(P, 21)
+    pa = c.argument(src, 2, delta, omega)
+    z = torch.zeros((3, pa.sets, 1 << k, 32), dtype=torch.uint8, device="cuda")
+    st = torch.zeros(3, dtype=torch.uint8, device="cuda")
+    _, status = c.run(pa, columns_tensor(sigma, u, P, c.chip.montgomery), betas, gammas, u, out=(z, st))
+    assert status == [0, 0, 0] and not z[:, :, u + 1:].any()
+    dom = H.EvaluationDomain(c.chip, k, k + 2, NR.omega_of(P, k + 2), NR.cube_root_of_unity(P))
+    assert dom.omega == omega
+    coeffs = dom.lagrange_to_coeff(z)
+    torch.cuda.synchronize()
+    zh, ch = z.cpu().numpy(), coeffs.cpu().numpy()
+    for b in range(3):
+        for s in range(pa.sets):
+            zi = to_ints(zh[b, s], P, False)
+            assert zi[0] == (1 if s == 0 else to_ints(zh[b, s - 1], P, False)[u]) and any(zi[1:u + 1])
+            assert NR.forward(to_ints(ch[b, s], P, False), k, omega, 1, P) == zi, (b, s)
