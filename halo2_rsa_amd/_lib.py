@@ -105,6 +105,28 @@ class H2RNttConfig(ctypes.Structure):
                 ("omega", ctypes.c_uint64 * 4), ("shift", ctypes.c_uint64 * 4)]
 
 
+H2R_LOOKUP_ARGS, H2R_QUOTIENT_MAX_FIXED = 5, 16
+
+
+class H2RColumnGroup(ctypes.Structure):
+    _fields_ = [("base", ctypes.c_void_p), ("elem_stride", ctypes.c_uint64), ("col_stride", ctypes.c_uint64)]
+
+
+class H2RQuotientInputs(ctypes.Structure):
+    GROUPS = ("advice", "extra", "perm_z", "lookup_a_perm", "lookup_s_perm", "lookup_z", "fixed", "sigma", "l")
+    CHALLENGES = ("theta", "beta", "gamma", "y")
+    _fields_ = [(nm, H2RColumnGroup) for nm in GROUPS] + [(nm, ctypes.c_void_p) for nm in CHALLENGES]
+
+
+class H2RQuotientConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("log_n", ctypes.c_uint32), ("log_ext", ctypes.c_uint32), ("blinding_factors", ctypes.c_uint32),
+                ("omega_ext", ctypes.c_uint64 * 4), ("zeta", ctypes.c_uint64 * 4), ("delta", ctypes.c_uint64 * 4),
+                ("num_fixed", ctypes.c_uint32), ("num_columns", ctypes.c_uint32), ("chunk_len", ctypes.c_uint32), ("n_extra", ctypes.c_uint32),
+                ("lookup_mask", ctypes.c_uint32), ("gate_fixed", ctypes.c_uint8 * 9), ("column_src", ctypes.c_uint8 * H2R_PERM_MAX_COLUMNS),
+                ("lookup_advice", ctypes.c_uint8 * H2R_LOOKUP_ARGS), ("lookup_tag", ctypes.c_uint8 * H2R_LOOKUP_ARGS),
+                ("lookup_enable", ctypes.c_uint8 * H2R_LOOKUP_ARGS), ("table_tag", ctypes.c_uint8), ("table_value", ctypes.c_uint8)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -152,7 +174,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_lookup_hist_values", "h2r_lookup_hist_values_strided", "h2r_lookup_hist_verify", "h2r_lookup_hist_fresh_op", "h2r_lookup_workspace_bytes", "h2r_lookup_permuted_columns", "h2r_field_eval",
            "h2r_lookup_input_columns", "h2r_lookup_product_workspace_bytes", "h2r_lookup_product_columns",
            "h2r_permutation_sets", "h2r_permutation_product_workspace_bytes", "h2r_permutation_product_columns",
-           "h2r_ntt_workspace_bytes", "h2r_ntt_columns",
+           "h2r_ntt_workspace_bytes", "h2r_ntt_columns", "h2r_quotient_sets", "h2r_quotient_columns",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -163,6 +185,7 @@ KERNEL_CHAIN, KERNEL_TRACE, KERNEL_HIST, KERNEL_AUX, KERNEL_EMIT, KERNEL_STEP, K
 KERNEL_LOOKUP_INPUT, KERNEL_LOOKUP_PRODUCT_TILES, KERNEL_LOOKUP_PRODUCT_CARRY, KERNEL_LOOKUP_PRODUCT_SCAN = 9, 10, 11, 12
 KERNEL_PERM_PRODUCT_TILES, KERNEL_PERM_PRODUCT_CARRY, KERNEL_PERM_PRODUCT_SCAN = 13, 14, 15
 KERNEL_NTT_SETUP, KERNEL_NTT_PASS = 16, 17
+KERNEL_QUOTIENT = 18
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
 FRESH_OPS = ["add", "sub", "add_mod", "sub_mod", "is_zero", "is_equal_fresh", "is_less_than", "is_less_than_or_equal",
@@ -362,6 +385,10 @@ def lib():
     L.h2r_ntt_workspace_bytes.argtypes = [pntt]
     L.h2r_ntt_workspace_bytes.restype = u64
     L.h2r_ntt_columns.argtypes = [vp, pntt, vp, u64, u64, vp, u64, u64, u32, u64, vp, vp]
+    pquot = ctypes.POINTER(H2RQuotientConfig)
+    L.h2r_quotient_sets.argtypes = [pquot, ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.h2r_quotient_sets.restype = u32
+    L.h2r_quotient_columns.argtypes = [vp, pquot, ctypes.POINTER(H2RQuotientInputs), u64, vp, u64, vp, vp]
     L.h2r_field_eval.argtypes = [vp, u32, pu64, pu64, pu64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]

@@ -1307,6 +1307,87 @@ class EvaluationDomain:
         """2^extended_k evaluations over the coset -> the 2^extended_k coefficients (truncation stays the caller's)."""
         return self.ntt(cols, self.extended_k, inverse=True, shift=self.zeta, out=out)
 
+    def vanishing_columns(self, blinding_factors: int) -> torch.Tensor:
+        """uint8 [3, 2^extended_k, 32]: l0, l_last and l_active = 1 - l_last - l_blind of the 2^k domain with `blinding_factors` blinding
+        rows, in extended form (lagrange_to_coeff, then coeff_to_extended) -- the `l` columns of quotient()."""
+        n = 1 << self.k
+        u = n - blinding_factors - 1
+        if u < 1:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.vanishing_columns")
+        host = np.zeros((3, n, 32), dtype=np.uint8)
+        one = np.frombuffer(int(self.one).to_bytes(32, "little"), dtype=np.uint8)
+        host[0, 0] = one
+        host[1, u] = one
+        host[2, :u] = one
+        lag = torch.from_numpy(host).to("cuda:%d" % self.chip.device)
+        return self.coeff_to_extended(self.lagrange_to_coeff(lag))
+
+    def quotient(self, blinding_factors: int, delta: int, gate_fixed: Sequence[int], column_src: Sequence[int], chunk_len: int, advice: torch.Tensor,
+                 perm_z: torch.Tensor, fixed: torch.Tensor, sigma: torch.Tensor, l: torch.Tensor, thetas: Sequence[int], betas: Sequence[int],
+                 gammas: Sequence[int], ys: Sequence[int], extra: Optional[torch.Tensor] = None, lookup_mask: int = 0,
+                 lookup_advice: Sequence[int] = (0, 1, 2, 3, 0), lookup_tag: Sequence[int] = (0,) * 5, lookup_enable: Sequence[int] = (0,) * 5,
+                 table_tag: int = 0, table_value: int = 0, lookup_a_perm: Optional[torch.Tensor] = None, lookup_s_perm: Optional[torch.Tensor] = None,
+                 lookup_z: Optional[torch.Tensor] = None, out=None):
+        """(h, status): the vanishing argument's quotient on the extended domain (h2r_quotient_columns; halo2's evaluate_h for this circuit's
+        constraint system, restated in DESIGN.md section 2g).  h: uint8 [batch, 2^extended_k, 32] in the chip's representation; status
+        H2R_E_SHAPE where a challenge is not canonical (that circuit's h is left untouched).
+        Every column is in extended form, uint8 with N = 2^extended_k rows whose last two dimensions are contiguous.  Per circuit
+        [batch, columns, N, 32]: advice (5, physical), extra (n_extra), perm_z (S), lookup_a_perm / lookup_s_perm / lookup_z (column k =
+        argument k, up to the highest bit of lookup_mask).  The proving key's [columns, N, 32]: fixed, sigma (one per permutation column), l
+        (vanishing_columns()).  gate_fixed: the indices of sa, sb, sc, sd, se, s_mul_ab, s_mul_cd, se_next, s_const among the fixed columns;
+        column_src / chunk_len as PermutationArgument; lookup_advice / lookup_tag / lookup_enable / table_tag / table_value: per argument
+        the physical advice column and the fixed columns of its input expression theta * tag + enable * advice, and of the table's.
+        delta and the challenges: integers in the chip's representation.  out: (h, status) to write into (h must overlap no input; a
+        status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        N = 1 << self.extended_k
+        batch = advice.shape[0]
+        cfg = _lib.H2RQuotientConfig()
+        cfg.struct_size = ctypes.sizeof(cfg)
+        cfg.log_n, cfg.log_ext, cfg.blinding_factors = self.k, self.extended_k, blinding_factors
+        for i in range(4):
+            cfg.omega_ext[i] = (self.omega_ext >> (64 * i)) & (2 ** 64 - 1)
+            cfg.zeta[i] = (self.zeta >> (64 * i)) & (2 ** 64 - 1)
+            cfg.delta[i] = (int(delta) >> (64 * i)) & (2 ** 64 - 1)
+        if len(column_src) > _lib.H2R_PERM_MAX_COLUMNS or len(gate_fixed) != 9 or any(len(x) != _lib.H2R_LOOKUP_ARGS for x in (lookup_advice, lookup_tag, lookup_enable)):
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.quotient")
+        cfg.num_fixed, cfg.num_columns, cfg.chunk_len, cfg.lookup_mask = fixed.shape[0], len(column_src), chunk_len, lookup_mask
+        cfg.n_extra = max([int(s) - 4 for s in column_src if int(s) >= 5] + [0])
+        for i, v in enumerate(gate_fixed):
+            cfg.gate_fixed[i] = int(v)
+        for c, s in enumerate(column_src):
+            cfg.column_src[c] = int(s)
+        for k in range(_lib.H2R_LOOKUP_ARGS):
+            cfg.lookup_advice[k], cfg.lookup_tag[k], cfg.lookup_enable[k] = int(lookup_advice[k]), int(lookup_tag[k]), int(lookup_enable[k])
+        cfg.table_tag, cfg.table_value = int(table_tag), int(table_value)
+        inp = _lib.H2RQuotientInputs()
+
+        def group(name, t, per_circuit):
+            if t is None:
+                return
+            assert t.dtype == torch.uint8 and t.dim() == (4 if per_circuit else 3) and t.shape[-1] == 32 and t.shape[-2] == N, name
+            assert t.stride(-1) == 1 and t.stride(-2) == 32 and (not per_circuit or t.shape[0] == batch), name
+            g = getattr(inp, name)
+            g.base, g.elem_stride, g.col_stride = t.data_ptr(), t.stride(0) if per_circuit else 0, t.stride(1) if per_circuit else t.stride(0)
+
+        for name, t in (("advice", advice), ("extra", extra), ("perm_z", perm_z), ("lookup_a_perm", lookup_a_perm), ("lookup_s_perm", lookup_s_perm),
+                        ("lookup_z", lookup_z)):
+            group(name, t, True)
+        for name, t in (("fixed", fixed), ("sigma", sigma), ("l", l)):
+            group(name, t, False)
+        dev = advice.device
+        ch = [LookupArgument._challenges(self, v, batch, dev) for v in (thetas, betas, gammas, ys)]
+        inp.theta, inp.beta, inp.gamma, inp.y = (c.data_ptr() for c in ch)
+        if out is None:
+            h = torch.empty((batch, N, 32), dtype=torch.uint8, device=dev)
+            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        else:
+            h, status = out
+        assert h.dim() == 3 and h.shape[1:] == (N, 32) and h.stride(2) == 1 and h.stride(1) == 32
+        check(lib().h2r_quotient_columns(self.chip._ctx, ctypes.byref(cfg), ctypes.byref(inp), batch, h.data_ptr(), h.stride(0),
+                                         status.data_ptr() if status is not None else None, self.chip._stream()), "h2r_quotient_columns")
+        self._keep_q = (ch, advice, extra, perm_z, lookup_a_perm, lookup_s_perm, lookup_z, fixed, sigma, l, h, status)   # alive until the stream has run the kernel
+        return h, status
+
 
 @dataclass
 class FreshResult:

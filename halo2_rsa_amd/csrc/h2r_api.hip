@@ -26,6 +26,7 @@
 #include "h2r_lookup_product.hpp"
 #include "h2r_permutation_product.hpp"
 #include "h2r_ntt.hpp"
+#include "h2r_quotient.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4099,7 +4100,7 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
 
 // ---- the evaluation domain's transforms (h2r_ntt.hpp, h2r_tu_ntt.hip) -------------------------------------------------------------------
 namespace {
-static_assert(H2R_KERNEL_NTT_PASS == H2R_KERNEL_NTT_SETUP + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_NTT_PASS + 1, "h2r.h: the launch classes");
+static_assert(H2R_KERNEL_NTT_PASS == H2R_KERNEL_NTT_SETUP + 1 && H2R_KERNEL_QUOTIENT == H2R_KERNEL_NTT_PASS + 1, "h2r.h: the launch classes");
 // what h2r_ntt_workspace_bytes answers 0 for: the parts of a configuration that need no ctx (omega and shift are compared with the ctx's p)
 int32_t ntt_cfg_status(const h2r_ntt_config *cfg) {
     if (cfg->struct_size != sizeof(h2r_ntt_config) || (cfg->flags & ~H2R_NTT_INVERSE)) return H2R_E_UNSUPPORTED;
@@ -4223,6 +4224,147 @@ int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const voi
                 HIP_TRY(launch_ntt_pass(na, (u32)std::min<u64>(cols_per, num_cols - c0), (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
             }
         }
+    }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the vanishing argument's quotient on the extended domain (h2r_quotient.hpp, h2r_tu_quotient.hip) -------------------------------------
+namespace {
+static_assert(H2R_KERNEL_COUNT == H2R_KERNEL_QUOTIENT + 1, "h2r.h: the launch classes");
+static_assert(H2R_QUOTIENT_MAX_FIXED == QUOT_MAX_FIXED && H2R_LOOKUP_ARGS == QUOT_LOOKUP_ARGS && H2R_PERM_MAX_COLUMNS == QUOT_PERM_MAX_COLUMNS &&
+              sizeof(((h2r_quotient_config *)nullptr)->gate_fixed) == QUOT_GATE_FIXED, "h2r.h and the kernel's argument struct");
+h2r_permutation_config quotient_perm_cfg(const h2r_quotient_config *cfg) {
+    h2r_permutation_config pc;
+    std::memset(&pc, 0, sizeof pc);
+    pc.struct_size = sizeof pc;
+    pc.num_columns = cfg->num_columns; pc.chunk_len = cfg->chunk_len; pc.n_extra = cfg->n_extra;
+    std::memcpy(pc.column_src, cfg->column_src, sizeof pc.column_src);
+    return pc;
+}
+// what h2r_quotient_sets answers 0 for: the parts of a configuration that need no ctx (omega_ext, zeta and delta are compared with the ctx's p)
+int32_t quotient_cfg_status(const h2r_quotient_config *cfg) {
+    if (cfg->struct_size != sizeof(h2r_quotient_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->log_n == 0 || cfg->log_ext <= cfg->log_n || cfg->log_ext > QUOT_MAX_LOG || cfg->log_ext - cfg->log_n > QUOT_MAX_SCALE_LOG) return H2R_E_SHAPE;
+    if ((u64)cfg->blinding_factors + 2 > (1ull << cfg->log_n)) return H2R_E_SHAPE;   // u = n - blinding_factors - 1 >= 1
+    if (cfg->num_fixed > QUOT_MAX_FIXED) return H2R_E_SHAPE;
+    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i)
+        if (cfg->gate_fixed[i] >= cfg->num_fixed) return H2R_E_SHAPE;
+    if (cfg->lookup_mask >> H2R_LOOKUP_ARGS) return H2R_E_SHAPE;
+    for (u32 k = 0; k < H2R_LOOKUP_ARGS; ++k) {
+        if (!((cfg->lookup_mask >> k) & 1u)) continue;
+        if (cfg->lookup_advice[k] >= 5 || cfg->lookup_tag[k] >= cfg->num_fixed || cfg->lookup_enable[k] >= cfg->num_fixed) return H2R_E_SHAPE;
+    }
+    if (cfg->lookup_mask && (cfg->table_tag >= cfg->num_fixed || cfg->table_value >= cfg->num_fixed)) return H2R_E_SHAPE;
+    const h2r_permutation_config pc = quotient_perm_cfg(cfg);
+    return perm_cfg_valid(&pc) ? H2R_OK : H2R_E_SHAPE;
+}
+// lookup column slots in use: the highest selected argument + 1
+u32 quotient_lookup_cols(u32 mask) { u32 nl = 0; while (mask >> nl) ++nl; return nl; }
+}  // namespace
+
+uint32_t h2r_quotient_sets(const h2r_quotient_config *cfg, uint32_t *circuit_columns, uint32_t *key_columns) try {
+    if (!cfg || quotient_cfg_status(cfg) != H2R_OK) return 0;
+    const h2r_permutation_config pc = quotient_perm_cfg(cfg);
+    const u32 S = perm_sets(&pc);
+    u32 fixed_seen = 0, nk = 0;
+    auto use = [&](u32 c) { fixed_seen |= 1u << c; };
+    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i) use(cfg->gate_fixed[i]);
+    for (u32 k = 0; k < H2R_LOOKUP_ARGS; ++k)
+        if ((cfg->lookup_mask >> k) & 1u) { use(cfg->lookup_tag[k]); use(cfg->lookup_enable[k]); ++nk; }
+    if (nk) { use(cfg->table_tag); use(cfg->table_value); }
+    if (circuit_columns) *circuit_columns = 5 + cfg->n_extra + S + 3 * nk;
+    if (key_columns) *key_columns = (u32)__builtin_popcount(fixed_seen) + cfg->num_columns + 3;
+    return S;
+} H2R_CATCH_ZERO
+
+int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg, const h2r_quotient_inputs *in, uint64_t batch, void *h_out,
+                             uint64_t h_elem_stride, uint8_t *status, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !in || !h_out) return H2R_E_NULL;
+    if (!in->theta || !in->beta || !in->gamma || !in->y) return H2R_E_NULL;
+    if (!in->advice.base || !in->perm_z.base || !in->fixed.base || !in->sigma.base || !in->l.base) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_quotient_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->n_extra && cfg->n_extra <= H2R_PERM_MAX_EXTRA && !in->extra.base) return H2R_E_NULL;
+    if (cfg->lookup_mask && !(cfg->lookup_mask >> H2R_LOOKUP_ARGS) && (!in->lookup_a_perm.base || !in->lookup_s_perm.base || !in->lookup_z.base)) return H2R_E_NULL;
+    if (const int32_t rc = quotient_cfg_status(cfg)) return rc;
+    const FieldConsts &f = ctx->fc;
+    if (ge_p(cfg->omega_ext, f.p) || ge_p(cfg->zeta, f.p) || ge_p(cfg->delta, f.p)) return H2R_E_SHAPE;
+    if (!(cfg->zeta[0] | cfg->zeta[1] | cfg->zeta[2] | cfg->zeta[3])) return H2R_E_SHAPE;
+    const bool mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0;
+    const u32 log_n = cfg->log_n, log_ext = cfg->log_ext, scale_log = log_ext - log_n, r = 1u << scale_log;
+    const Fe one = [&] { Fe x; for (int k = 0; k < 4; ++k) x.v[k] = f.one[k]; return x; }();
+    Fe omega, zeta, delta;   // Montgomery form from here on
+    for (int k = 0; k < 4; ++k) { omega.v[k] = cfg->omega_ext[k]; zeta.v[k] = cfg->zeta[k]; delta.v[k] = cfg->delta[k]; }
+    if (!mont) { omega = fe_to_mont(omega, f); zeta = fe_to_mont(zeta, f); delta = fe_to_mont(delta, f); }
+    QuotientArgs qa;
+    std::memset(static_cast<void *>(&qa), 0, sizeof qa);
+    qa.wpow[0] = omega;
+    for (u32 b = 1; b < QUOT_MAX_LOG; ++b) qa.wpow[b] = fe_mont_mul(qa.wpow[b - 1], qa.wpow[b - 1], f);
+    if (!fe_is_zero(fe_add(qa.wpow[log_ext - 1], one, f.p))) return H2R_E_SHAPE;   // a primitive N-th root of unity: omega_ext^(N / 2) = -1
+    {   // X_j^n = zeta^n * (omega_ext^n)^(j mod r): none of them may be 1
+        Fe zn = zeta;
+        for (u32 b = 0; b < log_n; ++b) zn = fe_mont_mul(zn, zn, f);
+        const Fe wn = qa.wpow[log_n];
+        for (u32 i = 0; i < r; ++i) {
+            const Fe d = fe_sub(zn, one, f.p);
+            if (fe_is_zero(d)) return H2R_E_SHAPE;
+            const Fe inv = fe_inv(fe_from_mont(d, f), f);   // d is d * R: back to the integer, invert
+            qa.xinv[i] = mont ? fe_to_mont(inv, f) : inv;   // a canonical ctx: the product with the plain integer is also the conversion on the store
+            zn = fe_mont_mul(zn, wn, f);
+        }
+    }
+    const h2r_permutation_config pc = quotient_perm_cfg(cfg);
+    const u32 S = perm_sets(&pc), nl = quotient_lookup_cols(cfg->lookup_mask);
+    const u64 col = 32ull << log_ext;
+    struct Group { const h2r_column_group *g; u32 cols; bool per_circuit; };
+    const Group groups[9] = {{&in->advice, 5, true}, {&in->extra, cfg->n_extra, true}, {&in->perm_z, S, true}, {&in->lookup_a_perm, nl, true},
+                             {&in->lookup_s_perm, nl, true}, {&in->lookup_z, nl, true}, {&in->fixed, cfg->num_fixed, false},
+                             {&in->sigma, cfg->num_columns, false}, {&in->l, 3, false}};
+    if (((reinterpret_cast<u64>(h_out) | h_elem_stride) & 15) || h_elem_stride < col) return H2R_E_SHAPE;
+    const u128 h0 = reinterpret_cast<u64>(h_out), h1 = h0 + ntt_extent(col, h_elem_stride, col, 1, batch);
+    for (const Group &gr : groups) {
+        if (!gr.cols) continue;
+        const u64 es = gr.per_circuit ? gr.g->elem_stride : 0, cs = gr.g->col_stride;
+        if ((reinterpret_cast<u64>(gr.g->base) | es | cs) & 15) return H2R_E_SHAPE;
+        if (cs < col) return H2R_E_SHAPE;
+        if (gr.per_circuit && !ntt_columns_disjoint(col, es, cs, gr.cols, batch)) return H2R_E_SHAPE;
+        // rotated reads come from other workgroups' ranges: h may overlap no input
+        const u128 g0 = reinterpret_cast<u64>(gr.g->base);
+        const u128 g1 = g0 + (gr.per_circuit ? ntt_extent(col, es, cs, gr.cols, batch) : (batch ? (u128)(gr.cols - 1) * cs + col : 0));
+        if (g0 < h1 && h0 < g1) return H2R_E_SHAPE;
+    }
+    if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+
+    auto cols = [](const h2r_column_group &g, bool used, bool per_circuit) {
+        QuotCols c;
+        c.base = used ? static_cast<const u8 *>(g.base) : nullptr;
+        c.elem_stride = used && per_circuit ? g.elem_stride : 0; c.col_stride = used ? g.col_stride : 0;
+        return c;
+    };
+    qa.advice = cols(in->advice, true, true); qa.extra = cols(in->extra, cfg->n_extra != 0, true); qa.perm_z = cols(in->perm_z, true, true);
+    qa.a_perm = cols(in->lookup_a_perm, nl != 0, true); qa.s_perm = cols(in->lookup_s_perm, nl != 0, true); qa.look_z = cols(in->lookup_z, nl != 0, true);
+    qa.fixed = cols(in->fixed, true, false); qa.sigma = cols(in->sigma, true, false); qa.l = cols(in->l, true, false);
+    qa.theta = in->theta; qa.beta = in->beta; qa.gamma = in->gamma; qa.y = in->y;
+    qa.status = status; qa.h = static_cast<u8 *>(h_out); qa.h_elem_stride = h_elem_stride;
+    qa.log_ext = log_ext; qa.scale_log = scale_log; qa.mont = mont ? 1u : 0u; qa.last_rot = cfg->blinding_factors + 1;
+    qa.m = cfg->num_columns; qa.chunk_len = std::min<u32>(cfg->chunk_len, cfg->num_columns); qa.n_sets = S; qa.lookup_mask = cfg->lookup_mask;
+    std::memcpy(qa.gate_fixed, cfg->gate_fixed, sizeof qa.gate_fixed); std::memcpy(qa.src, cfg->column_src, sizeof qa.src);
+    std::memcpy(qa.lookup_advice, cfg->lookup_advice, sizeof qa.lookup_advice); std::memcpy(qa.lookup_tag, cfg->lookup_tag, sizeof qa.lookup_tag);
+    std::memcpy(qa.lookup_enable, cfg->lookup_enable, sizeof qa.lookup_enable);
+    qa.table_tag = cfg->table_tag; qa.table_value = cfg->table_value;
+    qa.dpow[0] = one;
+    for (u32 c = 1; c < QUOT_PERM_MAX_COLUMNS; ++c) qa.dpow[c] = fe_mont_mul(qa.dpow[c - 1], delta, f);
+    qa.zeta = zeta; qa.f = f;
+    // launches below the 2^32 global size: slices of tiles (a grid's x holds the circuits, at most 65,535)
+    const u64 tiles = quotient_tiles(log_ext), max_blocks = ((1ull << 32) - 1) / 256;
+    const u64 tiles_per = std::min<u64>({tiles, 65535, max_blocks / batch});
+    if (!tiles_per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (u64 t0 = 0; t0 < tiles; t0 += tiles_per) {
+        qa.tile0 = (u32)t0;
+        ProfScope ps(H2R_KERNEL_QUOTIENT, st, true);
+        HIP_TRY(launch_quotient(qa, (u32)std::min<u64>(tiles_per, tiles - t0), (u32)batch, st, ps.a, ps.on ? ps.b : nullptr));
     }
     return H2R_OK;
 } H2R_CATCH_STATUS

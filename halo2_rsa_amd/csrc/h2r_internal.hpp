@@ -10,6 +10,7 @@
 //   h2r_tu_lookup_product.hip   the lookup argument's input columns and grand product (h2r_lookup_product.hpp)
 //   h2r_tu_permutation_product.hip   the permutation argument's grand product (h2r_permutation_product.hpp)
 //   h2r_tu_ntt.hip     the evaluation domain's transforms (h2r_ntt.hpp)
+//   h2r_tu_quotient.hip   the vanishing argument's quotient on the extended domain (h2r_quotient.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -118,5 +119,8 @@ struct NttSetupArgs;
 struct NttArgs;
 hipError_t launch_ntt_setup(const NttSetupArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 hipError_t launch_ntt_pass(const NttArgs &a, u32 num_cols, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_quotient.hip (argument struct: h2r_quotient.hpp).  The tiles [a.tile0, a.tile0 + num_tiles) of num_elems circuits.
+struct QuotientArgs;
+hipError_t launch_quotient(const QuotientArgs &a, u32 num_tiles, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

@@ -908,6 +908,74 @@ uint64_t h2r_ntt_workspace_bytes(const h2r_ntt_config *cfg);
 int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const void *in, uint64_t in_elem_stride, uint64_t in_col_stride,
                         void *out, uint64_t out_elem_stride, uint64_t out_col_stride, uint32_t num_cols, uint64_t batch, void *workspace,
                         h2r_stream_t stream);
+/* ---- the vanishing argument: the quotient polynomial h on the extended domain ----
+ * THIRD-PARTY behaviour (halo2 plonk::evaluation::evaluate_h feeding vanishing::prover::construct, not in the reference tree), restated in
+ * DESIGN.md section 2g; parity is pinned against a Python restatement (tests/quotient_ref.py, tests/test_quotient_gpu.py), not against
+ * upstream.  The one consumer of the extended cosets h2r_ntt_columns produces.  Specific to this circuit's constraint system -- the one main
+ * gate, at most H2R_PERM_MAX_COLUMNS permutation columns in sets, the H2R_LOOKUP_ARGS lookup arguments -- and not a general expression
+ * evaluator.  n = 2^log_n, N = 2^log_ext, r = N / n, u = n - blinding_factors - 1; X_j = zeta * omega_ext^j is the point of index j < N
+ * (natural order) and f<t>[j] = f[(j + t * r) mod N] the rotation of an extended column by t rows.  Per circuit (= element) its own theta,
+ * beta, gamma, y.  acc starts at 0 and every term t does acc = acc * y + t; the term order is upstream's and part of the contract:
+ *   1. gate:  sum_{i<5} s_i * v_i + s_mul_ab * v_0 * v_1 + s_mul_cd * v_2 * v_3 + se_next * v_4<+1> + s_const
+ *             (v_i = advice column i, PHYSICAL; s = the fixed columns gate_fixed[0..8] in h2r_fixed_row's order)
+ *   2. permutation, v_c = permutation column c (column_src[c] = 0..4: physical advice column, 5 + j: extra column j), S = ceil(m / chunk_len)
+ *      sets as in h2r_permutation_config, label_c = delta^c * beta * X_j with c the GLOBAL column index:
+ *        l0 * (1 - Z_0);   l_last * (Z_{S-1}^2 - Z_{S-1});   for s = 1 .. S-1: l0 * (Z_s - Z_{s-1}<-(blinding_factors + 1)>);
+ *        for s = 0 .. S-1: l_active * (Z_s<+1> * prod_{c in s} (v_c + beta * sigma_c + gamma) - Z_s * prod_{c in s} (v_c + label_c + gamma))
+ *   3. per selected lookup argument k (bit k of lookup_mask), ascending, with A_k = theta * fixed[lookup_tag[k]] + fixed[lookup_enable[k]] *
+ *      v_(lookup_advice[k]) and S = theta * fixed[table_tag] + fixed[table_value]:
+ *        l0 * (1 - Z_k);   l_last * (Z_k^2 - Z_k);   l_active * (Z_k<+1> * (A'_k + beta)(S'_k + gamma) - Z_k * (A_k + beta)(S + gamma));
+ *        l0 * (A'_k - S'_k);   l_active * (A'_k - S'_k) * (A'_k - A'_k<-1>)
+ *   4. h[j] = acc / (X_j^n - 1).  X_j^n takes only the r values zeta^n * (omega_ext^n)^(j mod r); the host inverts them.
+ * A_k is EVALUATED as an expression of the fixed and advice cosets, not read as the extension of h2r_lookup_input_columns's Lagrange column:
+ * the two agree on the domain, not on the coset, and a verifier recomputes the expression.  With lookup_enable = the indicator of a nonzero
+ * tag it equals section 2d's A on every row; upstream's exact input expression stays unpinned, which is why it is given as column indices.
+ *  - Every column is planar, N elements of 32 bytes in the ctx's representation (for these vectors only H2R_ADVICE_MONTGOMERY matters);
+ *    column c of circuit e of a group lies at base + e * elem_stride + c * col_stride.  Per circuit: advice (5 columns), extra (n_extra),
+ *    perm_z (S), lookup_a_perm / lookup_s_perm / lookup_z (column k = argument k; columns of unselected arguments are never read).  The
+ *    proving key's, shared by every circuit (elem_stride ignored): fixed (num_fixed), sigma (m), l (3: l0, l_last, l_active = 1 - l_last -
+ *    l_blind).  theta, beta, gamma, y: [batch][4] uint64 on the device.  Arithmetic is in the Montgomery domain; a canonical ctx converts on
+ *    load and store, a Montgomery ctx nothing; every result is the canonical representative.
+ *  - h of circuit e: N elements at h_out + e * h_elem_stride, written once.  h_out must overlap no input (rotated reads come from other
+ *    workgroups' ranges).  One pointwise launch, no workspace, no workgroup waits for another; the call enqueues and never synchronises;
+ *    launches are sliced internally below the 2^32 global size.  status (nullable, [batch]) is never cleared: circuits whose byte is nonzero
+ *    on entry are skipped; H2R_E_SHAPE where a challenge is not canonical (nothing is written for that circuit).
+ *  - h2r_quotient_sets: S of a configuration, and (nullable) the columns the call reads per circuit and from the key; 0 for a configuration
+ *    the call would refuse whatever the ctx (a host function; no device and no ctx needed).
+ *  - H2R_E_NULL for a NULL required pointer (status is optional; extra.base is required exactly when n_extra > 0, the three lookup groups
+ *    exactly when lookup_mask != 0); H2R_E_UNSUPPORTED for another struct_size, a host-only ctx (that one after every other check) or more
+ *    than 65,535 circuits; H2R_E_SHAPE for log_n = 0, log_ext <= log_n, log_ext > 24, log_ext - log_n > 4, u < 1, num_fixed > 16, an index
+ *    >= num_fixed (gate_fixed; of a selected argument lookup_tag / lookup_enable; table_tag / table_value when an argument is selected), a
+ *    lookup_advice >= 5 of a selected argument, lookup_mask bits beyond H2R_LOOKUP_ARGS, the permutation fields as h2r_permutation_config
+ *    refuses them, omega_ext, zeta or delta >= p, zeta = 0, omega_ext^(N/2) != -1, zeta^n in the subgroup (some X_j^n = 1), a pointer or
+ *    stride that is not 16-byte aligned, a stride smaller than its column, per-circuit columns of a group that overlap each other (either
+ *    elem_stride covers a circuit's columns or col_stride covers every circuit's column, as for h2r_ntt_columns), and h_out overlapping any
+ *    input range.  batch = 0 returns H2R_OK with no launch. */
+#define H2R_QUOTIENT_MAX_FIXED 16u
+typedef struct h2r_column_group {   /* planar columns: column c of circuit e at base + e * elem_stride + c * col_stride */
+    const void *base;
+    uint64_t elem_stride, col_stride;
+} h2r_column_group;
+typedef struct h2r_quotient_inputs {
+    h2r_column_group advice, extra, perm_z, lookup_a_perm, lookup_s_perm, lookup_z;   /* per circuit */
+    h2r_column_group fixed, sigma, l;                                                /* the proving key's: elem_stride is ignored */
+    const uint64_t *theta, *beta, *gamma, *y;                                        /* [batch][4] on the device, the ctx's representation */
+} h2r_quotient_inputs;
+typedef struct h2r_quotient_config {
+    uint32_t struct_size;              /* sizeof; anything else: H2R_E_UNSUPPORTED */
+    uint32_t log_n, log_ext, blinding_factors;
+    uint64_t omega_ext[4], zeta[4], delta[4];   /* a primitive 2^log_ext-th root of unity, the coset shift, F::DELTA: the ctx's representation */
+    uint32_t num_fixed;
+    uint32_t num_columns, chunk_len, n_extra;   /* as in h2r_permutation_config */
+    uint32_t lookup_mask;              /* bit k = argument k takes part */
+    uint8_t  gate_fixed[9];            /* sa, sb, sc, sd, se, s_mul_ab, s_mul_cd, se_next, s_const among the fixed columns */
+    uint8_t  column_src[H2R_PERM_MAX_COLUMNS];
+    uint8_t  lookup_advice[H2R_LOOKUP_ARGS], lookup_tag[H2R_LOOKUP_ARGS], lookup_enable[H2R_LOOKUP_ARGS];
+    uint8_t  table_tag, table_value;
+} h2r_quotient_config;
+uint32_t h2r_quotient_sets(const h2r_quotient_config *cfg, uint32_t *circuit_columns, uint32_t *key_columns);
+int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg, const h2r_quotient_inputs *in, uint64_t batch, void *h_out,
+                             uint64_t h_elem_stride, uint8_t *status, h2r_stream_t stream);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1203,7 +1271,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_LOOKUP_PRODUCT_TILES = 10, H2R_KERNEL_LOOKUP_PRODUCT_CARRY = 11, H2R_KERNEL_LOOKUP_PRODUCT_SCAN = 12 /* the grand product's three launches */,
        H2R_KERNEL_PERM_PRODUCT_TILES = 13, H2R_KERNEL_PERM_PRODUCT_CARRY = 14, H2R_KERNEL_PERM_PRODUCT_SCAN = 15 /* the permutation argument's grand product, likewise */,
        H2R_KERNEL_NTT_SETUP = 16 /* ntt_setup_kernel: the twiddle tables of one call */, H2R_KERNEL_NTT_PASS = 17 /* ntt_pass_kernel: one launch per pass */,
-       H2R_KERNEL_COUNT = 18 };
+       H2R_KERNEL_QUOTIENT = 18 /* quotient_kernel: h on the extended domain */,
+       H2R_KERNEL_COUNT = 19 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
