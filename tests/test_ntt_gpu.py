@@ -3,7 +3,8 @@ section 2f]) against the plain model of tests/ntt_ref.py, byte for byte.
 
 Every output buffer is pre-filled with a sentinel and has guard rows behind every column, which must come back unchanged.  The kernel works
 in tiles of 2^T elements (T = NTT_TILE_LOG, read from csrc/h2r_ntt.hpp) and takes ceil(log n / T) passes; sizes are chosen against T: under
-one tile, one tile, just above it (two passes), 2T (two full passes) and 2T + 1 (three passes).  Up to 2^(T+1) points the whole output is
+one tile, one tile, just above it (two passes), 2T (two full passes) and 2T + 1 (three passes), and against the power tables' split
+(NTT_SPLIT_LOG, read from the same header): 2^SPLIT and 2^(SPLIT + 1) points.  Up to 2^(T+1) points and at those two the whole output is
 compared with the model; at 2^(2T) and 2^(2T+1), where a Python transform has too many terms, with Horner at sampled points, with the
 closed form of geometric inputs, and with inputs whose inverse transform is known (two monomials)."""
 import os
@@ -27,7 +28,9 @@ R256 = 1 << 256
 SENTINEL = 0xAB
 GUARD = 3                                # sentinel rows behind every output column
 with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_ntt.hpp")) as _f:
-    T = int(re.search(r"constexpr u32 NTT_TILE_LOG = (\d+);", _f.read()).group(1))
+    _src = _f.read()
+    T = int(re.search(r"constexpr u32 NTT_TILE_LOG = (\d+);", _src).group(1))
+    SPLIT = int(re.search(r"constexpr u32 NTT_SPLIT_LOG = (\d+);", _src).group(1))   # exponents below 2^SPLIT come from the low power table alone
 
 
 @pytest.fixture(scope="module")
@@ -124,6 +127,26 @@ def test_dense_against_the_model(H, field, montgomery):
         x = [[[rng.randrange(P) for _ in range(1 << k_in)] for _ in range(2)]]
         for g in shifts(d, rng):
             assert d.run(x, k_out, shift=g)[0] == [NR.forward(c, k_out, w, g, P) for c in x[0]], ("forward", k_in, k_out, g)
+
+
+@pytest.mark.parametrize("k,field,montgomery", [(SPLIT, "pasta_fp", False), (SPLIT + 1, "bn254_fr", True)], ids=["split-canonical", "split+1-montgomery"])
+def test_dense_around_the_power_table_split(H, k, field, montgomery):
+    """2^SPLIT points: the last size whose factors between the passes and whose g^i all come from the low table; 2^(SPLIT + 1): the first
+    that needs the product of both tables -- two passes, (SPLIT + 1) / 2 rounded up and down, the size of a k = 10 circuit's extended
+    domain.  The whole output against the model, forward and inverse, and the forward of fewer coefficients than points (g^i for i below
+    and from 2^SPLIT on)."""
+    assert T < k <= 2 * T and SPLIT + 1 <= 2 * T
+    d = Dom(H, field, montgomery, k)
+    P, w = d.P, d.omega(k)
+    rng = random.Random("split/%d" % k)
+    x = [[[rng.randrange(P) for _ in range(1 << k)] for _ in range(2)]]
+    x[0][1][0], x[0][1][-1] = P - 1, 0
+    for g in shifts(d, rng):
+        assert d.run(x, k, shift=g)[0] == [NR.forward(c, k, w, g, P) for c in x[0]], ("forward", k, g)
+        assert d.run(x, k, inverse=True, shift=g)[0] == [NR.inverse(c, k, w, g, P) for c in x[0]], ("inverse", k, g)
+    for k_in in sorted({k - 3, SPLIT} - {k}):
+        short = [[c[:1 << k_in] for c in x[0]]]
+        assert d.run(short, k, shift=d.zeta)[0] == [NR.forward(c, k, w, d.zeta, P) for c in short[0]], ("forward", k_in, k)
 
 
 @pytest.mark.parametrize("montgomery", [False, True], ids=["canonical", "montgomery"])
