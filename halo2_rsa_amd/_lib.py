@@ -127,6 +127,17 @@ class H2RQuotientConfig(ctypes.Structure):
                 ("lookup_enable", ctypes.c_uint8 * H2R_LOOKUP_ARGS), ("table_tag", ctypes.c_uint8), ("table_value", ctypes.c_uint8)]
 
 
+H2R_OPEN_MAX_COLUMNS, H2R_OPEN_MAX_POINTS = 64, 4
+
+
+class H2ROpenColumn(ctypes.Structure):
+    _fields_ = [("base", ctypes.c_void_p), ("elem_stride", ctypes.c_uint64), ("point_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class H2ROpenConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("n_coeffs", ctypes.c_uint32), ("num_cols", ctypes.c_uint32), ("num_points", ctypes.c_uint32)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -175,6 +186,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_lookup_input_columns", "h2r_lookup_product_workspace_bytes", "h2r_lookup_product_columns",
            "h2r_permutation_sets", "h2r_permutation_product_workspace_bytes", "h2r_permutation_product_columns",
            "h2r_ntt_workspace_bytes", "h2r_ntt_columns", "h2r_quotient_sets", "h2r_quotient_columns",
+           "h2r_open_queries", "h2r_open_workspace_bytes", "h2r_open_eval_columns", "h2r_open_witness_columns", "h2r_fold_columns",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -186,6 +198,7 @@ KERNEL_LOOKUP_INPUT, KERNEL_LOOKUP_PRODUCT_TILES, KERNEL_LOOKUP_PRODUCT_CARRY, K
 KERNEL_PERM_PRODUCT_TILES, KERNEL_PERM_PRODUCT_CARRY, KERNEL_PERM_PRODUCT_SCAN = 13, 14, 15
 KERNEL_NTT_SETUP, KERNEL_NTT_PASS = 16, 17
 KERNEL_QUOTIENT = 18
+KERNEL_OPEN_TILES, KERNEL_OPEN_CARRY, KERNEL_OPEN_SCAN, KERNEL_FOLD = 19, 20, 21, 22
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
 FRESH_OPS = ["add", "sub", "add_mod", "sub_mod", "is_zero", "is_equal_fresh", "is_less_than", "is_less_than_or_equal",
@@ -389,6 +402,14 @@ def lib():
     L.h2r_quotient_sets.argtypes = [pquot, ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.h2r_quotient_sets.restype = u32
     L.h2r_quotient_columns.argtypes = [vp, pquot, ctypes.POINTER(H2RQuotientInputs), u64, vp, u64, vp, vp]
+    popen, pcols = ctypes.POINTER(H2ROpenConfig), ctypes.POINTER(H2ROpenColumn)
+    L.h2r_open_queries.argtypes = [popen, pcols, ctypes.POINTER(u32)]
+    L.h2r_open_queries.restype = u32
+    L.h2r_open_workspace_bytes.argtypes = [popen, pcols, u64]
+    L.h2r_open_workspace_bytes.restype = u64
+    L.h2r_open_eval_columns.argtypes = [vp, popen, pcols, vp, u64, vp, vp, vp, vp]
+    L.h2r_open_witness_columns.argtypes = [vp, popen, pcols, vp, vp, u64, vp, u64, u64, vp, vp, vp, vp]
+    L.h2r_fold_columns.argtypes = [vp, vp, u64, u64, u32, u32, vp, u64, vp, u64, vp, vp]
     L.h2r_field_eval.argtypes = [vp, u32, pu64, pu64, pu64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]

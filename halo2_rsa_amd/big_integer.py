@@ -1388,6 +1388,104 @@ class EvaluationDomain:
         self._keep_q = (ch, advice, extra, perm_z, lookup_a_perm, lookup_s_perm, lookup_z, fixed, sigma, l, h, status)   # alive until the stream has run the kernel
         return h, status
 
+    def fold(self, cols: torch.Tensor, scalars: Sequence[int], out=None):
+        """(folded, status): folded[e][i] = sum_c scalars[e]^c * cols[e][c][i] (h2r_fold_columns), uint8 [batch, n, 32].
+        cols: uint8 [batch, C, n, 32] in coefficient form, last two dimensions contiguous; with the 2^extended_k coefficients of h viewed
+        as [batch, 2^(extended_k - k), 2^k, 32] and scalars = x^n it is the folded h of vanishing::prover::evaluate.  scalars: integers in
+        the chip's representation; status H2R_E_SHAPE where one is not canonical (that circuit is left untouched).  out: (folded, status)
+        to write into (it must overlap no input; a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        if cols.dtype != torch.uint8 or cols.dim() != 4 or cols.shape[-1] != 32:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.fold")
+        assert cols.stride(-1) == 1 and cols.stride(-2) == 32
+        batch, C, n = cols.shape[:3]
+        s = LookupArgument._challenges(self, scalars, batch, cols.device)
+        if out is None:
+            folded = torch.empty((batch, n, 32), dtype=torch.uint8, device=cols.device)
+            status = torch.zeros(batch, dtype=torch.uint8, device=cols.device)
+        else:
+            folded, status = out
+        assert folded.dim() == 3 and folded.shape[1:] == (n, 32) and folded.stride(2) == 1 and folded.stride(1) == 32
+        check(lib().h2r_fold_columns(self.chip._ctx, cols.data_ptr(), cols.stride(0), cols.stride(1), C, n, s.data_ptr(), batch, folded.data_ptr(),
+                                     folded.stride(0), status.data_ptr() if status is not None else None, self.chip._stream()), "h2r_fold_columns")
+        self._keep_fold = (s, cols, folded, status)   # alive until the stream has run the kernel
+        return folded, status
+
+    def _open_columns(self, columns, batch: int, num_points: int, where: str):
+        """The descriptors of `columns` = [(tensor, point_mask)]: tensors uint8 [batch, n, 32] per circuit or [n, 32] for a key column."""
+        if not 0 < len(columns) <= _lib.H2R_OPEN_MAX_COLUMNS:
+            check(_lib.H2R_E_SHAPE, where)
+        n = columns[0][0].shape[-2]
+        cfg = _lib.H2ROpenConfig()
+        cfg.struct_size, cfg.n_coeffs, cfg.num_cols, cfg.num_points = ctypes.sizeof(cfg), n, len(columns), num_points
+        desc = (_lib.H2ROpenColumn * len(columns))()
+        for d, (t, mask) in zip(desc, columns):
+            assert t.dtype == torch.uint8 and t.dim() in (2, 3) and t.shape[-1] == 32 and t.shape[-2] == n and t.stride(-1) == 1 and t.stride(-2) == 32
+            assert t.dim() == 2 or t.shape[0] == batch
+            d.base, d.elem_stride, d.point_mask = t.data_ptr(), t.stride(0) if t.dim() == 3 else 0, int(mask)
+        return cfg, desc
+
+    def _open_points(self, points, dev) -> torch.Tensor:
+        """[batch][num_points] integers in the chip's representation -> int64 [batch, num_points, 4] on the device."""
+        w = np.array([[[(int(z) >> (64 * k)) & (2 ** 64 - 1) for k in range(4)] for z in row] for row in points], dtype=np.uint64)
+        assert w.ndim == 3 and 0 < w.shape[1] <= _lib.H2R_OPEN_MAX_POINTS
+        return torch.from_numpy(w.view(np.int64)).to(dev)
+
+    def open_eval(self, columns, points, out=None):
+        """(evals, status): evals int64 [batch, Q, 4], the evaluations of columns in coefficient form at per-circuit points
+        (h2r_open_eval_columns; halo2's eval_polynomial), in the chip's representation.
+        columns: a list of (tensor, point_mask) in the caller's transcript order, tensors uint8 [batch, n, 32], or [n, 32] for a proving-key
+        column shared by the batch; bit p of point_mask = "queried at points[e][p]".  The Q queries are the set bits in column order, points
+        ascending within a column.  points: [batch][num_points] integers in the chip's representation (the caller forms the rotations of
+        x).  status H2R_E_SHAPE where a point is not canonical (that circuit's evaluations are left untouched).  out: (evals, status) to
+        write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        batch, num_points = len(points), len(points[0])
+        dev = columns[0][0].device
+        cfg, desc = self._open_columns(columns, batch, num_points, "EvaluationDomain.open_eval")
+        Q = int(lib().h2r_open_queries(ctypes.byref(cfg), desc, None))
+        if Q == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_open_queries")
+        pts = self._open_points(points, dev)
+        if out is None:
+            evals = torch.zeros((batch, Q, 4), dtype=torch.int64, device=dev)
+            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        else:
+            evals, status = out
+        assert evals.is_contiguous() and tuple(evals.shape) == (batch, Q, 4)
+        ws = torch.empty(max(int(lib().h2r_open_workspace_bytes(ctypes.byref(cfg), desc, batch)), 16), dtype=torch.uint8, device=dev)
+        check(lib().h2r_open_eval_columns(self.chip._ctx, ctypes.byref(cfg), desc, pts.data_ptr(), batch, evals.data_ptr(),
+                                          status.data_ptr() if status is not None else None, ws.data_ptr(), self.chip._stream()), "h2r_open_eval_columns")
+        self._keep_open = (pts, ws, [t for t, _ in columns], evals, status)   # alive until the stream has run the kernels
+        return evals, status
+
+    def open_witness(self, columns, points, vs: Sequence[int], out=None):
+        """(W, batch_evals, status): the witness polynomials of the GWC multi-open (h2r_open_witness_columns; kate_division of
+        sum_i v^i f_i by X - z per point).  W uint8 [batch, num_points, n, 32]: per point the n coefficients of the
+        quotient (the last one 0), over the columns whose mask names the point, in column order, the powers of v from v^0 for every point; a
+        point that no column queries is left as it was (zeros when the call allocates).  batch_evals int64 [batch, num_points, 4]: the
+        remainders sum v^idx f_c(z).  columns / points as open_eval; vs: per circuit, integers in the chip's representation.  status
+        H2R_E_SHAPE where a point or v is not canonical.  out: (W, batch_evals, status) to write into (W must overlap no column)."""
+        batch, num_points = len(points), len(points[0])
+        dev = columns[0][0].device
+        cfg, desc = self._open_columns(columns, batch, num_points, "EvaluationDomain.open_witness")
+        if int(lib().h2r_open_queries(ctypes.byref(cfg), desc, None)) == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_open_queries")
+        n = cfg.n_coeffs
+        pts, v = self._open_points(points, dev), LookupArgument._challenges(self, vs, batch, dev)
+        if out is None:
+            W = torch.zeros((batch, num_points, n, 32), dtype=torch.uint8, device=dev)
+            be = torch.zeros((batch, num_points, 4), dtype=torch.int64, device=dev)
+            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        else:
+            W, be, status = out
+        assert W.dim() == 4 and tuple(W.shape[1:]) == (num_points, n, 32) and W.stride(3) == 1 and W.stride(2) == 32
+        assert be is None or (be.is_contiguous() and tuple(be.shape) == (batch, num_points, 4))
+        ws = torch.empty(max(int(lib().h2r_open_workspace_bytes(ctypes.byref(cfg), desc, batch)), 16), dtype=torch.uint8, device=dev)
+        check(lib().h2r_open_witness_columns(self.chip._ctx, ctypes.byref(cfg), desc, pts.data_ptr(), v.data_ptr(), batch, W.data_ptr(), W.stride(0),
+                                             W.stride(1), be.data_ptr() if be is not None else None, status.data_ptr() if status is not None else None,
+                                             ws.data_ptr(), self.chip._stream()), "h2r_open_witness_columns")
+        self._keep_witness = (pts, v, ws, [t for t, _ in columns], W, be, status)   # alive until the stream has run the kernels
+        return W, be, status
+
 
 @dataclass
 class FreshResult:

@@ -27,6 +27,7 @@
 #include "h2r_permutation_product.hpp"
 #include "h2r_ntt.hpp"
 #include "h2r_quotient.hpp"
+#include "h2r_open.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4230,7 +4231,7 @@ int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const voi
 
 // ---- the vanishing argument's quotient on the extended domain (h2r_quotient.hpp, h2r_tu_quotient.hip) -------------------------------------
 namespace {
-static_assert(H2R_KERNEL_COUNT == H2R_KERNEL_QUOTIENT + 1, "h2r.h: the launch classes");
+static_assert(H2R_KERNEL_OPEN_TILES == H2R_KERNEL_QUOTIENT + 1, "h2r.h: the launch classes");
 static_assert(H2R_QUOTIENT_MAX_FIXED == QUOT_MAX_FIXED && H2R_LOOKUP_ARGS == QUOT_LOOKUP_ARGS && H2R_PERM_MAX_COLUMNS == QUOT_PERM_MAX_COLUMNS &&
               sizeof(((h2r_quotient_config *)nullptr)->gate_fixed) == QUOT_GATE_FIXED, "h2r.h and the kernel's argument struct");
 h2r_permutation_config quotient_perm_cfg(const h2r_quotient_config *cfg) {
@@ -4365,6 +4366,166 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
         qa.tile0 = (u32)t0;
         ProfScope ps(H2R_KERNEL_QUOTIENT, st, true);
         HIP_TRY(launch_quotient(qa, (u32)std::min<u64>(tiles_per, tiles - t0), (u32)batch, st, ps.a, ps.on ? ps.b : nullptr));
+    }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the openings: fold, evaluations at x, GWC witness polynomials (h2r_open.hpp, h2r_tu_open.hip) -----------------------------------------
+namespace {
+static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_OPEN_SCAN == H2R_KERNEL_OPEN_TILES + 2 &&
+              H2R_KERNEL_COUNT == H2R_KERNEL_FOLD + 1, "h2r.h: the launch classes");
+static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
+// what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
+int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
+    if (cfg->struct_size != sizeof(h2r_open_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->n_coeffs == 0 || cfg->n_coeffs > OPEN_MAX_COEFFS || cfg->num_cols == 0 || cfg->num_cols > OPEN_MAX_COLUMNS ||
+        cfg->num_points == 0 || cfg->num_points > OPEN_MAX_POINTS) return H2R_E_SHAPE;
+    for (u32 c = 0; c < cfg->num_cols; ++c)
+        if (cols[c].point_mask == 0 || (cols[c].point_mask >> cfg->num_points) || cols[c].reserved) return H2R_E_SHAPE;
+    return H2R_OK;
+}
+u32 open_query_count(const h2r_open_config *cfg, const h2r_open_column *cols, u32 per_point[OPEN_MAX_POINTS]) {
+    u32 q = 0;
+    for (u32 p = 0; p < OPEN_MAX_POINTS; ++p) per_point[p] = 0;
+    for (u32 c = 0; c < cfg->num_cols; ++c)
+        for (u32 p = 0; p < cfg->num_points; ++p)
+            if ((cols[c].point_mask >> p) & 1u) { ++per_point[p]; ++q; }
+    return q;
+}
+// the checks the two opening calls share, in order; fills the kernels' arguments.  w_* = 0 / nullptr for the evaluations; others: the
+// witness call's other device ranges (points, v, batch_evals, the workspace), nullptr where there is none
+struct OpenRange { const void *p; u128 bytes; };
+int32_t open_args(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open_column *cols, uint64_t batch, const void *w_out,
+                  uint64_t w_elem_stride, uint64_t w_point_stride, const OpenRange (&others)[4], OpenArgs &oa) {
+    if (cfg->struct_size != sizeof(h2r_open_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->n_coeffs && cfg->n_coeffs <= OPEN_MAX_COEFFS && cfg->num_cols && cfg->num_cols <= OPEN_MAX_COLUMNS)
+        for (u32 c = 0; c < cfg->num_cols; ++c)
+            if (!cols[c].base) return H2R_E_NULL;
+    if (const int32_t rc = open_cfg_status(cfg, cols)) return rc;
+    const u64 col = 32ull * cfg->n_coeffs;
+    for (u32 c = 0; c < cfg->num_cols; ++c) {
+        if ((reinterpret_cast<u64>(cols[c].base) | cols[c].elem_stride) & 15) return H2R_E_SHAPE;
+        if (cols[c].elem_stride && cols[c].elem_stride < col) return H2R_E_SHAPE;
+    }
+    if (w_out) {
+        if ((reinterpret_cast<u64>(w_out) | w_elem_stride | w_point_stride) & 15) return H2R_E_SHAPE;
+        if (!ntt_columns_disjoint(col, w_elem_stride, w_point_stride, cfg->num_points, batch)) return H2R_E_SHAPE;
+        // the scans write W[i - 1] while other workgroups still read the columns: W may overlap no input
+        const u128 w0 = reinterpret_cast<u64>(w_out), w1 = w0 + ntt_extent(col, w_elem_stride, w_point_stride, cfg->num_points, batch);
+        for (u32 c = 0; c < cfg->num_cols; ++c) {
+            const u128 c0 = reinterpret_cast<u64>(cols[c].base), c1 = c0 + (batch ? (u128)(batch - 1) * cols[c].elem_stride + col : 0);
+            if (c0 < w1 && w0 < c1) return H2R_E_SHAPE;
+        }
+        for (const OpenRange &r : others) {   // ... nor the points, v, batch_evals or the workspace
+            const u128 r0 = reinterpret_cast<u64>(r.p), r1 = r0 + (batch ? r.bytes : 0);
+            if (r.p && r0 < w1 && w0 < r1) return H2R_E_SHAPE;
+        }
+    }
+    if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
+    std::memset(static_cast<void *>(&oa), 0, sizeof oa);
+    u32 per_point[OPEN_MAX_POINTS], q = 0;
+    oa.n_queries = open_query_count(cfg, cols, per_point);
+    for (u32 c = 0; c < cfg->num_cols; ++c) {
+        oa.cols[c] = OpenCol{static_cast<const u8 *>(cols[c].base), cols[c].elem_stride, cols[c].point_mask, q};
+        for (u32 p = 0; p < cfg->num_points; ++p)
+            if ((cols[c].point_mask >> p) & 1u) oa.qpoint[q++] = (u8)p;
+    }
+    for (u32 p = 0; p < OPEN_MAX_POINTS; ++p) oa.point_cols[p] = (u8)per_point[p];
+    oa.n_coeffs = cfg->n_coeffs; oa.n_tiles = open_tiles_of(cfg->n_coeffs); oa.num_cols = cfg->num_cols; oa.num_points = cfg->num_points;
+    oa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;
+    oa.slot_bytes = open_slot_bytes(cfg->n_coeffs, std::max<u32>(oa.n_queries, cfg->num_points));
+    oa.f = ctx->fc;
+    return H2R_OK;
+}
+// phases [0, n_phases) over the circuits, sliced below the 2^32 global size and the 65,535 of a grid's z
+int32_t open_launch(const h2r_ctx *ctx, OpenArgs &oa, u32 n_phases, uint64_t batch, void *workspace, hipStream_t st) {
+    const u64 max_blocks = ((1ull << 32) - 1) / 256, per_elem = (u64)oa.n_tiles * (oa.witness ? oa.num_points : 1u);
+    const u64 elems_per = std::min<u64>({batch, 65535, max_blocks / per_elem});
+    if (!elems_per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    oa.ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    for (u32 phase = 0; phase < n_phases; ++phase)
+        for (u64 e0 = 0; e0 < batch; e0 += elems_per) {
+            oa.elem0 = (u32)e0;
+            ProfScope ps(H2R_KERNEL_OPEN_TILES + phase, st, true);
+            HIP_TRY(launch_open(phase, oa, (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
+        }
+    return H2R_OK;
+}
+}  // namespace
+
+uint32_t h2r_open_queries(const h2r_open_config *cfg, const h2r_open_column *cols, uint32_t per_point[4]) try {
+    if (!cfg || !cols || open_cfg_status(cfg, cols) != H2R_OK) return 0;
+    u32 pp[OPEN_MAX_POINTS];
+    const u32 q = open_query_count(cfg, cols, pp);
+    if (per_point) for (u32 p = 0; p < OPEN_MAX_POINTS; ++p) per_point[p] = pp[p];
+    return q;
+} H2R_CATCH_ZERO
+
+uint64_t h2r_open_workspace_bytes(const h2r_open_config *cfg, const h2r_open_column *cols, uint64_t batch) try {
+    if (!cfg || !cols || open_cfg_status(cfg, cols) != H2R_OK || batch > 65535) return 0;
+    u32 pp[OPEN_MAX_POINTS];
+    const u32 q = open_query_count(cfg, cols, pp);
+    return 256 + batch * open_slot_bytes(cfg->n_coeffs, std::max<u32>(q, cfg->num_points));
+} H2R_CATCH_ZERO
+
+int32_t h2r_open_eval_columns(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open_column *cols, const uint64_t *points,
+                              uint64_t batch, uint64_t *evals, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !cols || !points || !evals || !workspace) return H2R_E_NULL;
+    OpenArgs oa;
+    const OpenRange none[4] = {};
+    if (const int32_t rc = open_args(ctx, cfg, cols, batch, nullptr, 0, 0, none, oa)) return rc;
+    if (batch == 0) return H2R_OK;
+    oa.points = points; oa.evals = evals; oa.status = status;
+    return open_launch(ctx, oa, 2, batch, workspace, static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_open_witness_columns(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open_column *cols, const uint64_t *points,
+                                 const uint64_t *v, uint64_t batch, void *w_out, uint64_t w_elem_stride, uint64_t w_point_stride,
+                                 uint64_t *batch_evals, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !cols || !points || !v || !w_out || !workspace) return H2R_E_NULL;
+    OpenArgs oa;
+    // (the sizes use num_points as given: at most 4 where the configuration is one the shared checks let through to the overlap test)
+    const u64 np = cfg->num_points <= OPEN_MAX_POINTS ? cfg->num_points : 0;
+    const OpenRange others[4] = {{points, (u128)batch * np * 32}, {v, (u128)batch * 32}, {batch_evals, (u128)batch * np * 32},
+                                 {workspace, h2r_open_workspace_bytes(cfg, cols, batch)}};
+    if (const int32_t rc = open_args(ctx, cfg, cols, batch, w_out, w_elem_stride, w_point_stride, others, oa)) return rc;
+    if (batch == 0) return H2R_OK;
+    oa.points = points; oa.v = v; oa.evals = batch_evals; oa.status = status; oa.witness = 1;
+    oa.w = static_cast<u8 *>(w_out); oa.w_elem_stride = w_elem_stride; oa.w_point_stride = w_point_stride;
+    return open_launch(ctx, oa, 3, batch, workspace, static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+int32_t h2r_fold_columns(const h2r_ctx *ctx, const void *in, uint64_t in_elem_stride, uint64_t in_col_stride, uint32_t num_cols,
+                         uint32_t n_coeffs, const uint64_t *s, uint64_t batch, void *out, uint64_t out_elem_stride, uint8_t *status,
+                         h2r_stream_t stream) try {
+    if (!ctx || !in || !s || !out) return H2R_E_NULL;
+    if (n_coeffs == 0 || n_coeffs > OPEN_MAX_COEFFS || num_cols == 0 || num_cols > OPEN_MAX_COLUMNS) return H2R_E_SHAPE;
+    const u64 col = 32ull * n_coeffs;
+    if ((reinterpret_cast<u64>(in) | in_elem_stride | in_col_stride | reinterpret_cast<u64>(out) | out_elem_stride) & 15) return H2R_E_SHAPE;
+    if (!ntt_columns_disjoint(col, in_elem_stride, in_col_stride, num_cols, batch) || out_elem_stride < col) return H2R_E_SHAPE;
+    {
+        const u128 i0 = reinterpret_cast<u64>(in), o0 = reinterpret_cast<u64>(out);
+        const u128 i1 = i0 + ntt_extent(col, in_elem_stride, in_col_stride, num_cols, batch), o1 = o0 + ntt_extent(col, out_elem_stride, col, 1, batch);
+        if (i0 < o1 && o0 < i1) return H2R_E_SHAPE;
+    }
+    if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    FoldArgs fa;
+    std::memset(static_cast<void *>(&fa), 0, sizeof fa);
+    fa.in = static_cast<const u8 *>(in); fa.in_elem_stride = in_elem_stride; fa.in_col_stride = in_col_stride;
+    fa.s = s; fa.status = status; fa.out = static_cast<u8 *>(out); fa.out_elem_stride = out_elem_stride;
+    fa.n_coeffs = n_coeffs; fa.num_cols = num_cols; fa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u; fa.f = ctx->fc;
+    // launches below the 2^32 global size: slices of tiles (a grid's x holds the circuits, at most 65,535)
+    const u64 tiles = (n_coeffs + FOLD_TILE - 1) / FOLD_TILE, max_blocks = ((1ull << 32) - 1) / 256;
+    const u64 tiles_per = std::min<u64>({tiles, 65535, max_blocks / batch});
+    if (!tiles_per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (u64 t0 = 0; t0 < tiles; t0 += tiles_per) {
+        fa.tile0 = (u32)t0;
+        ProfScope ps(H2R_KERNEL_FOLD, st, true);
+        HIP_TRY(launch_fold(fa, (u32)std::min<u64>(tiles_per, tiles - t0), (u32)batch, st, ps.a, ps.on ? ps.b : nullptr));
     }
     return H2R_OK;
 } H2R_CATCH_STATUS

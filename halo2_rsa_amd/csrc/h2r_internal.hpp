@@ -11,6 +11,7 @@
 //   h2r_tu_permutation_product.hip   the permutation argument's grand product (h2r_permutation_product.hpp)
 //   h2r_tu_ntt.hip     the evaluation domain's transforms (h2r_ntt.hpp)
 //   h2r_tu_quotient.hip   the vanishing argument's quotient on the extended domain (h2r_quotient.hpp)
+//   h2r_tu_open.hip    the openings: evaluations at x, GWC witness polynomials, the fold of h's pieces (h2r_open.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -122,5 +123,11 @@ hipError_t launch_ntt_pass(const NttArgs &a, u32 num_cols, u32 num_elems, hipStr
 // h2r_tu_quotient.hip (argument struct: h2r_quotient.hpp).  The tiles [a.tile0, a.tile0 + num_tiles) of num_elems circuits.
 struct QuotientArgs;
 hipError_t launch_quotient(const QuotientArgs &a, u32 num_tiles, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_open.hip (argument structs: h2r_open.hpp).  phase 0 = the tiles' sums, 1 = the carries and the evaluations, 2 = the scans that write W;
+// the circuits [a.elem0, a.elem0 + num_elems).  The fold: the tiles [a.tile0, a.tile0 + num_tiles) of num_elems circuits.
+struct OpenArgs;
+struct FoldArgs;
+hipError_t launch_open(u32 phase, const OpenArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_fold(const FoldArgs &a, u32 num_tiles, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

@@ -976,6 +976,59 @@ typedef struct h2r_quotient_config {
 uint32_t h2r_quotient_sets(const h2r_quotient_config *cfg, uint32_t *circuit_columns, uint32_t *key_columns);
 int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg, const h2r_quotient_inputs *in, uint64_t batch, void *h_out,
                              uint64_t h_elem_stride, uint8_t *status, h2r_stream_t stream);
+/* ---- the openings: the fold of h's pieces, the evaluations at x and its rotations, the GWC witness polynomials ----
+ * THIRD-PARTY behaviour (halo2 vanishing::prover::evaluate, poly::eval_polynomial and poly::kzg::multiopen::ProverGWC with kate_division,
+ * not in the reference tree), restated in DESIGN.md section 2h; parity is pinned against a Python restatement (tests/opening_ref.py,
+ * tests/test_open_gpu.py), not against upstream.  What lies between "h exists" and "the proof is written" except the commitments (MSMs:
+ * curve arithmetic, out of scope).  All arithmetic mod the ctx's p.  A column is n_coeffs field elements of 32 bytes in COEFFICIENT form, in
+ * the ctx's representation (for these planar vectors only H2R_ADVICE_MONTGOMERY matters), 1 <= n_coeffs <= 2^24, no power of two needed.
+ *  - A call names its columns by a host array of num_cols descriptors: column c of circuit e lies at base + e * elem_stride; elem_stride = 0
+ *    is a proving-key column shared by every circuit.  Bit p of point_mask = "column c is queried at point p", p < num_points.  The points
+ *    are points[batch][num_points][4] uint64 on the device, per circuit, and the caller's: the library forms no rotation of x.  The QUERY
+ *    LIST is the set bits in column order, points ascending within a column; Q = their number.  The library never names advice, fixed,
+ *    permuted or product columns: the descriptor order is the caller's transcript order.
+ *  - h2r_open_eval_columns: evals[e][q] = sum_i col_q[e][i] * z_{e,p(q)}^i for every query q = (column, point): [batch][Q][4] uint64 on the
+ *    device, the ctx's representation.  Two launches (per tile of 1,024 coefficients, then one wave per query); a column is read once for
+ *    all of its points.
+ *  - h2r_open_witness_columns: for circuit e and point p let Q_p be the columns whose mask has bit p, in column order, idx(c) the position
+ *    of c within Q_p (the powers of v start at v^0 = 1 for every point, as upstream's zip(powers(v)) per point set does), and
+ *    g(X) = sum_{c in Q_p} v_e^idx(c) * f_c(X).  Then W[e][p][i - 1] = g[i] + z * W[e][p][i] for i = n_coeffs - 1 .. 1 and
+ *    W[e][p][n_coeffs - 1] = 0: the synthetic division of g by (X - z), high to low, exactly kate_division.  The remainder g[0] + z * W[0] =
+ *    sum v^idx * f_c(z) goes to batch_evals[e][p] ([batch][num_points][4], nullable; the entry of a point that no column queries is left
+ *    alone).  Upstream subtracts the batched evaluation before it divides; that only zeroes the remainder, so the call takes no evaluations.
+ *    v: [batch][4] on the device.  W of (e, p): n_coeffs elements at w_out + e * w_elem_stride + p * w_point_stride; a point that no column
+ *    queries gets nothing written.  Three launches: the tiles' sums, the carries per point, the scans that write W.
+ *  - h2r_fold_columns: out[e][i] = sum_{c < num_cols} s_e^c * in[e][c][i], in[e][c] at in + e * in_elem_stride + c * in_col_stride, s:
+ *    [batch][4] on the device.  Pointwise, one launch, no workspace.  With s = x^n over the n-coefficient pieces of h (the 2^extended_k
+ *    coefficients viewed as num_cols columns at in_col_stride = n * 32) it is vanishing::prover::evaluate's folded h, an ordinary column for
+ *    the two calls above.
+ *  - The calls enqueue on `stream` and never synchronise; no workgroup waits for another; launches are sliced internally below the 2^32
+ *    global size.  workspace: h2r_open_workspace_bytes(cfg, cols, batch) bytes on the device (enough for either call), private to the call
+ *    until the stream has run it.  h2r_open_queries returns Q and (nullable) the number of columns per point; both helpers are host
+ *    functions that need no device and no ctx, and return 0 for a configuration or a mask the calls would refuse.
+ *  - status (nullable, [batch]) is never cleared: circuits whose byte is nonzero on entry are skipped; H2R_E_SHAPE where one of the circuit's
+ *    num_points points, its v or its s is >= p (nothing is written for that circuit).
+ *  - H2R_E_NULL for a NULL required pointer (status and batch_evals are optional); H2R_E_UNSUPPORTED for another struct_size, a host-only ctx
+ *    (that one after every other check) or more than 65,535 circuits; H2R_E_SHAPE for n_coeffs = 0 or > 2^24, num_cols = 0 or >
+ *    H2R_OPEN_MAX_COLUMNS, num_points = 0 or > H2R_OPEN_MAX_POINTS, a point_mask of 0 or with bits >= num_points, a nonzero `reserved`, a
+ *    column base, W / fold pointer or a stride that is not 16-byte aligned, a nonzero elem_stride (a W or fold stride) smaller than the
+ *    column, fold columns or W ranges that overlap each other (either stride covers the other's extent, as for h2r_ntt_columns; w_point_stride
+ *    is looked at for every p < num_points), and W overlapping any input -- a column, the points, v, batch_evals or the workspace -- or the
+ *    fold's out overlapping its input columns.  batch = 0 returns H2R_OK with no launch. */
+#define H2R_OPEN_MAX_COLUMNS 64
+#define H2R_OPEN_MAX_POINTS  4      /* x, omega x, omega^-1 x, omega^-(blinding_factors+1) x: what this constraint system queries */
+typedef struct h2r_open_column { const void *base; uint64_t elem_stride; uint32_t point_mask; uint32_t reserved; } h2r_open_column;
+typedef struct h2r_open_config { uint32_t struct_size, n_coeffs, num_cols, num_points; } h2r_open_config;
+uint32_t h2r_open_queries(const h2r_open_config *cfg, const h2r_open_column *cols, uint32_t per_point[4]);
+uint64_t h2r_open_workspace_bytes(const h2r_open_config *cfg, const h2r_open_column *cols, uint64_t batch);
+int32_t h2r_open_eval_columns(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open_column *cols, const uint64_t *points,
+                              uint64_t batch, uint64_t *evals, uint8_t *status, void *workspace, h2r_stream_t stream);
+int32_t h2r_open_witness_columns(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open_column *cols, const uint64_t *points,
+                                 const uint64_t *v, uint64_t batch, void *w_out, uint64_t w_elem_stride, uint64_t w_point_stride,
+                                 uint64_t *batch_evals, uint8_t *status, void *workspace, h2r_stream_t stream);
+int32_t h2r_fold_columns(const h2r_ctx *ctx, const void *in, uint64_t in_elem_stride, uint64_t in_col_stride, uint32_t num_cols,
+                         uint32_t n_coeffs, const uint64_t *s, uint64_t batch, void *out, uint64_t out_elem_stride, uint8_t *status,
+                         h2r_stream_t stream);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1272,7 +1325,9 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_PERM_PRODUCT_TILES = 13, H2R_KERNEL_PERM_PRODUCT_CARRY = 14, H2R_KERNEL_PERM_PRODUCT_SCAN = 15 /* the permutation argument's grand product, likewise */,
        H2R_KERNEL_NTT_SETUP = 16 /* ntt_setup_kernel: the twiddle tables of one call */, H2R_KERNEL_NTT_PASS = 17 /* ntt_pass_kernel: one launch per pass */,
        H2R_KERNEL_QUOTIENT = 18 /* quotient_kernel: h on the extended domain */,
-       H2R_KERNEL_COUNT = 19 };
+       H2R_KERNEL_OPEN_TILES = 19, H2R_KERNEL_OPEN_CARRY = 20, H2R_KERNEL_OPEN_SCAN = 21 /* the openings' launches: evaluations (two), witness polynomials (three) */,
+       H2R_KERNEL_FOLD = 22 /* fold_kernel */,
+       H2R_KERNEL_COUNT = 23 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
