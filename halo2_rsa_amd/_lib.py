@@ -43,7 +43,7 @@ class H2RPipelineInfo(ctypes.Structure):
                 ("three_queues", ctypes.c_uint32), ("probe_ms", ctypes.c_float), ("probe_span_ms", ctypes.c_float)]
 
 
-H2R_PIPE_ONE_LAUNCH_STEP, H2R_PIPE_TWO_QUEUE, H2R_PIPE_SIDE_STREAM = 0, 1, 2
+H2R_PIPE_ONE_LAUNCH_STEP, H2R_PIPE_TWO_QUEUE, H2R_PIPE_SIDE_STREAM, H2R_PIPE_AUTO = 0, 1, 2, 3
 
 
 class H2RLayout(ctypes.Structure):
@@ -163,7 +163,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_key_table_bytes", "h2r_key_table_build", "h2r_key_table_expand",
            "h2r_mul_mod_batch", "h2r_square_mod_batch", "h2r_pow_mod_fixed_exp_batch", "h2r_pow_mod_batch",
            "h2r_modpow_public_key_batch", "h2r_modpow_public_key_var_batch", "h2r_pipeline_create", "h2r_pipeline_create_ex", "h2r_pipeline_destroy",
-           "h2r_pipeline_modpow_public_key", "h2r_pipeline_modpow_public_key_advice", "h2r_pipeline_modpow_public_key_var", "h2r_pipeline_verify_pkcs1v15", "h2r_pipeline_join", "h2r_pipeline_info", "h2r_pipeline_call_plan", "h2r_exp_segment_plan", "h2r_arena_create", "h2r_arena_create_ex", "h2r_image_arena_create", "h2r_arena_region", "h2r_arena_region_bytes", "h2r_arena_region_ms", "h2r_arena_measurements", "h2r_arena_destroy", "h2r_verify_layout_fixed", "h2r_verify_pkcs1v15_batch",
+           "h2r_pipeline_modpow_public_key", "h2r_pipeline_modpow_public_key_advice", "h2r_pipeline_modpow_public_key_var", "h2r_pipeline_verify_pkcs1v15", "h2r_pipeline_join", "h2r_pipeline_info", "h2r_pipeline_set_form", "h2r_pipeline_call_plan", "h2r_exp_segment_plan", "h2r_arena_create", "h2r_arena_create_ex", "h2r_image_arena_create", "h2r_arena_region", "h2r_arena_region_bytes", "h2r_arena_region_ms", "h2r_arena_measurements", "h2r_arena_restore_constants", "h2r_arena_destroy", "h2r_verify_layout_fixed", "h2r_verify_pkcs1v15_batch",
            "h2r_verify_trace_flatten", "h2r_fresh_op_layout", "h2r_fresh_op_batch", "h2r_fresh_op_flatten",
            "h2r_mul_stream_bytes", "h2r_is_equal_muled_stream_bytes", "h2r_refresh_stream_bytes", "h2r_mul_batch",
            "h2r_mul_trace_flatten", "h2r_is_equal_muled_batch", "h2r_is_equal_muled_flatten", "h2r_refresh_batch",
@@ -280,6 +280,8 @@ def lib():
     L.h2r_arena_measurements.argtypes = [vp, ctypes.POINTER(ctypes.c_double), u32]
     L.h2r_arena_measurements.restype = u32
     L.h2r_arena_destroy.argtypes = [vp]
+    L.h2r_arena_restore_constants.argtypes = [vp, u32, vp]
+    L.h2r_pipeline_set_form.argtypes = [vp, u32]
     L.h2r_arena_destroy.restype = None
     L.h2r_exp_segment_plan.argtypes = [vp, ctypes.c_uint64, ctypes.c_char_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
                                        ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]

@@ -847,11 +847,17 @@ class Pipeline:
     """h2r_pipeline: batch k+1's off-circuit chain overlaps batch k's record emission (side HIP streams).
     Callers rotate through `depth` buffer sets and call join() before reading the last traces."""
 
-    def __init__(self, chip: BigIntChip, depth: int = 2, side_streams: int = 1):
+    def __init__(self, chip: BigIntChip, depth: int = 2, side_streams: int = 1, form: Optional[int] = None):
         self.chip = chip
         self.depth = depth
         self._p = ctypes.c_void_p()
         check(lib().h2r_pipeline_create_ex(chip._ctx, depth, side_streams, ctypes.byref(self._p)), "h2r_pipeline_create_ex")
+        if form is not None:
+            self.set_form(form)
+
+    def set_form(self, form: int):
+        """h2r_pipeline_set_form: H2R_PIPE_TWO_QUEUE / H2R_PIPE_ONE_LAUNCH_STEP instead of the queue probe's verdict, H2R_PIPE_AUTO gives it back."""
+        check(lib().h2r_pipeline_set_form(self._p, form), "h2r_pipeline_set_form")
 
     def modpow_public_key(self, x: AssignedInteger, e: int, n: AssignedInteger, trace_buf, workspace, out, status, in_field_buf=None):
         """in_field_buf (optional): batch * in_field_layout()[0] bytes for the assert_in_field witness."""
@@ -992,7 +998,9 @@ class TraceArena:
     """h2r_arena: `regions` trace regions of batch * elem_stride bytes each, the fastest of `candidates` mapped and measured
     ones (where a trace buffer lies physically decides how fast the record kernel writes it).
     .regions: uint8 tensors over the kept regions, fastest first (views of the arena's memory: drop them before close());
-    .region_ms / .measurements_ms: record-kernel times."""
+    .region_ms / .measurements_ms: record-kernel times.
+    The constant planes of the regions' record slots belong to the arena (include/h2r.h): matching calls do not store them again, and
+    whoever overwrites them calls restore(i) before the next matching call."""
 
     class _Raw:
         def __init__(self, ptr, n):
@@ -1033,6 +1041,10 @@ class TraceArena:
     def for_pow(cls, chip: BigIntChip, e: int, batch: int, regions: int = 2, candidates: int = 16) -> "TraceArena":
         pl = chip.pow_fixed_layout(e)
         return cls(chip, pl.elem_stride, pl.off_records, pl.num_mul_mods, batch, regions, candidates)
+
+    def restore(self, i: int):
+        """h2r_arena_restore_constants: rewrite the constant planes of every record slot of kept region i, on the current stream."""
+        check(lib().h2r_arena_restore_constants(self._a, i, self.chip._stream()), "h2r_arena_restore_constants")
 
     def close(self):
         if self._a:

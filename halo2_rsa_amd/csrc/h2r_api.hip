@@ -32,6 +32,7 @@
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
 #include "h2r_check.hpp"
+#include "h2r_arena_match.hpp"
 
 using namespace h2r;
 
@@ -224,6 +225,18 @@ struct ScratchGuard {  // stream-ordered scratch when the caller passes workspac
     void *p = nullptr; hipStream_t st = nullptr; bool owned = false;
     ~ScratchGuard() { if (owned && p) (void)hipFreeAsync(p, st); }
 };
+
+// The record slots of every live trace arena's kept regions (h2r_arena_match.hpp): their constant planes are in place.
+h2r_arena_match::Registry g_arena_slots;
+// Does every record of the launch `ta` describes (`elems` elements from ta.trace on) lie on such a slot?
+bool on_arena_slots(const h2r_ctx *c, const TraceArgs &ta, u64 elems) {
+    if (knobs().keep_const == 0 || ta.mode != TRACE_FULL) return false;
+    h2r_arena_match::Launch l;
+    l.device = c->params.device; l.limb_width = c->layout.limb_width; l.num_limbs = c->L;
+    l.trace = reinterpret_cast<u64>(ta.trace); l.elem_stride = ta.elem_stride; l.off_records = ta.off_records;
+    l.t_lo = ta.t_lo; l.T = ta.T; l.elems = elems;
+    return g_arena_slots.match(l);
+}
 
 void fill_trace_args(const h2r_ctx *c, TraceArgs &ta) {
     std::memset(&ta, 0, sizeof ta);
@@ -472,6 +485,7 @@ int32_t run_path(const h2r_ctx *c, const PowCall &call, const PowIssue &how) {
         ta.status = status; ta.n_items = batch * T; ta.T = T;
         if (how.seg) { ta.n_items = batch * how.seg->t_cnt; ta.T = how.seg->t_cnt; ta.t_lo = how.seg->t_lo; ta.T_ops = T; }   // this segment's mul_mods of every element
         ta.trace = static_cast<u8 *>(trace); ta.elem_stride = call.elem_stride; ta.off_records = call.off_records;
+        ta.keep_const = on_arena_slots(c, ta, batch) ? 1u : 0u;   // an arena region keeps its constant planes (h2r.h, trace arena)
         if (how.args_only) { how.args_only->ta = ta; how.args_only->has_trace = true; return H2R_OK; }
         hipStream_t ts = st;
         // LDS share of the record kernel's workgroups (the occupancy lever on this hardware: an LDS request the kernel never
@@ -844,6 +858,7 @@ struct h2r_pipeline {
     // cannot read the assignment, so it measures it once per caller stream: three 150 us one-wave spinners (pipeline_three_queues).
     std::map<hipStream_t, int> queue_probe;   // 1: three queues, 0: some pair shares one
     float probe_ms = 0.f, probe_span_ms = 0.f; // the last probe: host wall time, device-clock span
+    u32 form = H2R_PIPE_AUTO;                  // h2r_pipeline_set_form: a forced verdict instead of the probe's
 };
 
 // ---- multi-GPU: RCCL behind the C ABI --------------------------------------------------------------------------------------
@@ -1006,6 +1021,13 @@ struct h2r_arena {
     u64 region_bytes = 0;
     std::vector<Region> kept;          // fastest first
     std::vector<float> measured;       // every candidate, in allocation order
+    // A trace arena (h2r_arena_create): the geometry it was created for and a copy of the ctx's constant record.  The record slots of
+    // the kept regions hold the constant planes from the look on and are registered in g_arena_slots until the arena is destroyed.
+    bool trace_slots = false;
+    u32 limb_width = 0, num_limbs = 0, records_per_elem = 0;
+    u64 elem_stride = 0, first_record_off = 0, record_stride = 0, batch = 0;
+    u8 *const_rec = nullptr;
+    u64 const_off[7] = {}; u32 const_bytes[7] = {};   // the constant planes of a record: offset, bytes (all 2L entries)
 };
 
 namespace {
@@ -1025,6 +1047,19 @@ __global__ __launch_bounds__(256) void arena_fill_kernel(u8 *p, u64 bytes) {
     u8 *q = p + b * per_block;
     const u64 n = bytes - b * per_block < per_block ? bytes - b * per_block : per_block;
     for (u64 o = (u64)threadIdx.x * 16; o + 16 <= n; o += 4096) st16(q + o, 0x0123456789abcdefull ^ o, b);
+}
+// h2r_arena_restore_constants: the constant planes of every record slot of a region, from the constant record (4 bytes per thread and step;
+// every plane starts on a 16-byte boundary of the record and is a whole number of words)
+struct ArenaConstPlanes { u64 off[7]; u32 bytes[7]; };
+__global__ __launch_bounds__(256) void arena_restore_kernel(u8 *base, u64 elem_stride, u64 off_records, u64 record_stride, u32 T, u64 n_records,
+                                                            const u8 *cr, ArenaConstPlanes pl) {
+    for (u64 k = blockIdx.x; k < n_records; k += gridDim.x) {
+        const u64 elem = k / T, t = k - elem * T;
+        u8 *rec = base + elem * elem_stride + off_records + t * record_stride;
+        for (int p = 0; p < 7; ++p)
+            for (u32 o = threadIdx.x * 4; o < pl.bytes[p]; o += 256 * 4)
+                *reinterpret_cast<u32 *>(rec + pl.off[p] + o) = *reinterpret_cast<const u32 *>(cr + pl.off[p] + o);
+    }
 }
 using ArenaMeasure = std::function<int32_t(void *va, hipStream_t st, hipEvent_t ea, hipEvent_t eb, float *ms)>;
 int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes, hipStream_t st,
@@ -1065,6 +1100,7 @@ int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint
         acc.location = prop.location; acc.flags = hipMemAccessFlagsProtReadWrite;
         if (!hip_ok(hipMemSetAccess(r.va, r.mapped, &acc, 1), "hipMemSetAccess")) return H2R_E_HIP;
         if (!hip_ok(hipMemsetAsync(r.va, 0, region_bytes, st), "hipMemsetAsync")) return H2R_E_HIP;
+        if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) return H2R_E_HIP;   // (complete before the look's launches write the region)
         return measure(r.va, st, ea, eb, &r.ms);
     };
     std::vector<h2r_arena::Region> cands;
@@ -1196,6 +1232,8 @@ int32_t h2r_arena_create_ex(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t f
         if (knobs().trace_dyn_lds < 0 && lo.limb_width == 64 && ctx->L <= 32) ta.residency = 1;   // the kernel's stand-alone launch shape
         float sum = 0.f;
         for (int rep = 0; rep < 3; ++rep) {
+            // the first launch writes every plane of every record slot; the timed ones are what production runs on a kept region
+            ta.keep_const = (rep && knobs().keep_const != 0) ? 1u : 0u;
             if (!hip_ok(launch_trace(ctx, ta, s2, ea, eb), "launch_trace")) return H2R_E_HIP;
             if (!hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
             float ms = 0.f;
@@ -1205,7 +1243,53 @@ int32_t h2r_arena_create_ex(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t f
         *ms_out = sum / 2.f;
         return H2R_OK;
     };
-    return arena_build(ctx, batch * elem_stride, regions, candidates, max_look_bytes, st, measure, false, out);
+    const int32_t rc = arena_build(ctx, batch * elem_stride, regions, candidates, max_look_bytes, st, measure, false, out);
+    if (rc) return rc;
+    // the kept regions' record slots hold their constant planes: remember the geometry and register them
+    h2r_arena *a = *out;
+    a->limb_width = lo.limb_width; a->num_limbs = ctx->L; a->records_per_elem = records_per_elem;
+    a->elem_stride = elem_stride; a->first_record_off = first_record_off; a->record_stride = lo.record_stride; a->batch = batch;
+    const int planes[7] = {H2R_PL_ACCX_LO, H2R_PL_ACCX_HI, H2R_PL_QACC, H2R_PL_MODACC, H2R_PL_NQ2_LO, H2R_PL_NQ2_HI, H2R_PL_AMNQ2};
+    const u32 per_col[7] = {16, lo.limb_width == 64 ? 8u : 0u, lo.carry_bytes, lo.limb_bytes, 16, lo.limb_width == 64 ? 8u : 0u, lo.limb_bytes};
+    for (int k = 0; k < 7; ++k) { a->const_off[k] = lo.plane_off[planes[k]]; a->const_bytes[k] = per_col[k] * 2 * ctx->L; }
+    if (!hip_ok(hipMalloc(reinterpret_cast<void **>(&a->const_rec), lo.record_stride), "hipMalloc(arena constant record)") ||
+        !hip_ok(hipMemcpy(a->const_rec, ctx->const_rec_dev, lo.record_stride, hipMemcpyDeviceToDevice), "hipMemcpy(arena constant record)")) {
+        h2r_arena_destroy(a); *out = nullptr;
+        return H2R_E_HIP;
+    }
+    a->trace_slots = true;
+    // The constant planes are valid FROM CREATION by construction, not by what the look left behind: on 50 GB regions the look's first,
+    // all-planes launch was seen to lose most of its constant planes (zeros again afterwards -- the candidate's hipMemsetAsync is still
+    // settling next to it; the parent's later launches rewrote them, the flagged ones do not).  So every kept region gets them once more.
+    for (u32 k = 0; k < a->kept.size(); ++k) {
+        const int32_t rr = h2r_arena_restore_constants(a, k, stream);
+        if (rr) { h2r_arena_destroy(a); *out = nullptr; return rr; }
+    }
+    if (!hip_ok(hipStreamSynchronize(st), "hipStreamSynchronize")) { h2r_arena_destroy(a); *out = nullptr; return H2R_E_HIP; }
+    for (const h2r_arena::Region &r : a->kept) {
+        h2r_arena_match::Region m;
+        m.device = a->device; m.limb_width = a->limb_width; m.num_limbs = a->num_limbs;
+        m.base = reinterpret_cast<u64>(r.va); m.bytes = a->region_bytes;
+        m.elem_stride = elem_stride; m.first_record_off = first_record_off; m.records_per_elem = records_per_elem; m.batch = batch;
+        m.owner = a;
+        g_arena_slots.add(m);
+    }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_arena_restore_constants(h2r_arena *a, uint32_t region, h2r_stream_t stream) try {
+    if (!a) return H2R_E_NULL;
+    if (!a->trace_slots) return H2R_E_UNSUPPORTED;   // an image arena has no record slots
+    if (region >= a->kept.size()) return H2R_E_SHAPE;
+    H2R_ON_DEVICE(a->device);
+    ArenaConstPlanes pl;
+    for (int k = 0; k < 7; ++k) { pl.off[k] = a->const_off[k]; pl.bytes[k] = a->const_bytes[k]; }
+    const u64 n_records = a->batch * a->records_per_elem;   // < 2^32 (h2r_arena_create_ex)
+    const unsigned grid = (unsigned)std::min<u64>(n_records, 1u << 16);
+    hipLaunchKernelGGL(arena_restore_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<u8 *>(a->kept[region].va),
+                       a->elem_stride, a->first_record_off, a->record_stride, a->records_per_elem, n_records, a->const_rec, pl);
+    HIP_TRY(hipGetLastError());
+    return H2R_OK;
 } H2R_CATCH_STATUS
 
 // The same look for ANY large output the kernels stream into -- advice images, the lookup argument's A' / S' columns: where such a
@@ -1246,10 +1330,12 @@ uint32_t h2r_arena_measurements(const h2r_arena *a, double *ms_out, uint32_t cap
 } H2R_CATCH_ZERO
 void h2r_arena_destroy(h2r_arena *a) try {
     if (!a) return;
+    g_arena_slots.unregister_owner(a);   // before any memory goes back: no later launch may take an address of it for a record slot
     {
         DeviceGuard dg(a->device);
         (void)hipDeviceSynchronize();
         for (auto &r : a->kept) arena_free_region(r);
+        if (a->const_rec) (void)hipFree(a->const_rec);
     }
     delete a;
 } H2R_CATCH_VOID
@@ -1318,6 +1404,7 @@ int32_t pipeline_flush(h2r_pipeline *p, hipStream_t st) {
 bool pipeline_three_queues(h2r_pipeline *p, hipStream_t st, bool force = false) {
     if (p->aux[0] == p->aux[1]) return false;
     if (knobs().pipe_form >= 0) return knobs().pipe_form == 1;    // (developer build: H2R_PIPE_FORM forces the form, e.g. under a profiler)
+    if (p->form != H2R_PIPE_AUTO) return p->form == H2R_PIPE_TWO_QUEUE;   // h2r_pipeline_set_form: the caller's verdict, no probe
     auto it = p->queue_probe.find(st);
     if (!force && it != p->queue_probe.end()) return it->second != 0;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -1897,6 +1984,14 @@ int32_t pipeline_verify(h2r_pipeline *p, const void *sig, const void *n, const E
 }  // extern "C++"
 
 int32_t h2r_pipeline_create(const h2r_ctx *ctx, h2r_pipeline **out) try { return h2r_pipeline_create_ex(ctx, 2, 1, out); } H2R_CATCH_STATUS
+
+int32_t h2r_pipeline_set_form(h2r_pipeline *p, uint32_t form) try {
+    if (!p) return H2R_E_NULL;
+    if (form != H2R_PIPE_AUTO && form != H2R_PIPE_TWO_QUEUE && form != H2R_PIPE_ONE_LAUNCH_STEP) return H2R_E_SHAPE;
+    if (form == H2R_PIPE_TWO_QUEUE && p->aux[0] == p->aux[1]) return H2R_E_UNSUPPORTED;   // one side stream: there is no two-queue form to force
+    p->form = form;
+    return H2R_OK;
+} H2R_CATCH_STATUS
 
 int32_t h2r_pipeline_info(h2r_pipeline *p, h2r_stream_t stream, uint64_t batch, h2r_pipeline_info_t *out) try {
     if (!p || !out) return H2R_E_NULL;

@@ -51,6 +51,7 @@ struct Knobs {
     long exp_segments = -1;                      // H2R_EXP_SEGMENTS=n: segments a long exponent is walked in (0 / 1 = never; -1 = the default rule, exp_segment_count)
     long single_call_segments = -1;              // H2R_SINGLE_CALL_SEGMENTS=n: segments of a SHORT exponent in a single stream-ordered call of 513..1,536 RSA-2048 elements
     long rowprog_stage_rows = 0;                 // H2R_ROWPROG_STAGE_ROWS=64|128|256: rows (= threads) of a row-program workgroup (0 = the rule in launch_row_prog)
+    long keep_const = -1;                        // H2R_KEEP_CONST=0: record launches into a trace arena's regions store the constant planes like any other
     long cells_nwv = 0;                          // H2R_CELLS_NWV=1|8: waves per cells_kernel workgroup of a Montgomery ctx (0 = the rule at ctx creation)
     Knobs() {
 #ifdef H2R_DEV_KNOBS
@@ -66,6 +67,7 @@ struct Knobs {
         verify_fold = num("H2R_VERIFY_FOLD", -1); exp_segments = num("H2R_EXP_SEGMENTS", -1); single_call_segments = num("H2R_SINGLE_CALL_SEGMENTS", -1);
         pipe_step = num("H2R_PIPE_STEP", -1); pipe_form = num("H2R_PIPE_FORM", -1); pipe_twoq_l16 = num("H2R_PIPE_TWOQ_L16", 0); step_chain_x2_per_cu = num("H2R_STEP_CHAIN_X2_PER_CU", 0);
         rowprog_stage_rows = num("H2R_ROWPROG_STAGE_ROWS", 0); cells_nwv = num("H2R_CELLS_NWV", 0);
+        keep_const = num("H2R_KEEP_CONST", -1);
         pipe_sub_batch = num("H2R_PIPE_SUB_BATCH", 0); arena_chunk_mb = num("H2R_ARENA_CHUNK_MB", 0); plain_overlap = num("H2R_PLAIN_OVERLAP", -1); pipe_pace = num("H2R_PIPE_PACE", -1);
 #endif
     }

@@ -1210,6 +1210,8 @@ struct TraceArgs {
     u32 prio;                           // raise wave priority (pipeline co-scheduling)
     u32 acc_spg, acc_lo_row; u64 acc_lo_group, acc_hi_group;   // accumulator-plane addressing (h2r_layout)
     u32 mode;                           // TRACE_FULL (mul_mod), TRACE_MUL (BigIntChip::mul only), TRACE_EQ (is_equal_muled only)
+    u32 keep_const;                     // every record of the launch is a record slot of a trace arena's region, whose constant planes
+                                        // (ACCX/QACC/MODACC/NQ2/AMNQ2) are in place since the arena's look: they are not stored again
     const u64 *muled_a, *muled_b;       // TRACE_EQ inputs: [item][2L] x 4 u64 (256-bit columns)
     u64 *muled_out;                     // TRACE_MUL output, same format
     u8 *eq_out;                         // TRACE_EQ: final eq_bit per item
@@ -1372,7 +1374,9 @@ struct TraceShared {
 };
 // The work of workgroup `block` of `n_blocks` (the kernel below; also callable as one role of a larger launch)
 // TSEG = false (the step launches' record role, whose register allocation is tuned): no segment addressing (t_lo / T_ops) in the code.
-template <int LW, int L, int BT = TraceGeo<L>::BT, bool TSEG = true>
+// KEEPC = false (the verifier's step builds, which sit at their register limit: with the branch the RSA-2048 one spills 308 bytes per lane
+// instead of 192): TraceArgs::keep_const is ignored, every record is written whole.
+template <int LW, int L, int BT = TraceGeo<L>::BT, bool TSEG = true, bool KEEPC = true>
 __device__ __forceinline__ void trace_block(const TraceArgs &args, const u32 block, const u32 n_blocks, TraceShared<LW, L, BT> &sh) {
     using limb_t = typename LimbT<LW>::type;
     using W = Wide<LW>;
@@ -1566,24 +1570,29 @@ __device__ __forceinline__ void trace_block(const TraceArgs &args, const u32 blo
         // input-independent part of the step (acc_extra chain, :869-871): copy from the constant record
         // (whose entry 2L-1 is zero)
         const u8 *cr = args.const_rec;
-        const ulonglong2 ax = *reinterpret_cast<const ulonglong2 *>(cr + off[H2R_PL_ACCX_LO] + (u64)c * 16);
-        const ulonglong2 n2 = *reinterpret_cast<const ulonglong2 *>(cr + off[H2R_PL_NQ2_LO] + (u64)c * 16);
-        st16(rec + off[H2R_PL_ACCX_LO] + (u64)c * 16, ax.x, ax.y);
-        st16(rec + off[H2R_PL_NQ2_LO] + (u64)c * 16, n2.x, n2.y);
         if constexpr (LW == 64) {
-            st8(rec + off[H2R_PL_ACCX_HI] + (u64)c * 8, *reinterpret_cast<const u64 *>(cr + off[H2R_PL_ACCX_HI] + (u64)c * 8));
-            st8(rec + off[H2R_PL_NQ2_HI] + (u64)c * 8, *reinterpret_cast<const u64 *>(cr + off[H2R_PL_NQ2_HI] + (u64)c * 8));
             const ulonglong2 qa = *reinterpret_cast<const ulonglong2 *>(cr + off[H2R_PL_QACC] + (u64)c * 16);
             qacc.lo = ((u128)qa.y << 64) | qa.x;
             modacc = *reinterpret_cast<const u64 *>(cr + off[H2R_PL_MODACC] + (u64)c * 8);
-            st8(rec + off[H2R_PL_AMNQ2] + (u64)c * 8, *reinterpret_cast<const u64 *>(cr + off[H2R_PL_AMNQ2] + (u64)c * 8));
         } else {
             qacc.lo = *reinterpret_cast<const u64 *>(cr + off[H2R_PL_QACC] + (u64)c * 8);
             modacc = *reinterpret_cast<const u32 *>(cr + off[H2R_PL_MODACC] + (u64)c * 4);
-            st4(rec + off[H2R_PL_AMNQ2] + (u64)c * 4, *reinterpret_cast<const u32 *>(cr + off[H2R_PL_AMNQ2] + (u64)c * 4));
         }
-        store_carry<LW>(rec, off, H2R_PL_QACC, c, qacc);
-        store_limb<LW>(rec, off, H2R_PL_MODACC, c, modacc);
+        if (!KEEPC || args.keep_const == 0) {   // (wave-uniform) an arena region's record slots hold these seven planes already
+            const ulonglong2 ax = *reinterpret_cast<const ulonglong2 *>(cr + off[H2R_PL_ACCX_LO] + (u64)c * 16);
+            const ulonglong2 n2 = *reinterpret_cast<const ulonglong2 *>(cr + off[H2R_PL_NQ2_LO] + (u64)c * 16);
+            st16(rec + off[H2R_PL_ACCX_LO] + (u64)c * 16, ax.x, ax.y);
+            st16(rec + off[H2R_PL_NQ2_LO] + (u64)c * 16, n2.x, n2.y);
+            if constexpr (LW == 64) {
+                st8(rec + off[H2R_PL_ACCX_HI] + (u64)c * 8, *reinterpret_cast<const u64 *>(cr + off[H2R_PL_ACCX_HI] + (u64)c * 8));
+                st8(rec + off[H2R_PL_NQ2_HI] + (u64)c * 8, *reinterpret_cast<const u64 *>(cr + off[H2R_PL_NQ2_HI] + (u64)c * 8));
+                st8(rec + off[H2R_PL_AMNQ2] + (u64)c * 8, *reinterpret_cast<const u64 *>(cr + off[H2R_PL_AMNQ2] + (u64)c * 8));
+            } else {
+                st4(rec + off[H2R_PL_AMNQ2] + (u64)c * 4, *reinterpret_cast<const u32 *>(cr + off[H2R_PL_AMNQ2] + (u64)c * 4));
+            }
+            store_carry<LW>(rec, off, H2R_PL_QACC, c, qacc);
+            store_limb<LW>(rec, off, H2R_PL_MODACC, c, modacc);
+        }
         f1 = cmod == modacc;                               // cs_acc_eq, :873
         // range-assign the carry (:879-885): duplicate value + sub-limbs; range_eq == 1 (:886).
         // Columns C-1 (no range check, :888-892) and 2L-1 (no column) store zeros.
@@ -1997,7 +2006,7 @@ __global__ __launch_bounds__(64 * NW, H2R_CHAIN_MINB) void step_kernel(ChainArgs
     } else if (b < n_chain + n_rec) {
         // (a record role of a few workgroups per CU that WALK the records was tried: inlined into a loop the body spills 25
         //  registers at this launch's 80, as a real call it runs at 4.1 TB/s -- one workgroup per four records it is)
-        trace_block<LW, L, 64 * NW, false>(ta, b - n_chain, n_rec, sh.trace);
+        trace_block<LW, L, 64 * NW, false, !FOLD>(ta, b - n_chain, n_rec, sh.trace);
     } else if (b - n_chain - n_rec < aa.batch) {
         // last in dispatch order: these short workgroups fill the slots the record role's tail leaves (in front of the record
         // role they cost the step 3-5 us)

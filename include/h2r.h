@@ -400,7 +400,7 @@ int32_t h2r_pipeline_join(h2r_pipeline *p, h2r_stream_t stream);
  * stream therefore synchronises that stream once (~0.5 ms).  Three queues = the spinners' own device-clock stamps show all three running
  * at one instant AND first start to last end is <= 0.157 ms (0.154 measured on three queues, 0.160 when two streams share one; the host-side
  * wall time, which carries launch jitter, only has to be <= 0.195 ms). */
-enum { H2R_PIPE_ONE_LAUNCH_STEP = 0, H2R_PIPE_TWO_QUEUE = 1, H2R_PIPE_SIDE_STREAM = 2 };
+enum { H2R_PIPE_ONE_LAUNCH_STEP = 0, H2R_PIPE_TWO_QUEUE = 1, H2R_PIPE_SIDE_STREAM = 2, H2R_PIPE_AUTO = 3 };
 typedef struct h2r_pipeline_info_t {
     uint32_t struct_size;   /* in: sizeof(h2r_pipeline_info_t) */
     uint32_t depth, side_streams;
@@ -411,6 +411,12 @@ typedef struct h2r_pipeline_info_t {
                                (struct_size 24) is still served */
 } h2r_pipeline_info_t;
 int32_t h2r_pipeline_info(h2r_pipeline *p, h2r_stream_t stream, uint64_t batch, h2r_pipeline_info_t *out);
+/* The caller's verdict instead of the probe's: H2R_PIPE_TWO_QUEUE (the three streams are on three hardware queues) or
+ * H2R_PIPE_ONE_LAUNCH_STEP (they are not); H2R_PIPE_AUTO (the default) lets the probe decide again.  It only skips the queue probe --
+ * which shapes and call sizes HAVE a two-queue form or a one-launch step is unchanged, and h2r_pipeline_info reports the forced verdict.
+ * For a host that knows its queues, and for profiling and testing either form on any box (attaching a profiler changes what the probe
+ * measures).  Any other value: H2R_E_SHAPE; H2R_PIPE_TWO_QUEUE on a pipeline created with one side stream: H2R_E_UNSUPPORTED (it has no such form).  Takes effect from the next call on; call h2r_pipeline_join first when calls are in flight. */
+int32_t h2r_pipeline_set_form(h2r_pipeline *p, uint32_t form);
 
 /* ---- multi-GPU: one process per GPU, signatures sharded, RCCL over xGMI behind the C ABI ---------------------------------
  * Signatures are independent: every rank owns a contiguous shard of the batch (h2r_dist_shard_range), runs the
@@ -452,7 +458,21 @@ int32_t h2r_dist_allreduce_max_f64(h2r_dist *d, double *values, uint64_t count, 
  * While the kept regions are not 7 % faster than the median of everything measured (regions of up to 12 GB) up to four more rounds
  * of `candidates` are tried, each after giving everything back and behind a placeholder allocation of another size (48, 96, ...
  * GB, at most half of the free memory): fresh, unchurned device memory hands out the slow class only.
- * Synchronises `stream`.  The regions are ordinary device memory for every other purpose. */
+ * Synchronises `stream`.
+ * THE CONSTANT PLANES of the regions' record slots BELONG TO THE ARENA.  A record's ACCX_LO/HI, QACC, MODACC, NQ2_LO/HI and AMNQ2
+ * planes depend on (limb_width, num_limbs) alone; the look writes them into every record slot of every region it keeps (element i's
+ * record t at i * elem_stride + first_record_off + t * record_stride, i < batch, t < records_per_elem), and they are valid from
+ * creation.  A record launch whose records all lie on such slots -- same device and shape, `trace` = a region's base plus a whole
+ * number of elem_stride, equal elem_stride and records offset, within records_per_elem and batch -- does not store them again (8 % of
+ * a record's bytes for 32 x 64-bit limbs); any other launch (a plain buffer, another geometry, the stand-alone mul / is_equal_muled
+ * records) writes complete records as ever.  Whoever overwrites those planes (a memset of the region, another layout's call into it)
+ * calls h2r_arena_restore_constants(a, region, stream) before the next matching call: it rewrites the planes of every record slot
+ * of kept region `region` on `stream` (H2R_E_UNSUPPORTED for an image arena, H2R_E_SHAPE for a region the arena does not have).
+ * The decision is made on the host when the call is issued and travels in the kernel's arguments: a launch recorded into a captured
+ * graph keeps it, so such a graph must not be replayed after the arena was destroyed or after its planes were overwritten without a
+ * restore.  The step launches of the pipelined VERIFIER always write whole records (their builds sit at their register limit).
+ * Everything else in a region is ordinary device memory.  Destroy the arena only after the calls into its regions have been issued
+ * AND joined. */
 typedef struct h2r_arena h2r_arena;
 int32_t h2r_arena_create(const h2r_ctx *ctx, uint64_t elem_stride, uint64_t first_record_off, uint32_t records_per_elem,
                          uint64_t batch, uint32_t regions, uint32_t candidates, h2r_stream_t stream, h2r_arena **out);
@@ -478,6 +498,7 @@ void *h2r_arena_region(const h2r_arena *a, uint32_t i);
 uint64_t h2r_arena_region_bytes(const h2r_arena *a);
 double h2r_arena_region_ms(const h2r_arena *a, uint32_t i);          /* measured record-kernel time of kept region i */
 uint32_t h2r_arena_measurements(const h2r_arena *a, double *ms_out, uint32_t cap);   /* all candidates, allocation order */
+int32_t h2r_arena_restore_constants(h2r_arena *a, uint32_t region, h2r_stream_t stream);
 void h2r_arena_destroy(h2r_arena *a);
 
 /* How a pipelined (or a large plain) fixed-exponent call of `batch` elements is walked on this ctx: the sizes of the
