@@ -1031,12 +1031,38 @@ struct h2r_arena {
 };
 
 namespace {
+// The address ranges of regions that were unmapped.  They are RETIRED, not given back with hipMemAddressFree: a range that is freed and
+// then reserved and mapped again -- by the look's next candidate, by the next arena -- was seen to keep its old translation on the device
+// for a while.  Records written into the new region then went to the old, released chunks, and the region read back as the zero fill or the
+// look had left it: 33 of 40 small arenas created and closed in turn lost records of a call that way, 0 of 40 with the ranges retired
+// (5 of 40 when the physical chunks were kept and the range reused).  An unmapped reservation costs address space only; if a reservation
+// fails, the retired ranges are given back and it is tried once more.
+struct RetiredRanges {
+    std::mutex mu;
+    std::vector<std::pair<void *, size_t>> ranges;
+    void add(void *va, size_t bytes) { std::lock_guard<std::mutex> lk(mu); ranges.emplace_back(va, bytes); }
+    void give_back() {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &r : ranges) (void)hipMemAddressFree(r.first, r.second);
+        ranges.clear();
+    }
+};
+RetiredRanges &retired_ranges() { static RetiredRanges r; return r; }
+hipError_t arena_reserve(void **va, size_t bytes) {
+    hipError_t e = hipMemAddressReserve(va, bytes, 0, nullptr, 0);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        retired_ranges().give_back();
+        e = hipMemAddressReserve(va, bytes, 0, nullptr, 0);
+    }
+    return e;
+}
 void arena_free_region(h2r_arena::Region &r) {
     if (r.plain) { if (r.va) (void)hipFree(r.va); r.va = nullptr; return; }
     // chunk k is mapped at va + k * chunk for k < n_mapped (a candidate that failed half-way has fewer than handles.size())
     for (u64 k = 0; r.va && k < r.n_mapped; ++k) (void)hipMemUnmap(static_cast<u8 *>(r.va) + k * r.chunk, r.chunk);
     for (auto h : r.handles) (void)hipMemRelease(h);
-    if (r.va) (void)hipMemAddressFree(r.va, r.mapped);
+    if (r.va) retired_ranges().add(r.va, r.mapped);   // (not hipMemAddressFree: see RetiredRanges)
     r.va = nullptr; r.handles.clear(); r.n_mapped = 0;
 }
 // a streaming fill in the product kernels' store pattern (16 bytes per lane, non-temporal, whole 4 KB runs per workgroup step,
@@ -1088,7 +1114,7 @@ int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint
             if (!hip_ok(hipMalloc(&r.va, region_bytes), "hipMalloc")) { r.va = nullptr; return H2R_E_HIP; }
             return measure(r.va, st, ea, eb, &r.ms);   // (its first launch touches the pages)
         }
-        if (!hip_ok(hipMemAddressReserve(&r.va, r.mapped, 0, nullptr, 0), "hipMemAddressReserve")) { r.va = nullptr; return H2R_E_HIP; }
+        if (!hip_ok(arena_reserve(&r.va, r.mapped), "hipMemAddressReserve")) { r.va = nullptr; return H2R_E_HIP; }
         for (u64 k = 0; k < n_chunks; ++k) {
             hipMemGenericAllocationHandle_t h;
             if (!hip_ok(hipMemCreate(&h, chunk, &prop, 0), "hipMemCreate")) return H2R_E_HIP;
