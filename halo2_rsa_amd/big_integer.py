@@ -1499,6 +1499,62 @@ class EvaluationDomain:
         return W, be, status
 
 
+class CommitKey:
+    """The bases of the commitments on the device (h2r_msm_columns): n affine points of the curve of the chip's field
+    (bn256 G1 for bn254_fr; every other field is refused), 64 bytes each -- x then y, Fq elements in the chip's representation, (0, 0) the
+    identity -- as halo2curves' `ParamsKZG::g` / `g_lagrange` lie in memory for a Montgomery chip.  The bases are not validated."""
+
+    def __init__(self, chip: BigIntChip, bases: torch.Tensor):
+        if bases.dtype == torch.int64 and bases.dim() == 3 and tuple(bases.shape[1:]) == (2, 4):
+            pass
+        elif bases.dtype == torch.uint8 and bases.dim() == 2 and bases.shape[1] == 64:
+            pass
+        else:
+            check(_lib.H2R_E_SHAPE, "CommitKey")
+        assert bases.is_contiguous() and bases.is_cuda
+        self.chip, self.bases, self.n = chip, bases, int(bases.shape[0])
+
+    def _config(self, num_cols: int):
+        cfg = _lib.H2RMsmConfig()
+        cfg.struct_size, cfg.n, cfg.num_cols, cfg.reserved = ctypes.sizeof(cfg), self.n, num_cols, 0
+        return cfg
+
+    def plan(self, num_cols: int, batch: int) -> "_lib.H2RMsmInfo":
+        """window_bits, num_windows, slice_points, num_slices and workspace_bytes of a call (h2r_msm_plan, a host function)."""
+        info, cfg = _lib.H2RMsmInfo(), self._config(num_cols)
+        if lib().h2r_msm_plan(ctypes.byref(cfg), batch, ctypes.byref(info)) == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_msm_plan")
+        return info
+
+    def commit(self, columns, out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int64 [batch, num_cols, 2, 4]: the affine commitments sum_i columns[c][e][i] * bases[i] in the chip's representation, (0, 0) for the
+        identity.  columns: a list of tensors uint8 [batch, n, 32] (scalars in the chip's representation), or [n, 32] for a column the
+        whole batch shares (batch = 1 where every column is such a one).  out: the tensor to write into (it must overlap no input);
+        status: uint8 [batch], a byte that is nonzero on entry skips the circuit (its commitments are left as they were); workspace: uint8,
+        plan(num_cols, batch).workspace_bytes bytes, 16-byte aligned, the call's own until the stream has run it (allocated when None)."""
+        if not 0 < len(columns) <= _lib.H2R_MSM_MAX_COLUMNS:
+            check(_lib.H2R_E_SHAPE, "CommitKey.commit")
+        batch = next((int(t.shape[0]) for t in columns if t.dim() == 3), 1)
+        cfg = self._config(len(columns))
+        desc = (_lib.H2RMsmColumn * len(columns))()
+        for d, t in zip(desc, columns):
+            assert t.dtype == torch.uint8 and t.dim() in (2, 3) and tuple(t.shape[-2:]) == (self.n, 32) and t.stride(-1) == 1 and t.stride(-2) == 32
+            assert t.dim() == 2 or t.shape[0] == batch
+            d.base, d.elem_stride = t.data_ptr(), t.stride(0) if t.dim() == 3 else 0
+        dev = self.bases.device
+        if out is None:
+            out = torch.zeros((batch, len(columns), 2, 4), dtype=torch.int64, device=dev)
+        assert out.is_contiguous() and out.dtype == torch.int64 and tuple(out.shape) == (batch, len(columns), 2, 4)
+        need = int(lib().h2r_msm_workspace_bytes(ctypes.byref(cfg), batch))
+        ws = workspace if workspace is not None else torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+        check(lib().h2r_msm_columns(self.chip._ctx, ctypes.byref(cfg), desc, self.bases.data_ptr(), batch, out.data_ptr(),
+                                    status.data_ptr() if status is not None else None, ws.data_ptr(), self.chip._stream()), "h2r_msm_columns")
+        self._keep = (ws, list(columns), out, status)   # alive until the stream has run the kernels
+        return out
+
+
 @dataclass
 class FreshResult:
     value: Optional[AssignedInteger]

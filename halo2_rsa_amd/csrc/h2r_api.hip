@@ -28,6 +28,7 @@
 #include "h2r_ntt.hpp"
 #include "h2r_quotient.hpp"
 #include "h2r_open.hpp"
+#include "h2r_msm.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4494,7 +4495,8 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
 // ---- the openings: fold, evaluations at x, GWC witness polynomials (h2r_open.hpp, h2r_tu_open.hip) -----------------------------------------
 namespace {
 static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_OPEN_SCAN == H2R_KERNEL_OPEN_TILES + 2 &&
-              H2R_KERNEL_COUNT == H2R_KERNEL_FOLD + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_MSM_BUCKET == H2R_KERNEL_FOLD + 1 && H2R_KERNEL_MSM_FOLD == H2R_KERNEL_MSM_BUCKET + 1 &&
+              H2R_KERNEL_COUNT == H2R_KERNEL_MSM_FOLD + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -4648,6 +4650,124 @@ int32_t h2r_fold_columns(const h2r_ctx *ctx, const void *in, uint64_t in_elem_st
         ProfScope ps(H2R_KERNEL_FOLD, st, true);
         HIP_TRY(launch_fold(fa, (u32)std::min<u64>(tiles_per, tiles - t0), (u32)batch, st, ps.a, ps.on ? ps.b : nullptr));
     }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the commitments: multi-scalar multiplications over the curve of the ctx's field (h2r_msm.hpp, h2r_curve.hpp, h2r_tu_msm.hip) ---------
+namespace {
+static_assert(H2R_MSM_MAX_COLUMNS == MSM_MAX_COLUMNS, "h2r.h and the kernels' argument struct");
+// what the host helpers answer 0 for: the configuration and the batch, which need no ctx and no pointer
+int32_t msm_cfg_status(const h2r_msm_config *cfg, uint64_t batch) {
+    if (cfg->struct_size != sizeof(h2r_msm_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->n == 0 || cfg->n > MSM_MAX_POINTS || cfg->num_cols == 0 || cfg->num_cols > MSM_MAX_COLUMNS || cfg->reserved) return H2R_E_SHAPE;
+    if (batch > 65535) return H2R_E_UNSUPPORTED;
+    return H2R_OK;
+}
+}  // namespace
+
+uint64_t h2r_msm_plan(const h2r_msm_config *cfg, uint64_t batch, h2r_msm_info *info) try {
+    if (!cfg || !info || msm_cfg_status(cfg, batch) != H2R_OK) return 0;
+    info->window_bits = MSM_WINDOW_BITS; info->num_windows = MSM_WINDOWS; info->slice_points = MSM_SLICE; info->num_slices = msm_slices_of(cfg->n);
+    info->workspace_bytes = msm_workspace_bytes(cfg->n, cfg->num_cols, batch);
+    return info->workspace_bytes;
+} H2R_CATCH_ZERO
+
+uint64_t h2r_msm_workspace_bytes(const h2r_msm_config *cfg, uint64_t batch) try {
+    return cfg && msm_cfg_status(cfg, batch) == H2R_OK ? msm_workspace_bytes(cfg->n, cfg->num_cols, batch) : 0;
+} H2R_CATCH_ZERO
+
+int32_t h2r_msm_columns(const h2r_ctx *ctx, const h2r_msm_config *cfg, const h2r_msm_column *cols, const void *bases, uint64_t batch,
+                        uint64_t *out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !cols || !bases || !out || !workspace) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_msm_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->num_cols && cfg->num_cols <= MSM_MAX_COLUMNS)
+        for (u32 c = 0; c < cfg->num_cols; ++c)
+            if (!cols[c].base) return H2R_E_NULL;
+    if (cfg->n == 0 || cfg->n > MSM_MAX_POINTS || cfg->num_cols == 0 || cfg->num_cols > MSM_MAX_COLUMNS || cfg->reserved) return H2R_E_SHAPE;
+    const u64 col = 32ull * cfg->n;
+    if ((reinterpret_cast<u64>(bases) | reinterpret_cast<u64>(out) | reinterpret_cast<u64>(workspace)) & 15) return H2R_E_SHAPE;
+    for (u32 c = 0; c < cfg->num_cols; ++c) {
+        if ((reinterpret_cast<u64>(cols[c].base) | cols[c].elem_stride) & 15) return H2R_E_SHAPE;
+        if (cols[c].elem_stride && cols[c].elem_stride < col) return H2R_E_SHAPE;
+    }
+    if (batch) {   // out and the workspace are written while other workgroups still read the columns and the bases
+        const u128 o0 = reinterpret_cast<u64>(out), o1 = o0 + (u128)batch * cfg->num_cols * 64;
+        const u128 w0 = reinterpret_cast<u64>(workspace), w1 = w0 + (u128)256 + (u128)batch * cfg->num_cols * MSM_WINDOWS * msm_slices_of(cfg->n) * MSM_PARTIAL_BYTES;
+        const u128 b0 = reinterpret_cast<u64>(bases), b1 = b0 + (u128)64 * cfg->n;
+        if ((o0 < w1 && w0 < o1) || (o0 < b1 && b0 < o1) || (w0 < b1 && b0 < w1)) return H2R_E_SHAPE;
+        for (u32 c = 0; c < cfg->num_cols; ++c) {
+            const u128 c0 = reinterpret_cast<u64>(cols[c].base), c1 = c0 + (u128)(batch - 1) * cols[c].elem_stride + col;
+            if ((c0 < o1 && o0 < c1) || (c0 < w1 && w0 < c1)) return H2R_E_SHAPE;
+        }
+    }
+    if (batch > 65535) return H2R_E_UNSUPPORTED;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    MsmArgs ma;
+    std::memset(static_cast<void *>(&ma), 0, sizeof ma);
+    for (u32 c = 0; c < cfg->num_cols; ++c) ma.cols[c] = MsmCol{static_cast<const u8 *>(cols[c].base), cols[c].elem_stride};
+    ma.bases = static_cast<const u8 *>(bases); ma.status = status; ma.out = out;
+    ma.ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    ma.n = cfg->n; ma.num_cols = cfg->num_cols; ma.num_slices = msm_slices_of(cfg->n);
+    ma.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;
+    ma.fr = ctx->fc; ma.cv = *cv;
+    // launches below the 2^32 global size and the 65,535 of a grid's y / z: slices of circuits
+    const u64 max_blocks = ((1ull << 32) - 1) / 256, per_elem = (u64)ma.num_slices * MSM_WINDOWS * ma.num_cols;
+    const u64 elems_per = std::min<u64>({batch, 65535, max_blocks / per_elem});
+    if (!elems_per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (u32 phase = 0; phase < 2; ++phase)
+        for (u64 e0 = 0; e0 < batch; e0 += elems_per) {
+            ma.elem0 = (u32)e0;
+            ProfScope ps(H2R_KERNEL_MSM_BUCKET + phase, st, true);
+            HIP_TRY(launch_msm(phase, ma, (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
+        }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t *out) try {
+    if (!ctx || !a || !out || ((op == 0 || op == 1 || op == 4) && !b)) return H2R_E_NULL;
+    if (op > 4) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    const FieldConsts &f = cv->fq;
+    bool ok = true;
+    auto coord = [&](const uint64_t *w) {   // a canonical coordinate -> the Montgomery form
+        Fe x; for (int k = 0; k < 4; ++k) x.v[k] = w[k];
+        if (ge_p(x.v, f.p)) { ok = false; return fe_zero(); }
+        return fe_to_mont(x, f);
+    };
+    auto put = [&](uint64_t *w, const Fe &x) { const Fe c = fe_from_mont(x, f); for (int k = 0; k < 4; ++k) w[k] = c.v[k]; };
+    PtProj p; p.x = coord(a); p.y = coord(a + 4); p.z = coord(a + 8);
+    PtProj r = p;
+    if (op == 0) {
+        PtProj q; q.x = coord(b); q.y = coord(b + 4); q.z = coord(b + 8);
+        if (!ok) return H2R_E_SHAPE;
+        r = pt_add(p, q, *cv);
+    } else if (op == 1) {
+        PtAff q; q.x = coord(b); q.y = coord(b + 4);
+        if (!ok) return H2R_E_SHAPE;
+        r = pt_add_affine(p, q, *cv);
+    } else if (op == 2) {
+        if (!ok) return H2R_E_SHAPE;
+        r = pt_double(p, *cv);
+    } else if (op == 3) {
+        if (!ok) return H2R_E_SHAPE;
+        const PtAff q = pt_to_affine(p, *cv);
+        put(out, q.x); put(out + 4, q.y);
+        return H2R_OK;
+    } else {   // k * P as the kernels form it: the digit's multiple per window, a Horner over the windows from the top
+        if (!ok) return H2R_E_SHAPE;
+        r = pt_identity(*cv);
+        for (u32 w = MSM_WINDOWS; w-- > 0;) {
+            const u32 d = (u32)(b[w >> 3] >> ((w & 7u) * 8)) & 0xffu;
+            r = pt_add(pt_shift_window(r, *cv), pt_mul_digit(p, d, *cv), *cv);
+        }
+    }
+    put(out, r.x); put(out + 4, r.y); put(out + 8, r.z);
     return H2R_OK;
 } H2R_CATCH_STATUS
 

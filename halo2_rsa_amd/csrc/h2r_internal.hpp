@@ -12,6 +12,7 @@
 //   h2r_tu_ntt.hip     the evaluation domain's transforms (h2r_ntt.hpp)
 //   h2r_tu_quotient.hip   the vanishing argument's quotient on the extended domain (h2r_quotient.hpp)
 //   h2r_tu_open.hip    the openings: evaluations at x, GWC witness polynomials, the fold of h's pieces (h2r_open.hpp)
+//   h2r_tu_msm.hip     the commitments: multi-scalar multiplications over the curve of the ctx's field (h2r_msm.hpp, h2r_curve.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -131,5 +132,9 @@ struct OpenArgs;
 struct FoldArgs;
 hipError_t launch_open(u32 phase, const OpenArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 hipError_t launch_fold(const FoldArgs &a, u32 num_tiles, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_msm.hip (argument struct: h2r_msm.hpp).  phase 0 = the buckets of every (slice, window, column), 1 = the fold per column; the circuits
+// [a.elem0, a.elem0 + num_elems).
+struct MsmArgs;
+hipError_t launch_msm(u32 phase, const MsmArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

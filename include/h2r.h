@@ -1000,8 +1000,8 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
 /* ---- the openings: the fold of h's pieces, the evaluations at x and its rotations, the GWC witness polynomials ----
  * THIRD-PARTY behaviour (halo2 vanishing::prover::evaluate, poly::eval_polynomial and poly::kzg::multiopen::ProverGWC with kate_division,
  * not in the reference tree), restated in DESIGN.md section 2h; parity is pinned against a Python restatement (tests/opening_ref.py,
- * tests/test_open_gpu.py), not against upstream.  What lies between "h exists" and "the proof is written" except the commitments (MSMs:
- * curve arithmetic, out of scope).  All arithmetic mod the ctx's p.  A column is n_coeffs field elements of 32 bytes in COEFFICIENT form, in
+ * tests/test_open_gpu.py), not against upstream.  What lies between "h exists" and "the proof is written" except the commitments (the MSMs:
+ * h2r_msm_columns below).  All arithmetic mod the ctx's p.  A column is n_coeffs field elements of 32 bytes in COEFFICIENT form, in
  * the ctx's representation (for these planar vectors only H2R_ADVICE_MONTGOMERY matters), 1 <= n_coeffs <= 2^24, no power of two needed.
  *  - A call names its columns by a host array of num_cols descriptors: column c of circuit e lies at base + e * elem_stride; elem_stride = 0
  *    is a proving-key column shared by every circuit.  Bit p of point_mask = "column c is queried at point p", p < num_points.  The points
@@ -1050,6 +1050,47 @@ int32_t h2r_open_witness_columns(const h2r_ctx *ctx, const h2r_open_config *cfg,
 int32_t h2r_fold_columns(const h2r_ctx *ctx, const void *in, uint64_t in_elem_stride, uint64_t in_col_stride, uint32_t num_cols,
                          uint32_t n_coeffs, const uint64_t *s, uint64_t batch, void *out, uint64_t out_elem_stride, uint8_t *status,
                          h2r_stream_t stream);
+/* ---- the commitments: multi-scalar multiplications over the curve of the ctx's field ----
+ * What create_proof does with every column before it draws the next challenge: C = sum_i s_i * P_i over fixed bases (the KZG parameters'
+ * g or g_lagrange).  DESIGN.md section 2i.  Only a ctx whose field is H2R_FIELD_BN254_FR has a curve here: bn256 G1, y^2 = x^3 + 3 over Fq,
+ * of prime order r = the ctx's p; every other field gets H2R_E_UNSUPPORTED.  The encoding of points is a restatement of halo2curves
+ * (G1Affine: x then y, (0, 0) for the identity), not pinned against it.
+ *  - bases: n affine points on the device, 64 bytes each: x then y, four 64-bit words each, Fq elements in the ctx's representation (a
+ *    Montgomery ctx reads a halo2curves G1Affine array as it lies in memory).  (0, 0) is the identity and contributes nothing.  The bases are
+ *    the caller's key material and are NOT validated: an off-curve point or a coordinate >= q gives unspecified output bytes, never a fault
+ *    or an unbounded loop.
+ *  - scalars: columns of n elements of 32 bytes in the ctx's representation, named by a host array of num_cols descriptors: column c of
+ *    circuit e lies at base + e * elem_stride; elem_stride = 0 is one copy for the whole batch.  1 <= n <= 2^24, no power of two needed.
+ *    The scalar is the integer the 32 bytes mean (canonical ctx: the 256-bit integer itself, a value >= p included -- the group order is p and
+ *    the windows cover all 256 bits, so it multiplies like its residue; Montgomery ctx: w * R^-1 mod p).
+ *  - out[batch][num_cols][2][4] uint64 on the device: affine x, y in the ctx's representation, the canonical representative of each
+ *    coordinate, (0, 0) for the identity: the bytes do not depend on the order of additions.
+ *  - status (nullable, [batch]) is never cleared: a circuit whose byte is nonzero on entry is skipped (nothing is written, no workspace
+ *    result is consumed).  The call has no per-circuit error of its own.
+ *  - h2r_msm_plan (host only, no ctx, no device) fills `info` and returns workspace_bytes; it returns 0 and leaves `info` alone for a
+ *    configuration the call would refuse.  h2r_msm_workspace_bytes returns the same number.  h2r_msm_columns enqueues two launches on
+ *    `stream` (the buckets per (slice, window, column, circuit); the fold per (column, circuit)) and never synchronises; no workgroup waits
+ *    for another; launches are sliced internally below the 2^32 global size; the workspace is private to the call until the stream has run it.
+ *  - H2R_E_NULL for a NULL required pointer (status is optional); H2R_E_UNSUPPORTED for another struct_size, more than 65,535 circuits, a
+ *    field without a curve, or a host-only ctx (that one after every other check); H2R_E_SHAPE for n = 0 or > 2^24, num_cols = 0 or >
+ *    H2R_MSM_MAX_COLUMNS, a nonzero `reserved`, a column base, bases, out or workspace pointer or a stride that is not 16-byte aligned, a
+ *    nonzero elem_stride smaller than the column, and out or the workspace overlapping a column, the bases or each other.  batch = 0
+ *    returns H2R_OK with no launch.
+ *  - h2r_curve_eval (host only; works on a host-only ctx): the curve-level twin of h2r_field_eval, running the very functions the kernels
+ *    inline.  Operands are CANONICAL coordinates: a projective triple X, Y, Z (12 words; the identity is (0 : 1 : 0)) or an affine pair x, y
+ *    (8 words; (0, 0) is the identity).  op 0 = complete addition (a, b projective -> out projective), 1 = mixed addition (a projective, b
+ *    affine -> projective), 2 = doubling (a -> projective), 3 = to-affine (a projective -> out affine), 4 = k * P (a projective, b = k: four
+ *    words, any 256-bit integer -> projective; the windows and the Horner of the kernels).  H2R_E_SHAPE for a coordinate >= q or another op,
+ *    H2R_E_UNSUPPORTED for a field without a curve. */
+#define H2R_MSM_MAX_COLUMNS 64
+typedef struct h2r_msm_column { const void *base; uint64_t elem_stride; } h2r_msm_column;
+typedef struct h2r_msm_config { uint32_t struct_size, n, num_cols, reserved; } h2r_msm_config;
+typedef struct h2r_msm_info { uint32_t window_bits, num_windows, slice_points, num_slices; uint64_t workspace_bytes; } h2r_msm_info;
+uint64_t h2r_msm_plan(const h2r_msm_config *cfg, uint64_t batch, h2r_msm_info *info);
+uint64_t h2r_msm_workspace_bytes(const h2r_msm_config *cfg, uint64_t batch);
+int32_t h2r_msm_columns(const h2r_ctx *ctx, const h2r_msm_config *cfg, const h2r_msm_column *cols, const void *bases, uint64_t batch,
+                        uint64_t *out, uint8_t *status, void *workspace, h2r_stream_t stream);
+int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t *out);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1348,7 +1389,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_QUOTIENT = 18 /* quotient_kernel: h on the extended domain */,
        H2R_KERNEL_OPEN_TILES = 19, H2R_KERNEL_OPEN_CARRY = 20, H2R_KERNEL_OPEN_SCAN = 21 /* the openings' launches: evaluations (two), witness polynomials (three) */,
        H2R_KERNEL_FOLD = 22 /* fold_kernel */,
-       H2R_KERNEL_COUNT = 23 };
+       H2R_KERNEL_MSM_BUCKET = 23, H2R_KERNEL_MSM_FOLD = 24 /* the commitments' two launches: msm_bucket_kernel, msm_fold_kernel */,
+       H2R_KERNEL_COUNT = 25 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
