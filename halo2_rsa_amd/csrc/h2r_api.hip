@@ -34,6 +34,7 @@
 #include "h2r_sha256.hpp"
 #include "h2r_check.hpp"
 #include "h2r_arena_match.hpp"
+#include "h2r_stage_args.hpp"
 
 using namespace h2r;
 
@@ -99,6 +100,12 @@ struct ProfScope {  // start/stop events of one launch when profiling is armed
         g_prof.push_back(ProfRec{kernel, a, b});
     }
 };
+// One launch of a prover stage: fn(a, b) is the launch_x call, a / b the events that time it when profiling is armed.
+template <class Fn> int32_t stage_launch(u32 kernel_class, hipStream_t st, Fn &&fn) {
+    ProfScope ps(kernel_class, st, true);
+    HIP_TRY(fn(ps.a, ps.on ? ps.b : nullptr));
+    return H2R_OK;
+}
 
 // (developer knobs: h2r_internal.hpp)
 
@@ -4013,6 +4020,27 @@ int32_t h2r_lookup_hist_advice(const h2r_ctx *ctx, const h2r_lookup_config *cfg,
     return H2R_OK;
 } H2R_CATCH_STATUS
 
+// ---- what the prover stages' host sides share ("A stage's host side"; the buffer arithmetic: h2r_stage_args.hpp) --------------
+namespace {
+using namespace h2r_stage_args;
+bool ctx_mont(const h2r_ctx *ctx) { return (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0; }
+Fe fe_load(const uint64_t w[4]) { Fe x; for (int k = 0; k < 4; ++k) x.v[k] = w[k]; return x; }
+Fe fe_one(const FieldConsts &f) { return fe_load(f.one); }
+Fe fe_r2(const FieldConsts &f) { return fe_load(f.r2); }
+// a configuration's constant, held in the ctx's representation, in Montgomery form
+Fe cfg_to_mont(const h2r_ctx *ctx, const uint64_t w[4]) { return ctx_mont(ctx) ? fe_load(w) : fe_to_mont(fe_load(w), ctx->fc); }
+Fe fe_pow2k(Fe x, u32 k, const FieldConsts &f) { while (k--) x = fe_mont_mul(x, x, f); return x; }   // x^(2^k)
+// a primitive 2^log_n-th root of unity: omega^(n / 2) = -1
+bool is_primitive_root(const Fe &omega, u32 log_n, const FieldConsts &f) { return fe_is_zero(fe_add(fe_pow2k(omega, log_n - 1, f), fe_one(f), f.p)); }
+void fe_power_table(Fe *out, u32 n, const Fe &base, const FieldConsts &f) {   // out[c] = base^c
+    for (u32 c = 0; c < n; ++c) out[c] = c ? fe_mont_mul(out[c - 1], base, f) : fe_one(f);
+}
+void fe_squaring_chain(Fe *out, u32 n, Fe base, const FieldConsts &f) {   // out[b] = base^(2^b)
+    for (u32 b = 0; b < n; ++b) { out[b] = base; base = fe_mont_mul(base, base, f); }
+}
+u8 *workspace_256(void *workspace) { return reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256)); }
+}  // namespace
+
 // ---- the lookup argument's input columns A and grand-product columns Z (h2r_lookup_product.hpp, h2r_tu_lookup_product.hip) ------------
 namespace {
 // The table's rows all lie in the first tile of a column: the product kernels' table branch (and the timing tool's product counts) rest on it.
@@ -4028,11 +4056,6 @@ bool lookup_cfg_valid(const h2r_lookup_config *cfg) {
     }
     return off == cfg->n_rows;
 }
-// Circuits per launch: grid.z holds at most 65,535, and a launch's global size (threads) stays below 2^32.  0: even one circuit is too large.
-u64 lookup_launch_elems(u64 blocks_per_elem, u32 threads) {
-    const u64 per = ((1ull << 32) - 1) / (blocks_per_elem * threads);
-    return per < 65535 ? per : 65535;
-}
 }  // namespace
 
 int32_t h2r_lookup_input_columns(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const h2r_advice_layout *layout, const uint8_t *kinds_dev,
@@ -4047,7 +4070,7 @@ int32_t h2r_lookup_input_columns(const h2r_ctx *ctx, const h2r_lookup_config *cf
     else if (const int32_t rc = layout_lookup_valid(layout)) return rc;
     if (!usable_rows || usable_rows > kLookupMaxUsableRows) return H2R_E_SHAPE;
     if ((u64)first_row + rows > usable_rows) return H2R_E_SHAPE;   // the image's rows occupy [first_row, first_row + rows) of the usable rows
-    if (out_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 || (out_elem_stride & 15) || (reinterpret_cast<u64>(a_in_out) & 15)) return H2R_E_SHAPE;
+    if (out_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 || misaligned(a_in_out, out_elem_stride)) return H2R_E_SHAPE;
     LookupInputArgs ia;
     std::memset(static_cast<void *>(&ia), 0, sizeof ia);
     if (const int32_t rc = advice_dst(ctx, const_cast<void *>(image), image_stride, rows, batch, &ia.img)) return rc;
@@ -4062,21 +4085,18 @@ int32_t h2r_lookup_input_columns(const h2r_ctx *ctx, const h2r_lookup_config *cf
     ia.kinds = kinds_dev; ia.rows = rows; ia.usable_rows = usable_rows; ia.first_row = first_row; ia.arg_mask = arg_mask & 31u;
     ia.n_lens = cfg->n_lens;
     for (u32 i = 0; i < cfg->n_lens; ++i) ia.tag[i] = cfg->tag[i];
-    for (int k = 0; k < 4; ++k) ia.p[k] = ctx->fc.p[k];
+    std::memcpy(ia.p, ctx->fc.p, sizeof ia.p);
     ia.out_elem_stride = out_elem_stride;
-    const u64 per = lookup_launch_elems((u64)LOOKUP_ARGS * ((usable_rows + 255) / 256), 256);
+    const u64 per = slice_items((u64)LOOKUP_ARGS * ((usable_rows + 255) / 256), batch);   // circuits per launch (grid.z)
     if (!per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (u64 e0 = 0; e0 < batch; e0 += per) {
-        const u64 ne = std::min(per, batch - e0);
+    return for_each_slice(batch, per, [&](u64 e0, u64 ne) {
         ia.img.base = static_cast<u8 *>(const_cast<void *>(image)) + e0 * ia.img.elem_stride;
         ia.status = status ? status + e0 : nullptr; ia.theta = theta + 4 * e0;
         ia.out = static_cast<u8 *>(a_in_out) + e0 * out_elem_stride;
-        ProfScope ps(H2R_KERNEL_LOOKUP_INPUT, st, true);
-        HIP_TRY(launch_lookup_input(ia, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
-    }
-    return H2R_OK;
+        return stage_launch(H2R_KERNEL_LOOKUP_INPUT, st, [&](hipEvent_t a, hipEvent_t b) { return launch_lookup_input(ia, (u32)ne, st, a, b); });
+    });
 } H2R_CATCH_STATUS
 
 uint64_t h2r_lookup_product_workspace_bytes(uint32_t usable_rows, uint64_t num_elems) try {
@@ -4090,41 +4110,36 @@ int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *
     if (!ctx || !cfg || !a_in || !a_perm || !s_perm || !theta || !beta || !gamma || !z_out || !workspace) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     if (!lookup_cfg_valid(cfg)) return H2R_E_SHAPE;
-    if (!usable_rows || usable_rows > kLookupMaxUsableRows || in_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 || (in_elem_stride & 15) || (reinterpret_cast<u64>(a_in) & 15) ||
-        (reinterpret_cast<u64>(a_perm) & 15) || (reinterpret_cast<u64>(s_perm) & 15)) return H2R_E_SHAPE;
+    if (!usable_rows || usable_rows > kLookupMaxUsableRows || in_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 ||
+        misaligned(a_in, in_elem_stride) || misaligned(a_perm) || misaligned(s_perm)) return H2R_E_SHAPE;
     const u64 zcol = ((u64)usable_rows + 1) * 32;
-    if (z_col_stride < zcol || (z_col_stride & 31) || (z_elem_stride & 15) || (reinterpret_cast<u64>(z_out) & 15)) return H2R_E_SHAPE;
+    if (z_col_stride < zcol || (z_col_stride & 31) || misaligned(z_out, z_elem_stride)) return H2R_E_SHAPE;
     if (num_elems > 65535) return H2R_E_UNSUPPORTED;
-    // [element][argument] (z_elem_stride covers the five columns) or [argument][element] (z_col_stride covers every element)
-    const bool elem_major = z_elem_stride >= (LOOKUP_ARGS - 1) * z_col_stride + zcol;
-    const bool col_major = num_elems == 0 || (z_elem_stride >= zcol && z_col_stride >= (num_elems - 1) * z_elem_stride + zcol);
-    if (!elem_major && !col_major) return H2R_E_SHAPE;
+    // [element][argument] or [argument][element]; without elements the strides are not looked at
+    if (num_elems && !ColumnBlock{z_out, zcol, z_elem_stride, z_col_stride, LOOKUP_ARGS, num_elems}.disjoint()) return H2R_E_SHAPE;
     if (num_elems == 0 || !(arg_mask & 31u)) return H2R_OK;
     LookupProductArgs pa;
     std::memset(static_cast<void *>(&pa), 0, sizeof pa);
     pa.in_elem_stride = in_elem_stride; pa.usable_rows = usable_rows; pa.n_tiles = lookup_product_tiles(usable_rows); pa.arg_mask = arg_mask & 31u;
-    pa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;
+    pa.mont = ctx_mont(ctx);
     pa.n_rows = cfg->n_rows; pa.n_lens = cfg->n_lens;
     for (u32 i = 0; i < cfg->n_lens; ++i) { pa.tag[i] = cfg->tag[i]; pa.row_off[i] = cfg->row_off[i]; }
     pa.f = ctx->fc; pa.z_elem_stride = z_elem_stride; pa.z_col_stride = z_col_stride;
-    const u64 per = lookup_launch_elems((u64)LOOKUP_ARGS * pa.n_tiles, 256);
+    const u64 per = slice_items((u64)LOOKUP_ARGS * pa.n_tiles, num_elems);   // circuits per launch (grid.z)
     if (!per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
-    for (u64 e0 = 0; e0 < num_elems; e0 += per) {
-        const u64 ne = std::min(per, num_elems - e0);
+    u8 *ws = workspace_256(workspace);
+    return for_each_slice(num_elems, per, [&](u64 e0, u64 ne) -> int32_t {
         pa.a_in = static_cast<const u8 *>(a_in) + e0 * in_elem_stride; pa.a_perm = static_cast<const u8 *>(a_perm) + e0 * in_elem_stride;
         pa.s_perm = static_cast<const u8 *>(s_perm) + e0 * in_elem_stride;
         pa.theta = theta + 4 * e0; pa.beta = beta + 4 * e0; pa.gamma = gamma + 4 * e0;
         pa.z = static_cast<u8 *>(z_out) + e0 * z_elem_stride; pa.status = status ? status + e0 : nullptr;
         pa.ws = ws + e0 * LOOKUP_ARGS * lookup_product_slot_bytes(usable_rows);
-        for (u32 phase = 0; phase < 3; ++phase) {
-            ProfScope ps(H2R_KERNEL_LOOKUP_PRODUCT_TILES + phase, st, true);
-            HIP_TRY(launch_lookup_product(phase, pa, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
-        }
-    }
-    return H2R_OK;
+        for (u32 phase = 0; phase < 3; ++phase)
+            if (const int32_t rc = stage_launch(H2R_KERNEL_LOOKUP_PRODUCT_TILES + phase, st, [&](hipEvent_t a, hipEvent_t b) { return launch_lookup_product(phase, pa, (u32)ne, st, a, b); })) return rc;
+        return H2R_OK;
+    });
 } H2R_CATCH_STATUS
 
 // ---- the permutation argument's grand-product columns Z (h2r_permutation_product.hpp, h2r_tu_permutation_product.hip) ------------------------
@@ -4169,17 +4184,14 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
     if (ge_p(cfg->delta, ctx->fc.p) || ge_p(cfg->omega, ctx->fc.p)) return H2R_E_SHAPE;
     if (!usable_rows || usable_rows > kLookupMaxUsableRows) return H2R_E_SHAPE;
     if ((u64)first_row + rows > usable_rows) return H2R_E_SHAPE;   // the image's rows occupy [first_row, first_row + rows) of the usable rows
-    auto misaligned = [](const void *p, u64 s0, u64 s1) { return ((reinterpret_cast<u64>(p) | s0 | s1) & 15) != 0; };
-    if (misaligned(image, image_stride, 0) || misaligned(sigma, sigma_col_stride, 0) || misaligned(z_out, z_elem_stride, z_col_stride)) return H2R_E_SHAPE;
+    if (misaligned(image, image_stride) || misaligned(sigma, sigma_col_stride) || misaligned(z_out, z_elem_stride, z_col_stride)) return H2R_E_SHAPE;
     if (cfg->n_extra && misaligned(extra, extra_elem_stride, extra_col_stride)) return H2R_E_SHAPE;
     if (sigma_col_stride < (u64)usable_rows * 32) return H2R_E_SHAPE;
     const u32 S = perm_sets(cfg);
     const u64 zcol = ((u64)usable_rows + 1) * 32;
     if (z_col_stride < zcol || (z_col_stride & 31)) return H2R_E_SHAPE;
-    // [element][set] (z_elem_stride covers the S columns) or [set][element] (z_col_stride covers every element)
-    const bool elem_major = z_elem_stride >= (S - 1) * z_col_stride + zcol;
-    const bool col_major = batch == 0 || (z_elem_stride >= zcol && z_col_stride >= (batch - 1) * z_elem_stride + zcol);
-    if (!elem_major && !col_major) return H2R_E_SHAPE;
+    // [element][set] or [set][element]; without elements the strides are not looked at
+    if (batch && !ColumnBlock{z_out, zcol, z_elem_stride, z_col_stride, S, batch}.disjoint()) return H2R_E_SHAPE;
     PermProductArgs pa;
     std::memset(static_cast<void *>(&pa), 0, sizeof pa);
     if (const int32_t rc = advice_dst(ctx, const_cast<void *>(image), image_stride, rows, batch, &pa.img)) return rc;
@@ -4191,34 +4203,27 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
     pa.m = cfg->num_columns; pa.chunk_len = std::min<u32>(cfg->chunk_len, cfg->num_columns); pa.n_sets = S;
     for (u32 c = 0; c < cfg->num_columns; ++c) pa.src[c] = cfg->column_src[c];
     // delta^c and omega^(2^b) in Montgomery form, whichever form the configuration holds them in
-    Fe delta, omega;
-    for (int k = 0; k < 4; ++k) { delta.v[k] = cfg->delta[k]; omega.v[k] = cfg->omega[k]; pa.dpow[0].v[k] = f.one[k]; }
-    if (!pa.mont) { delta = fe_to_mont(delta, f); omega = fe_to_mont(omega, f); }
-    for (u32 c = 1; c < PERM_MAX_COLUMNS; ++c) pa.dpow[c] = fe_mont_mul(pa.dpow[c - 1], delta, f);
-    pa.wpow[0] = omega;
-    for (u32 b = 1; b < PERM_OMEGA_BITS; ++b) pa.wpow[b] = fe_mont_mul(pa.wpow[b - 1], pa.wpow[b - 1], f);
+    fe_power_table(pa.dpow, PERM_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), f);
+    fe_squaring_chain(pa.wpow, PERM_OMEGA_BITS, cfg_to_mont(ctx, cfg->omega), f);
     pa.f = f;
     pa.extra_elem_stride = cfg->n_extra ? extra_elem_stride : 0; pa.extra_col_stride = cfg->n_extra ? extra_col_stride : 0;
     pa.sigma = static_cast<const u8 *>(sigma); pa.sigma_col_stride = sigma_col_stride;
     pa.z_elem_stride = z_elem_stride; pa.z_col_stride = z_col_stride;
-    const u64 per = lookup_launch_elems((u64)S * pa.n_tiles, 256);
+    const u64 per = slice_items((u64)S * pa.n_tiles, batch);   // circuits per launch (grid.z)
     if (!per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    u8 *ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
-    for (u64 e0 = 0; e0 < batch; e0 += per) {
-        const u64 ne = std::min(per, batch - e0);
+    u8 *ws = workspace_256(workspace);
+    return for_each_slice(batch, per, [&](u64 e0, u64 ne) -> int32_t {
         pa.img.base = static_cast<u8 *>(const_cast<void *>(image)) + e0 * pa.img.elem_stride;
         pa.extra = cfg->n_extra ? static_cast<const u8 *>(extra) + e0 * extra_elem_stride : nullptr;
         pa.beta = beta + 4 * e0; pa.gamma = gamma + 4 * e0;
         pa.z = static_cast<u8 *>(z_out) + e0 * z_elem_stride; pa.status = status ? status + e0 : nullptr;
         pa.ws = ws + e0 * perm_product_slot_bytes(usable_rows, S);
-        for (u32 phase = 0; phase < 3; ++phase) {
-            ProfScope ps(H2R_KERNEL_PERM_PRODUCT_TILES + phase, st, true);
-            HIP_TRY(launch_perm_product(phase, pa, (u32)ne, st, ps.a, ps.on ? ps.b : nullptr));
-        }
-    }
-    return H2R_OK;
+        for (u32 phase = 0; phase < 3; ++phase)
+            if (const int32_t rc = stage_launch(H2R_KERNEL_PERM_PRODUCT_TILES + phase, st, [&](hipEvent_t a, hipEvent_t b) { return launch_perm_product(phase, pa, (u32)ne, st, a, b); })) return rc;
+        return H2R_OK;
+    });
 } H2R_CATCH_STATUS
 
 // ---- the evaluation domain's transforms (h2r_ntt.hpp, h2r_tu_ntt.hip) -------------------------------------------------------------------
@@ -4231,16 +4236,6 @@ int32_t ntt_cfg_status(const h2r_ntt_config *cfg) {
     if ((cfg->flags & H2R_NTT_INVERSE) && cfg->log_n_in != cfg->log_n_out) return H2R_E_SHAPE;
     if (!(cfg->shift[0] | cfg->shift[1] | cfg->shift[2] | cfg->shift[3])) return H2R_E_SHAPE;
     return H2R_OK;
-}
-// num_cols x batch columns of `col` bytes: strides that hold a column, and columns that do not overlap each other
-bool ntt_columns_disjoint(u64 col, u64 elem_stride, u64 col_stride, u32 num_cols, u64 batch) {
-    if (elem_stride < col || col_stride < col) return false;
-    const u128 elem_major = (u128)(num_cols - 1) * col_stride + col, col_major = batch ? (u128)(batch - 1) * elem_stride + col : 0;
-    return elem_stride >= elem_major || col_stride >= col_major;
-}
-// bytes from the first column's first byte to the last column's last one
-u128 ntt_extent(u64 col, u64 elem_stride, u64 col_stride, u32 num_cols, u64 batch) {
-    return batch ? (u128)(batch - 1) * elem_stride + (u128)(num_cols - 1) * col_stride + col : 0;
 }
 }  // namespace
 
@@ -4256,54 +4251,39 @@ int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const voi
     if (num_cols == 0) return H2R_E_SHAPE;
     const FieldConsts &f = ctx->fc;
     if (ge_p(cfg->omega, f.p) || ge_p(cfg->shift, f.p)) return H2R_E_SHAPE;
-    const bool mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0, inverse = (cfg->flags & H2R_NTT_INVERSE) != 0;
+    const bool mont = ctx_mont(ctx), inverse = (cfg->flags & H2R_NTT_INVERSE) != 0;
     const u32 log_n = cfg->log_n_out, log_m = cfg->log_n_in;
-    const Fe one = [&] { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = f.one[k]; return r; }();
-    Fe omega, shift;   // Montgomery form from here on
-    for (int k = 0; k < 4; ++k) { omega.v[k] = cfg->omega[k]; shift.v[k] = cfg->shift[k]; }
-    if (!mont) { omega = fe_to_mont(omega, f); shift = fe_to_mont(shift, f); }
-    {   // a primitive 2^log_n-th root of unity: omega^(n / 2) = -1
-        Fe x = omega;
-        for (u32 b = 1; b < log_n; ++b) x = fe_mont_mul(x, x, f);
-        if (!fe_is_zero(fe_add(x, one, f.p))) return H2R_E_SHAPE;
-    }
-    auto misaligned = [](const void *p, u64 s0, u64 s1) { return ((reinterpret_cast<u64>(p) | s0 | s1) & 15) != 0; };
+    const Fe one = fe_one(f), omega = cfg_to_mont(ctx, cfg->omega), shift = cfg_to_mont(ctx, cfg->shift);   // Montgomery form from here on
+    if (!is_primitive_root(omega, log_n, f)) return H2R_E_SHAPE;
     if (misaligned(in, in_elem_stride, in_col_stride) || misaligned(out, out_elem_stride, out_col_stride)) return H2R_E_SHAPE;
-    const u64 in_col = 32ull << log_m, out_col = 32ull << log_n;
-    if (!ntt_columns_disjoint(in_col, in_elem_stride, in_col_stride, num_cols, batch) ||
-        !ntt_columns_disjoint(out_col, out_elem_stride, out_col_stride, num_cols, batch)) return H2R_E_SHAPE;
-    {   // the passes after the first work in place in `out` while other workgroups still read `in`: the two ranges are disjoint
-        const u128 i0 = reinterpret_cast<u64>(in), o0 = reinterpret_cast<u64>(out);
-        const u128 i1 = i0 + ntt_extent(in_col, in_elem_stride, in_col_stride, num_cols, batch);
-        const u128 o1 = o0 + ntt_extent(out_col, out_elem_stride, out_col_stride, num_cols, batch);
-        if (i0 < o1 && o0 < i1) return H2R_E_SHAPE;
-    }
+    const ColumnBlock in_cols{in, 32ull << log_m, in_elem_stride, in_col_stride, num_cols, batch};
+    const ColumnBlock out_cols{out, 32ull << log_n, out_elem_stride, out_col_stride, num_cols, batch};
+    // the passes after the first work in place in `out` while other workgroups still read `in`: the two ranges are disjoint
+    if (!in_cols.disjoint() || !out_cols.disjoint() || overlaps(in_cols, out_cols)) return H2R_E_SHAPE;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     if (batch == 0) return H2R_OK;
 
     const NttPlan pl = ntt_plan(log_n);
     auto inv = [&](const Fe &x) { return fe_to_mont(fe_inv(fe_from_mont(x, f), f), f); };   // x is x * R: back to the integer, invert, forth
-    auto pow2k = [&](Fe x, u32 k) { for (u32 b = 0; b < k; ++b) x = fe_mont_mul(x, x, f); return x; };
     const bool coset = !fe_eq(shift, one);
     const Fe w = inverse ? inv(omega) : omega, g = inverse ? inv(shift) : shift;
     NttSetupArgs sa;
     std::memset(static_cast<void *>(&sa), 0, sizeof sa);
-    auto table = [&](u32 t, Fe base, const Fe &first, u64 count) {
+    auto table = [&](u32 t, const Fe &base, const Fe &first, u64 count) {
         sa.first[t] = first;
         sa.count[t] = (u32)std::min<u64>(NTT_SPLIT, (count + 3) & ~3ull);
-        for (u32 b = 0; b < NTT_SPLIT_LOG; ++b) { sa.pow2[t][b] = base; base = fe_mont_mul(base, base, f); }
+        fe_squaring_chain(sa.pow2[t], NTT_SPLIT_LOG, base, f);
     };
-    table(0, pow2k(w, log_n - pl.smax), one, 1ull << (pl.smax - 1));
+    table(0, fe_pow2k(w, log_n - pl.smax, f), one, 1ull << (pl.smax - 1));
     if (pl.passes > 1) {
         table(1, w, one, 1ull << log_n);
-        if (log_n > NTT_SPLIT_LOG) table(2, pow2k(w, NTT_SPLIT_LOG), one, 1ull << (log_n - NTT_SPLIT_LOG));
+        if (log_n > NTT_SPLIT_LOG) table(2, fe_pow2k(w, NTT_SPLIT_LOG, f), one, 1ull << (log_n - NTT_SPLIT_LOG));
     }
     NttArgs na;
     std::memset(static_cast<void *>(&na), 0, sizeof na);
     // the first load and the last store: a canonical ctx converts there (x * R^2 -> the Montgomery form, x * 1 -> the integer), within the
     // product that applies g^i (forward, on the load) or n^-1 * g^-i (inverse, on the store) where there is one
-    const Fe r2 = [&] { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = f.r2[k]; return r; }();
-    na.load_mode = mont ? NTT_F_NONE : NTT_F_CONST; na.load_const = r2;
+    na.load_mode = mont ? NTT_F_NONE : NTT_F_CONST; na.load_const = fe_r2(f);
     na.store_mode = mont ? NTT_F_NONE : NTT_F_CONST; na.store_const = fe_small(1);
     if (inverse) {
         Fe ninv = inv(fe_to_mont(fe_small(1ull << log_n), f));
@@ -4311,44 +4291,36 @@ int32_t h2r_ntt_columns(const h2r_ctx *ctx, const h2r_ntt_config *cfg, const voi
         na.store_mode = coset ? NTT_F_TABLE : NTT_F_CONST; na.store_const = ninv;
         if (coset) {
             table(3, g, ninv, 1ull << log_n);
-            if (log_n > NTT_SPLIT_LOG) table(4, pow2k(g, NTT_SPLIT_LOG), one, 1ull << (log_n - NTT_SPLIT_LOG));
+            if (log_n > NTT_SPLIT_LOG) table(4, fe_pow2k(g, NTT_SPLIT_LOG, f), one, 1ull << (log_n - NTT_SPLIT_LOG));
         }
     } else if (coset) {
         na.load_mode = NTT_F_TABLE;
         table(3, g, mont ? one : fe_to_mont(one, f), 1ull << log_m);
-        if (log_m > NTT_SPLIT_LOG) table(4, pow2k(g, NTT_SPLIT_LOG), one, 1ull << (log_m - NTT_SPLIT_LOG));
+        if (log_m > NTT_SPLIT_LOG) table(4, fe_pow2k(g, NTT_SPLIT_LOG, f), one, 1ull << (log_m - NTT_SPLIT_LOG));
     }
     sa.f = f; na.f = f;
     na.log_n = log_n; na.log_m = log_m; na.passes = pl.passes; na.smax = pl.smax;
     for (u32 q = 0; q < NTT_MAX_PASSES; ++q) na.s[q] = pl.s[q];
     na.in_elem_stride = in_elem_stride; na.in_col_stride = in_col_stride; na.out_elem_stride = out_elem_stride; na.out_col_stride = out_col_stride;
-    // launches below the 2^32 global size and the 65,535 of a grid's y and z: slices of columns, then of elements
-    const u64 max_blocks = ((1ull << 32) - 1) / 256;
+    // slices of columns (grid.y), then of elements (grid.z)
     u64 tiles = 0;
     for (u32 q = 0; q < pl.passes; ++q) tiles = std::max<u64>(tiles, ntt_pass_tiles(log_n, pl.s[q]));
-    const u64 cols_per = std::min<u64>({num_cols, 65535, max_blocks / tiles});
-    const u64 elems_per = std::min<u64>({batch, 65535, max_blocks / (tiles * cols_per)});
+    const u64 cols_per = slice_items(tiles, num_cols), elems_per = slice_items(tiles * cols_per, batch);
     if (!cols_per || !elems_per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    sa.tab = reinterpret_cast<Fe *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    sa.tab = reinterpret_cast<Fe *>(workspace_256(workspace));
     na.tab = sa.tab;
-    {
-        ProfScope ps(H2R_KERNEL_NTT_SETUP, st, true);
-        HIP_TRY(launch_ntt_setup(sa, st, ps.a, ps.on ? ps.b : nullptr));
-    }
-    for (u64 e0 = 0; e0 < batch; e0 += elems_per) {
-        for (u64 c0 = 0; c0 < num_cols; c0 += cols_per) {
+    if (const int32_t rc = stage_launch(H2R_KERNEL_NTT_SETUP, st, [&](hipEvent_t a, hipEvent_t b) { return launch_ntt_setup(sa, st, a, b); })) return rc;
+    return for_each_slice(batch, elems_per, [&](u64 e0, u64 ne) {
+        return for_each_slice(num_cols, cols_per, [&](u64 c0, u64 nc) -> int32_t {
             na.in = static_cast<const u8 *>(in) + e0 * in_elem_stride + c0 * in_col_stride;
             na.out = static_cast<u8 *>(out) + e0 * out_elem_stride + c0 * out_col_stride;
-            for (u32 q = 0; q < pl.passes; ++q) {
-                na.pass = q;
-                ProfScope ps(H2R_KERNEL_NTT_PASS, st, true);
-                HIP_TRY(launch_ntt_pass(na, (u32)std::min<u64>(cols_per, num_cols - c0), (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
-            }
-        }
-    }
-    return H2R_OK;
+            for (na.pass = 0; na.pass < pl.passes; ++na.pass)
+                if (const int32_t rc = stage_launch(H2R_KERNEL_NTT_PASS, st, [&](hipEvent_t a, hipEvent_t b) { return launch_ntt_pass(na, (u32)nc, (u32)ne, st, a, b); })) return rc;
+            return H2R_OK;
+        });
+    });
 } H2R_CATCH_STATUS
 
 // ---- the vanishing argument's quotient on the extended domain (h2r_quotient.hpp, h2r_tu_quotient.hip) -------------------------------------
@@ -4412,20 +4384,15 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
     const FieldConsts &f = ctx->fc;
     if (ge_p(cfg->omega_ext, f.p) || ge_p(cfg->zeta, f.p) || ge_p(cfg->delta, f.p)) return H2R_E_SHAPE;
     if (!(cfg->zeta[0] | cfg->zeta[1] | cfg->zeta[2] | cfg->zeta[3])) return H2R_E_SHAPE;
-    const bool mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0;
+    const bool mont = ctx_mont(ctx);
     const u32 log_n = cfg->log_n, log_ext = cfg->log_ext, scale_log = log_ext - log_n, r = 1u << scale_log;
-    const Fe one = [&] { Fe x; for (int k = 0; k < 4; ++k) x.v[k] = f.one[k]; return x; }();
-    Fe omega, zeta, delta;   // Montgomery form from here on
-    for (int k = 0; k < 4; ++k) { omega.v[k] = cfg->omega_ext[k]; zeta.v[k] = cfg->zeta[k]; delta.v[k] = cfg->delta[k]; }
-    if (!mont) { omega = fe_to_mont(omega, f); zeta = fe_to_mont(zeta, f); delta = fe_to_mont(delta, f); }
+    const Fe one = fe_one(f), omega = cfg_to_mont(ctx, cfg->omega_ext), zeta = cfg_to_mont(ctx, cfg->zeta);   // Montgomery form from here on
     QuotientArgs qa;
     std::memset(static_cast<void *>(&qa), 0, sizeof qa);
-    qa.wpow[0] = omega;
-    for (u32 b = 1; b < QUOT_MAX_LOG; ++b) qa.wpow[b] = fe_mont_mul(qa.wpow[b - 1], qa.wpow[b - 1], f);
-    if (!fe_is_zero(fe_add(qa.wpow[log_ext - 1], one, f.p))) return H2R_E_SHAPE;   // a primitive N-th root of unity: omega_ext^(N / 2) = -1
+    fe_squaring_chain(qa.wpow, QUOT_MAX_LOG, omega, f);
+    if (!is_primitive_root(omega, log_ext, f)) return H2R_E_SHAPE;
     {   // X_j^n = zeta^n * (omega_ext^n)^(j mod r): none of them may be 1
-        Fe zn = zeta;
-        for (u32 b = 0; b < log_n; ++b) zn = fe_mont_mul(zn, zn, f);
+        Fe zn = fe_pow2k(zeta, log_n, f);
         const Fe wn = qa.wpow[log_n];
         for (u32 i = 0; i < r; ++i) {
             const Fe d = fe_sub(zn, one, f.p);
@@ -4442,18 +4409,13 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
     const Group groups[9] = {{&in->advice, 5, true}, {&in->extra, cfg->n_extra, true}, {&in->perm_z, S, true}, {&in->lookup_a_perm, nl, true},
                              {&in->lookup_s_perm, nl, true}, {&in->lookup_z, nl, true}, {&in->fixed, cfg->num_fixed, false},
                              {&in->sigma, cfg->num_columns, false}, {&in->l, 3, false}};
-    if (((reinterpret_cast<u64>(h_out) | h_elem_stride) & 15) || h_elem_stride < col) return H2R_E_SHAPE;
-    const u128 h0 = reinterpret_cast<u64>(h_out), h1 = h0 + ntt_extent(col, h_elem_stride, col, 1, batch);
+    if (misaligned(h_out, h_elem_stride) || h_elem_stride < col) return H2R_E_SHAPE;
+    const ColumnBlock h{h_out, col, h_elem_stride, col, 1, batch};
     for (const Group &gr : groups) {
         if (!gr.cols) continue;
-        const u64 es = gr.per_circuit ? gr.g->elem_stride : 0, cs = gr.g->col_stride;
-        if ((reinterpret_cast<u64>(gr.g->base) | es | cs) & 15) return H2R_E_SHAPE;
-        if (cs < col) return H2R_E_SHAPE;
-        if (gr.per_circuit && !ntt_columns_disjoint(col, es, cs, gr.cols, batch)) return H2R_E_SHAPE;
-        // rotated reads come from other workgroups' ranges: h may overlap no input
-        const u128 g0 = reinterpret_cast<u64>(gr.g->base);
-        const u128 g1 = g0 + (gr.per_circuit ? ntt_extent(col, es, cs, gr.cols, batch) : (batch ? (u128)(gr.cols - 1) * cs + col : 0));
-        if (g0 < h1 && h0 < g1) return H2R_E_SHAPE;
+        const ColumnBlock g{gr.g->base, col, gr.per_circuit ? gr.g->elem_stride : 0, gr.g->col_stride, gr.cols, batch};   // (a key's columns: one set for every circuit)
+        if (misaligned(g.base, g.elem_stride, g.col_stride) || g.col_stride < col || (gr.per_circuit && !g.disjoint())) return H2R_E_SHAPE;
+        if (overlaps(g, h)) return H2R_E_SHAPE;   // rotated reads come from other workgroups' ranges: h may overlap no input
     }
     if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
     if (batch == 0) return H2R_OK;
@@ -4475,21 +4437,17 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
     std::memcpy(qa.lookup_advice, cfg->lookup_advice, sizeof qa.lookup_advice); std::memcpy(qa.lookup_tag, cfg->lookup_tag, sizeof qa.lookup_tag);
     std::memcpy(qa.lookup_enable, cfg->lookup_enable, sizeof qa.lookup_enable);
     qa.table_tag = cfg->table_tag; qa.table_value = cfg->table_value;
-    qa.dpow[0] = one;
-    for (u32 c = 1; c < QUOT_PERM_MAX_COLUMNS; ++c) qa.dpow[c] = fe_mont_mul(qa.dpow[c - 1], delta, f);
+    fe_power_table(qa.dpow, QUOT_PERM_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), f);
     qa.zeta = zeta; qa.f = f;
-    // launches below the 2^32 global size: slices of tiles (a grid's x holds the circuits, at most 65,535)
-    const u64 tiles = quotient_tiles(log_ext), max_blocks = ((1ull << 32) - 1) / 256;
-    const u64 tiles_per = std::min<u64>({tiles, 65535, max_blocks / batch});
+    // slices of tiles (a grid's x holds the circuits, at most 65,535)
+    const u64 tiles = quotient_tiles(log_ext), tiles_per = slice_items(batch, tiles);
     if (!tiles_per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (u64 t0 = 0; t0 < tiles; t0 += tiles_per) {
+    return for_each_slice(tiles, tiles_per, [&](u64 t0, u64 nt) {
         qa.tile0 = (u32)t0;
-        ProfScope ps(H2R_KERNEL_QUOTIENT, st, true);
-        HIP_TRY(launch_quotient(qa, (u32)std::min<u64>(tiles_per, tiles - t0), (u32)batch, st, ps.a, ps.on ? ps.b : nullptr));
-    }
-    return H2R_OK;
+        return stage_launch(H2R_KERNEL_QUOTIENT, st, [&](hipEvent_t a, hipEvent_t b) { return launch_quotient(qa, (u32)nt, (u32)batch, st, a, b); });
+    });
 } H2R_CATCH_STATUS
 
 // ---- the openings: fold, evaluations at x, GWC witness polynomials (h2r_open.hpp, h2r_tu_open.hip) -----------------------------------------
@@ -4526,23 +4484,17 @@ int32_t open_args(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open
             if (!cols[c].base) return H2R_E_NULL;
     if (const int32_t rc = open_cfg_status(cfg, cols)) return rc;
     const u64 col = 32ull * cfg->n_coeffs;
-    for (u32 c = 0; c < cfg->num_cols; ++c) {
-        if ((reinterpret_cast<u64>(cols[c].base) | cols[c].elem_stride) & 15) return H2R_E_SHAPE;
-        if (cols[c].elem_stride && cols[c].elem_stride < col) return H2R_E_SHAPE;
-    }
+    for (u32 c = 0; c < cfg->num_cols; ++c)
+        if (misaligned(cols[c].base, cols[c].elem_stride) || (cols[c].elem_stride && cols[c].elem_stride < col)) return H2R_E_SHAPE;
     if (w_out) {
-        if ((reinterpret_cast<u64>(w_out) | w_elem_stride | w_point_stride) & 15) return H2R_E_SHAPE;
-        if (!ntt_columns_disjoint(col, w_elem_stride, w_point_stride, cfg->num_points, batch)) return H2R_E_SHAPE;
+        if (misaligned(w_out, w_elem_stride, w_point_stride)) return H2R_E_SHAPE;
+        const ColumnBlock w{w_out, col, w_elem_stride, w_point_stride, cfg->num_points, batch};
+        if (!w.disjoint()) return H2R_E_SHAPE;
         // the scans write W[i - 1] while other workgroups still read the columns: W may overlap no input
-        const u128 w0 = reinterpret_cast<u64>(w_out), w1 = w0 + ntt_extent(col, w_elem_stride, w_point_stride, cfg->num_points, batch);
-        for (u32 c = 0; c < cfg->num_cols; ++c) {
-            const u128 c0 = reinterpret_cast<u64>(cols[c].base), c1 = c0 + (batch ? (u128)(batch - 1) * cols[c].elem_stride + col : 0);
-            if (c0 < w1 && w0 < c1) return H2R_E_SHAPE;
-        }
-        for (const OpenRange &r : others) {   // ... nor the points, v, batch_evals or the workspace
-            const u128 r0 = reinterpret_cast<u64>(r.p), r1 = r0 + (batch ? r.bytes : 0);
-            if (r.p && r0 < w1 && w0 < r1) return H2R_E_SHAPE;
-        }
+        for (u32 c = 0; c < cfg->num_cols; ++c)
+            if (overlaps(w, ColumnBlock{cols[c].base, col, cols[c].elem_stride, col, 1, batch})) return H2R_E_SHAPE;
+        for (const OpenRange &r : others)   // ... nor the points, v, batch_evals or the workspace
+            if (r.p && overlaps(w, r.p, batch ? r.bytes : 0)) return H2R_E_SHAPE;
     }
     if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
     std::memset(static_cast<void *>(&oa), 0, sizeof oa);
@@ -4555,24 +4507,22 @@ int32_t open_args(const h2r_ctx *ctx, const h2r_open_config *cfg, const h2r_open
     }
     for (u32 p = 0; p < OPEN_MAX_POINTS; ++p) oa.point_cols[p] = (u8)per_point[p];
     oa.n_coeffs = cfg->n_coeffs; oa.n_tiles = open_tiles_of(cfg->n_coeffs); oa.num_cols = cfg->num_cols; oa.num_points = cfg->num_points;
-    oa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;
+    oa.mont = ctx_mont(ctx);
     oa.slot_bytes = open_slot_bytes(cfg->n_coeffs, std::max<u32>(oa.n_queries, cfg->num_points));
     oa.f = ctx->fc;
     return H2R_OK;
 }
 // phases [0, n_phases) over the circuits, sliced below the 2^32 global size and the 65,535 of a grid's z
 int32_t open_launch(const h2r_ctx *ctx, OpenArgs &oa, u32 n_phases, uint64_t batch, void *workspace, hipStream_t st) {
-    const u64 max_blocks = ((1ull << 32) - 1) / 256, per_elem = (u64)oa.n_tiles * (oa.witness ? oa.num_points : 1u);
-    const u64 elems_per = std::min<u64>({batch, 65535, max_blocks / per_elem});
+    const u64 elems_per = slice_items((u64)oa.n_tiles * (oa.witness ? oa.num_points : 1u), batch);
     if (!elems_per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
-    oa.ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    oa.ws = workspace_256(workspace);
     for (u32 phase = 0; phase < n_phases; ++phase)
-        for (u64 e0 = 0; e0 < batch; e0 += elems_per) {
-            oa.elem0 = (u32)e0;
-            ProfScope ps(H2R_KERNEL_OPEN_TILES + phase, st, true);
-            HIP_TRY(launch_open(phase, oa, (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
-        }
+        if (const int32_t rc = for_each_slice(batch, elems_per, [&](u64 e0, u64 ne) {
+                oa.elem0 = (u32)e0;
+                return stage_launch(H2R_KERNEL_OPEN_TILES + phase, st, [&](hipEvent_t a, hipEvent_t b) { return launch_open(phase, oa, (u32)ne, st, a, b); });
+            })) return rc;
     return H2R_OK;
 }
 }  // namespace
@@ -4625,32 +4575,25 @@ int32_t h2r_fold_columns(const h2r_ctx *ctx, const void *in, uint64_t in_elem_st
     if (!ctx || !in || !s || !out) return H2R_E_NULL;
     if (n_coeffs == 0 || n_coeffs > OPEN_MAX_COEFFS || num_cols == 0 || num_cols > OPEN_MAX_COLUMNS) return H2R_E_SHAPE;
     const u64 col = 32ull * n_coeffs;
-    if ((reinterpret_cast<u64>(in) | in_elem_stride | in_col_stride | reinterpret_cast<u64>(out) | out_elem_stride) & 15) return H2R_E_SHAPE;
-    if (!ntt_columns_disjoint(col, in_elem_stride, in_col_stride, num_cols, batch) || out_elem_stride < col) return H2R_E_SHAPE;
-    {
-        const u128 i0 = reinterpret_cast<u64>(in), o0 = reinterpret_cast<u64>(out);
-        const u128 i1 = i0 + ntt_extent(col, in_elem_stride, in_col_stride, num_cols, batch), o1 = o0 + ntt_extent(col, out_elem_stride, col, 1, batch);
-        if (i0 < o1 && o0 < i1) return H2R_E_SHAPE;
-    }
+    if (misaligned(in, in_elem_stride, in_col_stride) || misaligned(out, out_elem_stride)) return H2R_E_SHAPE;
+    const ColumnBlock in_cols{in, col, in_elem_stride, in_col_stride, num_cols, batch}, out_cols{out, col, out_elem_stride, col, 1, batch};
+    if (!in_cols.disjoint() || out_elem_stride < col || overlaps(in_cols, out_cols)) return H2R_E_SHAPE;
     if (ctx->params.device < 0 || batch > 65535) return H2R_E_UNSUPPORTED;
     if (batch == 0) return H2R_OK;
     FoldArgs fa;
     std::memset(static_cast<void *>(&fa), 0, sizeof fa);
     fa.in = static_cast<const u8 *>(in); fa.in_elem_stride = in_elem_stride; fa.in_col_stride = in_col_stride;
     fa.s = s; fa.status = status; fa.out = static_cast<u8 *>(out); fa.out_elem_stride = out_elem_stride;
-    fa.n_coeffs = n_coeffs; fa.num_cols = num_cols; fa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u; fa.f = ctx->fc;
-    // launches below the 2^32 global size: slices of tiles (a grid's x holds the circuits, at most 65,535)
-    const u64 tiles = (n_coeffs + FOLD_TILE - 1) / FOLD_TILE, max_blocks = ((1ull << 32) - 1) / 256;
-    const u64 tiles_per = std::min<u64>({tiles, 65535, max_blocks / batch});
+    fa.n_coeffs = n_coeffs; fa.num_cols = num_cols; fa.mont = ctx_mont(ctx); fa.f = ctx->fc;
+    // slices of tiles (a grid's x holds the circuits, at most 65,535)
+    const u64 tiles = (n_coeffs + FOLD_TILE - 1) / FOLD_TILE, tiles_per = slice_items(batch, tiles);
     if (!tiles_per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    for (u64 t0 = 0; t0 < tiles; t0 += tiles_per) {
+    return for_each_slice(tiles, tiles_per, [&](u64 t0, u64 nt) {
         fa.tile0 = (u32)t0;
-        ProfScope ps(H2R_KERNEL_FOLD, st, true);
-        HIP_TRY(launch_fold(fa, (u32)std::min<u64>(tiles_per, tiles - t0), (u32)batch, st, ps.a, ps.on ? ps.b : nullptr));
-    }
-    return H2R_OK;
+        return stage_launch(H2R_KERNEL_FOLD, st, [&](hipEvent_t a, hipEvent_t b) { return launch_fold(fa, (u32)nt, (u32)batch, st, a, b); });
+    });
 } H2R_CATCH_STATUS
 
 // ---- the commitments: multi-scalar multiplications over the curve of the ctx's field (h2r_msm.hpp, h2r_curve.hpp, h2r_tu_msm.hip) ---------
@@ -4683,22 +4626,17 @@ int32_t h2r_msm_columns(const h2r_ctx *ctx, const h2r_msm_config *cfg, const h2r
     if (cfg->num_cols && cfg->num_cols <= MSM_MAX_COLUMNS)
         for (u32 c = 0; c < cfg->num_cols; ++c)
             if (!cols[c].base) return H2R_E_NULL;
-    if (cfg->n == 0 || cfg->n > MSM_MAX_POINTS || cfg->num_cols == 0 || cfg->num_cols > MSM_MAX_COLUMNS || cfg->reserved) return H2R_E_SHAPE;
+    if (const int32_t rc = msm_cfg_status(cfg, 0)) return rc;   // (the batch's own turn comes after the ranges)
     const u64 col = 32ull * cfg->n;
-    if ((reinterpret_cast<u64>(bases) | reinterpret_cast<u64>(out) | reinterpret_cast<u64>(workspace)) & 15) return H2R_E_SHAPE;
-    for (u32 c = 0; c < cfg->num_cols; ++c) {
-        if ((reinterpret_cast<u64>(cols[c].base) | cols[c].elem_stride) & 15) return H2R_E_SHAPE;
-        if (cols[c].elem_stride && cols[c].elem_stride < col) return H2R_E_SHAPE;
-    }
+    if (misaligned(bases) || misaligned(out) || misaligned(workspace)) return H2R_E_SHAPE;
+    for (u32 c = 0; c < cfg->num_cols; ++c)
+        if (misaligned(cols[c].base, cols[c].elem_stride) || (cols[c].elem_stride && cols[c].elem_stride < col)) return H2R_E_SHAPE;
     if (batch) {   // out and the workspace are written while other workgroups still read the columns and the bases
-        const u128 o0 = reinterpret_cast<u64>(out), o1 = o0 + (u128)batch * cfg->num_cols * 64;
-        const u128 w0 = reinterpret_cast<u64>(workspace), w1 = w0 + (u128)256 + (u128)batch * cfg->num_cols * MSM_WINDOWS * msm_slices_of(cfg->n) * MSM_PARTIAL_BYTES;
-        const u128 b0 = reinterpret_cast<u64>(bases), b1 = b0 + (u128)64 * cfg->n;
-        if ((o0 < w1 && w0 < o1) || (o0 < b1 && b0 < o1) || (w0 < b1 && b0 < w1)) return H2R_E_SHAPE;
-        for (u32 c = 0; c < cfg->num_cols; ++c) {
-            const u128 c0 = reinterpret_cast<u64>(cols[c].base), c1 = c0 + (u128)(batch - 1) * cols[c].elem_stride + col;
-            if ((c0 < o1 && o0 < c1) || (c0 < w1 && w0 < c1)) return H2R_E_SHAPE;
-        }
+        const u128 o_bytes = (u128)batch * cfg->num_cols * 64, b_bytes = (u128)64 * cfg->n;
+        const u128 w_bytes = (u128)256 + (u128)batch * cfg->num_cols * MSM_WINDOWS * msm_slices_of(cfg->n) * MSM_PARTIAL_BYTES;
+        if (overlaps(out, o_bytes, workspace, w_bytes) || overlaps(out, o_bytes, bases, b_bytes) || overlaps(workspace, w_bytes, bases, b_bytes)) return H2R_E_SHAPE;
+        for (u32 c = 0; c < cfg->num_cols; ++c)
+            if (const ColumnBlock s{cols[c].base, col, cols[c].elem_stride, col, 1, batch}; overlaps(s, out, o_bytes) || overlaps(s, workspace, w_bytes)) return H2R_E_SHAPE;
     }
     if (batch > 65535) return H2R_E_UNSUPPORTED;
     const CurveConsts *cv = curve_of_field(ctx->params.field);
@@ -4709,22 +4647,19 @@ int32_t h2r_msm_columns(const h2r_ctx *ctx, const h2r_msm_config *cfg, const h2r
     std::memset(static_cast<void *>(&ma), 0, sizeof ma);
     for (u32 c = 0; c < cfg->num_cols; ++c) ma.cols[c] = MsmCol{static_cast<const u8 *>(cols[c].base), cols[c].elem_stride};
     ma.bases = static_cast<const u8 *>(bases); ma.status = status; ma.out = out;
-    ma.ws = reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256));
+    ma.ws = workspace_256(workspace);
     ma.n = cfg->n; ma.num_cols = cfg->num_cols; ma.num_slices = msm_slices_of(cfg->n);
-    ma.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;
+    ma.mont = ctx_mont(ctx);
     ma.fr = ctx->fc; ma.cv = *cv;
-    // launches below the 2^32 global size and the 65,535 of a grid's y / z: slices of circuits
-    const u64 max_blocks = ((1ull << 32) - 1) / 256, per_elem = (u64)ma.num_slices * MSM_WINDOWS * ma.num_cols;
-    const u64 elems_per = std::min<u64>({batch, 65535, max_blocks / per_elem});
+    const u64 elems_per = slice_items((u64)ma.num_slices * MSM_WINDOWS * ma.num_cols, batch);   // slices of circuits
     if (!elems_per) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     for (u32 phase = 0; phase < 2; ++phase)
-        for (u64 e0 = 0; e0 < batch; e0 += elems_per) {
-            ma.elem0 = (u32)e0;
-            ProfScope ps(H2R_KERNEL_MSM_BUCKET + phase, st, true);
-            HIP_TRY(launch_msm(phase, ma, (u32)std::min<u64>(elems_per, batch - e0), st, ps.a, ps.on ? ps.b : nullptr));
-        }
+        if (const int32_t rc = for_each_slice(batch, elems_per, [&](u64 e0, u64 ne) {
+                ma.elem0 = (u32)e0;
+                return stage_launch(H2R_KERNEL_MSM_BUCKET + phase, st, [&](hipEvent_t a, hipEvent_t b) { return launch_msm(phase, ma, (u32)ne, st, a, b); });
+            })) return rc;
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -4736,7 +4671,7 @@ int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const
     const FieldConsts &f = cv->fq;
     bool ok = true;
     auto coord = [&](const uint64_t *w) {   // a canonical coordinate -> the Montgomery form
-        Fe x; for (int k = 0; k < 4; ++k) x.v[k] = w[k];
+        const Fe x = fe_load(w);
         if (ge_p(x.v, f.p)) { ok = false; return fe_zero(); }
         return fe_to_mont(x, f);
     };

@@ -130,6 +130,28 @@ def test_accepted_arrangements(ctx):
     lib().h2r_ctx_destroy(planar)
 
 
+def test_no_elements_leaves_the_z_layout_unseen(ctx):
+    """batch = 0: Z's strides need not hold a column apart from each other (only z_col_stride's own bounds apply), and the call goes on
+    to meet the host-only ctx.  The shared column-block test would refuse these strides: the export asks it only when there are elements."""
+    ok = _lib.H2R_E_UNSUPPORTED
+    assert call(ctx, config(), batch=0, z_elem_stride=0) == ok
+    assert call(ctx, config(), batch=0, z_elem_stride=COL - 32) == ok
+    assert call(ctx, config(), batch=0, z_elem_stride=2 * COL) == ok                          # (refused with elements: SHAPE_CAUSES)
+    assert call(ctx, config(), batch=0, z_elem_stride=0, z_col_stride=COL - 32) == _lib.H2R_E_SHAPE
+    assert call(ctx, config(), batch=0, z_elem_stride=0, z_col_stride=COL + 16) == _lib.H2R_E_SHAPE
+    assert call(ctx, config(), batch=1, z_elem_stride=0) == _lib.H2R_E_SHAPE                  # one element: the strides count
+
+
+def test_huge_z_strides_are_judged_without_wrapping(ctx):
+    """Three sets at strides of 2^63: two elements' columns collide (element 1's set 0 IS element 0's set 1), but 2 * 2^63 + column is
+    `column` in 64 bits, which an element stride of 2^63 covers.  The layout test is 128-bit now and refuses what the 64-bit one let
+    through to the host-only ctx's H2R_E_UNSUPPORTED."""
+    three = config(src=(0, 1, 2), chunk=1)
+    assert call(ctx, three, z_elem_stride=1 << 63, z_col_stride=1 << 63) == _lib.H2R_E_SHAPE
+    assert call(ctx, three, batch=1, z_elem_stride=1 << 63, z_col_stride=1 << 63) == _lib.H2R_E_UNSUPPORTED   # one element: [set][element] holds
+    assert call(ctx, three, z_elem_stride=COL, z_col_stride=1 << 63) == _lib.H2R_E_UNSUPPORTED                 # [set][element], truly
+
+
 def test_sets():
     sets = lib().h2r_permutation_sets
     for (m, chunk), want in {(5, 2): 3, (6, 2): 3, (6, 6): 1, (6, 7): 1, (3, 1): 3, (8, 3): 3, (1, 1): 1}.items():
