@@ -154,6 +154,14 @@ class H2RMsmInfo(ctypes.Structure):
                 ("workspace_bytes", ctypes.c_uint64)]
 
 
+H2R_CURVE_NTT_INVERSE = 1
+
+
+class H2RCurveNttConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("log_n", ctypes.c_uint32), ("flags", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("omega", ctypes.c_uint64 * 4)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -204,6 +212,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_ntt_workspace_bytes", "h2r_ntt_columns", "h2r_quotient_sets", "h2r_quotient_columns",
            "h2r_open_queries", "h2r_open_workspace_bytes", "h2r_open_eval_columns", "h2r_open_witness_columns", "h2r_fold_columns",
            "h2r_msm_plan", "h2r_msm_workspace_bytes", "h2r_msm_columns", "h2r_curve_eval",
+           "h2r_curve_ntt_workspace_bytes", "h2r_curve_ntt",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -217,6 +226,7 @@ KERNEL_NTT_SETUP, KERNEL_NTT_PASS = 16, 17
 KERNEL_QUOTIENT = 18
 KERNEL_OPEN_TILES, KERNEL_OPEN_CARRY, KERNEL_OPEN_SCAN, KERNEL_FOLD = 19, 20, 21, 22
 KERNEL_MSM_BUCKET, KERNEL_MSM_FOLD = 23, 24
+KERNEL_CURVE_NTT_TWIDDLE, KERNEL_CURVE_NTT_LOAD, KERNEL_CURVE_NTT_STAGE, KERNEL_CURVE_NTT_STORE = 25, 26, 27, 28
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
 FRESH_OPS = ["add", "sub", "add_mod", "sub_mod", "is_zero", "is_equal_fresh", "is_less_than", "is_less_than_or_equal",
@@ -438,6 +448,9 @@ def lib():
     L.h2r_msm_workspace_bytes.restype = u64
     L.h2r_msm_columns.argtypes = [vp, pmsm, pmcols, vp, u64, vp, vp, vp, vp]
     L.h2r_curve_eval.argtypes = [vp, u32, pu64, pu64, pu64]
+    L.h2r_curve_ntt_workspace_bytes.argtypes = [ctypes.POINTER(H2RCurveNttConfig)]
+    L.h2r_curve_ntt_workspace_bytes.restype = u64
+    L.h2r_curve_ntt.argtypes = [vp, ctypes.POINTER(H2RCurveNttConfig), vp, vp, vp, vp]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.h2r_dist_destroy.argtypes = [vp]

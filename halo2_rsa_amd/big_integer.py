@@ -1319,6 +1319,10 @@ class EvaluationDomain:
         """2^extended_k evaluations over the coset -> the 2^extended_k coefficients (truncation stays the caller's)."""
         return self.ntt(cols, self.extended_k, inverse=True, shift=self.zeta, out=out)
 
+    def lagrange_key(self, key: "CommitKey") -> "CommitKey":
+        """The Lagrange-basis key of this domain over the first 2^k bases of `key` (halo2's g_lagrange from g): key.transform(omega, k)."""
+        return key.transform(self.omega, self.k)
+
     def vanishing_columns(self, blinding_factors: int) -> torch.Tensor:
         """uint8 [3, 2^extended_k, 32]: l0, l_last and l_active = 1 - l_last - l_blind of the 2^k domain with `blinding_factors` blinding
         rows, in extended form (lagrange_to_coeff, then coeff_to_extended) -- the `l` columns of quotient()."""
@@ -1553,6 +1557,38 @@ class CommitKey:
                                     status.data_ptr() if status is not None else None, ws.data_ptr(), self.chip._stream()), "h2r_msm_columns")
         self._keep = (ws, list(columns), out, status)   # alive until the stream has run the kernels
         return out
+
+    def transform(self, omega: int, k: Optional[int] = None, inverse: bool = True, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> "CommitKey":
+        """A new key over the transform of the first 2^k bases (h2r_curve_ntt): inverse (the default)
+        out[i] = [n^-1] sum_j [omega^(-i j)] bases[j] -- with the powers of tau as bases and the domain's omega, halo2's g_lagrange --,
+        forward out[i] = sum_j [omega^(i j)] bases[j].  omega: a primitive 2^k-th root of unity of the chip's field, an integer in the chip's
+        representation.  k: log2 n by default; a key whose n is no power of two needs an explicit k <= log2 n.  out: the tensor of 2^k
+        points to write into (the layout of `bases`; it must overlap neither the bases nor the workspace); workspace: uint8,
+        h2r_curve_ntt_workspace_bytes bytes, 16-byte aligned, the call's own until the stream has run it (allocated when None)."""
+        if k is None:
+            k = self.n.bit_length() - 1
+            if self.n != 1 << k:
+                check(_lib.H2R_E_SHAPE, "CommitKey.transform")
+        k = int(k)
+        if k < 1 or (1 << k) > self.n:
+            check(_lib.H2R_E_SHAPE, "CommitKey.transform")
+        cfg = _lib.H2RCurveNttConfig()
+        cfg.struct_size, cfg.log_n, cfg.flags, cfg.reserved = ctypes.sizeof(cfg), k, _lib.H2R_CURVE_NTT_INVERSE if inverse else 0, 0
+        for i in range(4):
+            cfg.omega[i] = (int(omega) >> (64 * i)) & (2 ** 64 - 1)
+        n, dev = 1 << k, self.bases.device
+        if out is None:
+            out = torch.zeros((n, 2, 4), dtype=torch.int64, device=dev) if self.bases.dtype == torch.int64 else torch.zeros((n, 64), dtype=torch.uint8, device=dev)
+        assert out.is_contiguous() and out.is_cuda and out.numel() * out.element_size() == 64 * n
+        need = int(lib().h2r_curve_ntt_workspace_bytes(ctypes.byref(cfg)))
+        ws = workspace if workspace is not None else torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+        check(lib().h2r_curve_ntt(self.chip._ctx, ctypes.byref(cfg), self.bases.data_ptr(), out.data_ptr(), ws.data_ptr(), self.chip._stream()),
+              "h2r_curve_ntt")
+        key = CommitKey(self.chip, out)
+        key._keep = (ws, self.bases, out)   # alive until the stream has run the kernels
+        return key
 
 
 @dataclass

@@ -29,6 +29,7 @@
 #include "h2r_quotient.hpp"
 #include "h2r_open.hpp"
 #include "h2r_msm.hpp"
+#include "h2r_curve_ntt.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4454,7 +4455,8 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
 namespace {
 static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_OPEN_SCAN == H2R_KERNEL_OPEN_TILES + 2 &&
               H2R_KERNEL_MSM_BUCKET == H2R_KERNEL_FOLD + 1 && H2R_KERNEL_MSM_FOLD == H2R_KERNEL_MSM_BUCKET + 1 &&
-              H2R_KERNEL_COUNT == H2R_KERNEL_MSM_FOLD + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_CURVE_NTT_TWIDDLE == H2R_KERNEL_MSM_FOLD + 1 && H2R_KERNEL_CURVE_NTT_STORE == H2R_KERNEL_CURVE_NTT_TWIDDLE + 3 &&
+              H2R_KERNEL_COUNT == H2R_KERNEL_CURVE_NTT_STORE + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -4664,8 +4666,9 @@ int32_t h2r_msm_columns(const h2r_ctx *ctx, const h2r_msm_config *cfg, const h2r
 } H2R_CATCH_STATUS
 
 int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t *out) try {
-    if (!ctx || !a || !out || ((op == 0 || op == 1 || op == 4) && !b)) return H2R_E_NULL;
-    if (op > 4) return H2R_E_SHAPE;
+    if (!ctx || !a || !out || ((op == 0 || op == 1 || op == 4 || op == 6 || op == 7) && !b)) return H2R_E_NULL;
+    // (op 5 stays refused: it was the first unknown op when ops 6 and 7 were added, and tests/test_msm_host.py pins its refusal)
+    if (op > 7 || op == 5) return H2R_E_SHAPE;
     const CurveConsts *cv = curve_of_field(ctx->params.field);
     if (!cv) return H2R_E_UNSUPPORTED;
     const FieldConsts &f = cv->fq;
@@ -4694,16 +4697,80 @@ int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const
         const PtAff q = pt_to_affine(p, *cv);
         put(out, q.x); put(out + 4, q.y);
         return H2R_OK;
-    } else {   // k * P as the kernels form it: the digit's multiple per window, a Horner over the windows from the top
+    } else if (op == 4) {   // k * P as the kernels form it: the digit's multiple per window, a Horner over the windows from the top
         if (!ok) return H2R_E_SHAPE;
         r = pt_identity(*cv);
         for (u32 w = MSM_WINDOWS; w-- > 0;) {
             const u32 d = (u32)(b[w >> 3] >> ((w & 7u) * 8)) & 0xffu;
             r = pt_add(pt_shift_window(r, *cv), pt_mul_digit(p, d, *cv), *cv);
         }
+    } else {   // k * P as a butterfly of h2r_curve_ntt forms it: 6 = the wave-uniform double-and-add, 7 = the lane's 2-bit windows
+        if (!ok) return H2R_E_SHAPE;
+        const u64 k[4] = {b[0], b[1], b[2], b[3]};
+        r = op == 6 ? pt_mul_uniform(p, k, *cv) : pt_mul_window2(p, k, *cv);
     }
     put(out, r.x); put(out + 4, r.y); put(out + 8, r.z);
     return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the Lagrange-basis commitment key: a transform over the points of the curve of the ctx's field (h2r_curve_ntt.hpp, h2r_tu_curve_ntt.hip) ----
+namespace {
+// what h2r_curve_ntt_workspace_bytes answers 0 for: the parts of a configuration that need no ctx (omega is compared with the ctx's p)
+int32_t curve_ntt_cfg_status(const h2r_curve_ntt_config *cfg) {
+    if (cfg->struct_size != sizeof(h2r_curve_ntt_config) || (cfg->flags & ~H2R_CURVE_NTT_INVERSE)) return H2R_E_UNSUPPORTED;
+    if (cfg->log_n == 0 || cfg->log_n > CNTT_MAX_LOG || cfg->reserved) return H2R_E_SHAPE;
+    return H2R_OK;
+}
+}  // namespace
+
+uint64_t h2r_curve_ntt_workspace_bytes(const h2r_curve_ntt_config *cfg) try {
+    return cfg && curve_ntt_cfg_status(cfg) == H2R_OK ? curve_ntt_workspace_bytes(cfg->log_n) : 0;
+} H2R_CATCH_ZERO
+
+int32_t h2r_curve_ntt(const h2r_ctx *ctx, const h2r_curve_ntt_config *cfg, const void *in, void *out, void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !in || !out || !workspace) return H2R_E_NULL;
+    if (const int32_t rc = curve_ntt_cfg_status(cfg)) return rc;
+    const FieldConsts &f = ctx->fc;
+    if (ge_p(cfg->omega, f.p)) return H2R_E_SHAPE;
+    const u32 log_n = cfg->log_n;
+    const bool inverse = (cfg->flags & H2R_CURVE_NTT_INVERSE) != 0;
+    const Fe omega = cfg_to_mont(ctx, cfg->omega);   // Montgomery form from here on
+    if (!is_primitive_root(omega, log_n, f)) return H2R_E_SHAPE;
+    if (misaligned(in) || misaligned(out) || misaligned(workspace)) return H2R_E_SHAPE;
+    // the stages work in place in the workspace while other workgroups still read `in`; the store writes `out` while others read the workspace
+    const u128 p_bytes = (u128)64 << log_n, w_bytes = curve_ntt_workspace_bytes(log_n);
+    if (overlaps(in, p_bytes, out, p_bytes) || overlaps(in, p_bytes, workspace, w_bytes) || overlaps(out, p_bytes, workspace, w_bytes)) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+
+    auto inv = [&](const Fe &x) { return fe_to_mont(fe_inv(fe_from_mont(x, f), f), f); };   // x is x * R: back to the integer, invert, forth
+    CurveNttArgs ca;
+    std::memset(static_cast<void *>(&ca), 0, sizeof ca);
+    fe_squaring_chain(ca.wpow, CNTT_MAX_LOG, inverse ? inv(omega) : omega, f);
+    const Fe ninv = fe_from_mont(inv(fe_to_mont(fe_small(1ull << log_n), f)), f);
+    for (int k = 0; k < 4; ++k) ca.ninv[k] = ninv.v[k];
+    ca.in = static_cast<const u8 *>(in); ca.out = static_cast<u8 *>(out);
+    ca.pts = workspace_256(workspace); ca.tw = reinterpret_cast<u64 *>(ca.pts + ((u64)CNTT_POINT_BYTES << log_n));
+    ca.log_n = log_n; ca.mont = ctx_mont(ctx); ca.inverse = inverse;
+    ca.form = knobs().curve_ntt_form == 1 ? CNTT_FORM_PER_LANE : CNTT_FORM_DEFAULT;
+    ca.fr = f; ca.cv = *cv;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // a launch of `items` lanes, sliced by workgroups below the 2^32 global size and the 65,535 of a grid dimension
+    auto launch = [&](u32 kernel_class, u32 phase, u64 items) {
+        const u64 blocks = (items + kBlockThreads - 1) / kBlockThreads;
+        return for_each_slice(blocks, slice_items(1, blocks), [&](u64 b0, u64 nb) {
+            ca.block0 = (u32)b0;
+            return stage_launch(kernel_class, st, [&](hipEvent_t a, hipEvent_t b) { return launch_curve_ntt(phase, ca, (u32)nb, st, a, b); });
+        });
+    };
+    const u64 n = 1ull << log_n;
+    if (const int32_t rc = launch(H2R_KERNEL_CURVE_NTT_TWIDDLE, 0, n / 2)) return rc;
+    if (const int32_t rc = launch(H2R_KERNEL_CURVE_NTT_LOAD, 1, n)) return rc;
+    for (ca.stage = 1; ca.stage <= log_n; ++ca.stage)
+        if (const int32_t rc = launch(H2R_KERNEL_CURVE_NTT_STAGE, 2, n / 2)) return rc;
+    return launch(H2R_KERNEL_CURVE_NTT_STORE, 3, n);
 } H2R_CATCH_STATUS
 
 // The copy constraints of one fixed-exponent pow element (h2r_pow_trace_emit_advice's image: CONST1, CONST0, then the records), rows

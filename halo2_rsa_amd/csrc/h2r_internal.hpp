@@ -13,6 +13,7 @@
 //   h2r_tu_quotient.hip   the vanishing argument's quotient on the extended domain (h2r_quotient.hpp)
 //   h2r_tu_open.hip    the openings: evaluations at x, GWC witness polynomials, the fold of h's pieces (h2r_open.hpp)
 //   h2r_tu_msm.hip     the commitments: multi-scalar multiplications over the curve of the ctx's field (h2r_msm.hpp, h2r_curve.hpp)
+//   h2r_tu_curve_ntt.hip   the Lagrange-basis commitment key: the transform over the curve's points (h2r_curve_ntt.hpp, h2r_curve.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -54,6 +55,7 @@ struct Knobs {
     long rowprog_stage_rows = 0;                 // H2R_ROWPROG_STAGE_ROWS=64|128|256: rows (= threads) of a row-program workgroup (0 = the rule in launch_row_prog)
     long keep_const = -1;                        // H2R_KEEP_CONST=0: record launches into a trace arena's regions store the constant planes like any other
     long cells_nwv = 0;                          // H2R_CELLS_NWV=1|8: waves per cells_kernel workgroup of a Montgomery ctx (0 = the rule at ctx creation)
+    long curve_ntt_form = 0;                     // H2R_CURVE_NTT_FORM=1: every butterfly of h2r_curve_ntt runs per-lane bit-by-bit double-and-add (the timing tool's baseline)
     Knobs() {
 #ifdef H2R_DEV_KNOBS
         auto num = [](const char *name, long dflt) { const char *v = std::getenv(name); return v ? std::atol(v) : dflt; };
@@ -68,7 +70,7 @@ struct Knobs {
         verify_fold = num("H2R_VERIFY_FOLD", -1); exp_segments = num("H2R_EXP_SEGMENTS", -1); single_call_segments = num("H2R_SINGLE_CALL_SEGMENTS", -1);
         pipe_step = num("H2R_PIPE_STEP", -1); pipe_form = num("H2R_PIPE_FORM", -1); pipe_twoq_l16 = num("H2R_PIPE_TWOQ_L16", 0); step_chain_x2_per_cu = num("H2R_STEP_CHAIN_X2_PER_CU", 0);
         rowprog_stage_rows = num("H2R_ROWPROG_STAGE_ROWS", 0); cells_nwv = num("H2R_CELLS_NWV", 0);
-        keep_const = num("H2R_KEEP_CONST", -1);
+        keep_const = num("H2R_KEEP_CONST", -1); curve_ntt_form = num("H2R_CURVE_NTT_FORM", 0);
         pipe_sub_batch = num("H2R_PIPE_SUB_BATCH", 0); arena_chunk_mb = num("H2R_ARENA_CHUNK_MB", 0); plain_overlap = num("H2R_PLAIN_OVERLAP", -1); pipe_pace = num("H2R_PIPE_PACE", -1);
 #endif
     }
@@ -136,5 +138,9 @@ hipError_t launch_fold(const FoldArgs &a, u32 num_tiles, u32 num_elems, hipStrea
 // [a.elem0, a.elem0 + num_elems).
 struct MsmArgs;
 hipError_t launch_msm(u32 phase, const MsmArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_curve_ntt.hip (argument struct: h2r_curve_ntt.hpp).  phase 0 = the twiddle table, 1 = the load, 2 = stage a.stage, 3 = the store; the
+// workgroups [a.block0, a.block0 + num_blocks) of 256 twiddles / points / butterflies / points.
+struct CurveNttArgs;
+hipError_t launch_curve_ntt(u32 phase, const CurveNttArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

@@ -1091,6 +1091,36 @@ uint64_t h2r_msm_workspace_bytes(const h2r_msm_config *cfg, uint64_t batch);
 int32_t h2r_msm_columns(const h2r_ctx *ctx, const h2r_msm_config *cfg, const h2r_msm_column *cols, const void *bases, uint64_t batch,
                         uint64_t *out, uint8_t *status, void *workspace, h2r_stream_t stream);
 int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const uint64_t *b, uint64_t *out);
+/* ---- the Lagrange-basis commitment key: a transform over the points of the curve of the ctx's field ----
+ * THIRD-PARTY behaviour (halo2 poly::kzg::commitment::g_to_lagrange: a best_fft over projective points, not in the reference tree), restated
+ * in DESIGN.md section 2k; parity is pinned against a Python restatement (tests/curve_ntt_ref.py, tests/test_curve_ntt_gpu.py), not against
+ * upstream.  A number-theoretic transform whose elements are points and whose twiddle products are scalar multiplications; with n = 2^log_n
+ * and natural index order on both sides, the conventions of h2r_ntt_columns:
+ *    forward:                       out[i] = sum_j [omega^(i j)] in[j]
+ *    inverse (H2R_CURVE_NTT_INVERSE): out[i] = [n^-1] sum_j [omega^(-i j)] in[j]
+ * g_lagrange at k is the inverse transform of the first 2^k points of g.  Only a ctx whose field has a curve (h2r_msm_columns above).
+ *  - in, out: n affine points on the device, 64 bytes each, in exactly h2r_msm_columns' encoding: x then y, Fq elements in the ctx's
+ *    representation, (0, 0) the identity -- legal on input, and what an identity result is written as.  Output coordinates are the canonical
+ *    representatives: the bytes do not depend on the order of operations.  The inputs are key material and are NOT validated: an off-curve
+ *    point or a coordinate >= q gives unspecified output bytes, never a fault or an unbounded loop.
+ *  - omega: a primitive 2^log_n-th root of unity of the ctx's field (the scalars), in the ctx's representation; omega^-1 and n^-1 are
+ *    inverted on the host.  There is no status array.  The call enqueues on `stream` and never synchronises: the twiddle table, the load
+ *    (affine -> projective, bit-reversed), one launch per stage (log_n of them, in place in the workspace), the store (n^-1 for the inverse,
+ *    projective -> affine); no workgroup waits for another; launches are sliced internally below the 2^32 global size.
+ *    workspace: h2r_curve_ntt_workspace_bytes(cfg) bytes on the device, private to the call until the stream has run it (a host function; no
+ *    device and no ctx needed; 0 for a config the call would refuse whatever the ctx: struct_size, flags, log_n, reserved).
+ *  - H2R_E_NULL for a NULL ctx, cfg, in, out or workspace; H2R_E_UNSUPPORTED for another struct_size or unknown flag bits (before everything
+ *    else), a field without a curve, or a host-only ctx (that one after every other check); H2R_E_SHAPE for log_n = 0 or > 24, a nonzero
+ *    `reserved`, omega >= p, omega^(n / 2) != -1, a pointer that is not 16-byte aligned, and in, out and the workspace overlapping each
+ *    other at all.
+ *  - h2r_curve_eval ops 6 and 7 (a projective, b = k: four words, any 256-bit integer -> projective): k * P exactly as a butterfly forms
+ *    it, 6 = double-and-add over the non-adjacent form of k (the form of the stages whose wavefronts share one twiddle, and of n^-1),
+ *    7 = fixed 2-bit windows over the table {O, P, 2P, 3P} (the form of the stages whose lanes hold different twiddles).  op 5 stays
+ *    refused (H2R_E_SHAPE). */
+#define H2R_CURVE_NTT_INVERSE 1u
+typedef struct h2r_curve_ntt_config { uint32_t struct_size, log_n, flags, reserved; uint64_t omega[4]; } h2r_curve_ntt_config;
+uint64_t h2r_curve_ntt_workspace_bytes(const h2r_curve_ntt_config *cfg);
+int32_t h2r_curve_ntt(const h2r_ctx *ctx, const h2r_curve_ntt_config *cfg, const void *in, void *out, void *workspace, h2r_stream_t stream);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1390,7 +1420,9 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_OPEN_TILES = 19, H2R_KERNEL_OPEN_CARRY = 20, H2R_KERNEL_OPEN_SCAN = 21 /* the openings' launches: evaluations (two), witness polynomials (three) */,
        H2R_KERNEL_FOLD = 22 /* fold_kernel */,
        H2R_KERNEL_MSM_BUCKET = 23, H2R_KERNEL_MSM_FOLD = 24 /* the commitments' two launches: msm_bucket_kernel, msm_fold_kernel */,
-       H2R_KERNEL_COUNT = 25 };
+       H2R_KERNEL_CURVE_NTT_TWIDDLE = 25, H2R_KERNEL_CURVE_NTT_LOAD = 26, H2R_KERNEL_CURVE_NTT_STAGE = 27 /* one launch per stage */,
+       H2R_KERNEL_CURVE_NTT_STORE = 28 /* h2r_curve_ntt's launches: the twiddle table, affine -> projective, the stages, projective -> affine */,
+       H2R_KERNEL_COUNT = 29 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
