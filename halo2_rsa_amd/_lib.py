@@ -227,6 +227,7 @@ KERNEL_QUOTIENT = 18
 KERNEL_OPEN_TILES, KERNEL_OPEN_CARRY, KERNEL_OPEN_SCAN, KERNEL_FOLD = 19, 20, 21, 22
 KERNEL_MSM_BUCKET, KERNEL_MSM_FOLD = 23, 24
 KERNEL_CURVE_NTT_TWIDDLE, KERNEL_CURVE_NTT_LOAD, KERNEL_CURVE_NTT_STAGE, KERNEL_CURVE_NTT_STORE = 25, 26, 27, 28
+FIELD_MUL, FIELD_TO_MONTGOMERY, FIELD_FROM_MONTGOMERY = 2, 6, 7   # h2r_field_eval's operations a * b, a * R and a * R^-1 mod p (include/h2r.h)
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
 FRESH_OPS = ["add", "sub", "add_mod", "sub_mod", "is_zero", "is_equal_fresh", "is_less_than", "is_less_than_or_equal",

@@ -5,6 +5,8 @@ for the methods on the hot path -- `assign_integer`, `mul_mod`, `square_mod`, `p
 `pow_mod_fixed_exp` -- in batch form: every integer argument is a batch of integers (one per
 independent circuit), resident in HBM.  All arithmetic happens in libh2r.so (hand-written HIP);
 this module only moves pointers.  There is no CPU fallback.
+The prover stages that the reference's module has no counterpart of (LookupArgument, PermutationArgument, EvaluationDomain, CommitKey)
+live in `prover` and are re-exported here; `_marshal` holds what both modules do between an argument and a pointer.
 """
 import ctypes
 from dataclasses import dataclass
@@ -15,6 +17,8 @@ import torch
 
 from . import _lib
 from ._lib import H2RLayout, H2RParams, H2RPowLayout, check, lib
+from ._marshal import hold, image_stride, kinds_tensor, ptr, ref
+from .prover import CommitKey, EvaluationDomain, LookupArgument, PermutationArgument  # noqa: F401  (re-exported: they lived here once)
 
 
 def _e_bytes(e: int) -> bytes:
@@ -399,7 +403,7 @@ class BigIntChip:
         table and the copy pairs.  kinds: uint8 row kinds (numpy or device tensor); copies: H2RCopy array (ctypes) or a device tensor of
         [n, 4] int32; returns (bad int32 [batch], first int64 [batch]); bad == 0 everywhere for a satisfying assignment."""
         dev = image.device
-        kd = kinds if isinstance(kinds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(kinds, dtype=np.uint8)).to(dev)
+        kd = kinds_tensor(kinds, dev)
         rows = kd.numel()
         cd, n_copies = None, 0
         if copies is not None:
@@ -411,14 +415,11 @@ class BigIntChip:
         bad = torch.empty(batch, dtype=torch.int32, device=dev)
         first = torch.empty(batch, dtype=torch.int64, device=dev)
         flags = _lib.H2R_F_SHARED_MODULUS if (src_n is not None and src_n.batch == 1 and batch != 1) else 0
-        stride = image.shape[1] if image.dim() > 1 else image.numel() // batch
         check(lib().h2r_advice_check(self._ctx, ctypes.byref(lookup.cfg) if lookup is not None else None,
-                                     ctypes.byref(layout) if layout is not None else None, kd.data_ptr(), rows, image.data_ptr(), stride, batch,
-                                     status.data_ptr() if status is not None else None, cd.data_ptr() if cd is not None else None, n_copies,
-                                     src_a.data_ptr() if src_a is not None else None, src_b.data_ptr() if src_b is not None else None,
-                                     src_n.data_ptr() if src_n is not None else None, flags, bad.data_ptr(), first.data_ptr(), self._stream()),
+                                     ref(layout), kd.data_ptr(), rows, image.data_ptr(), image_stride(image, batch), batch, ptr(status), ptr(cd),
+                                     n_copies, ptr(src_a), ptr(src_b), ptr(src_n), flags, bad.data_ptr(), first.data_ptr(), self._stream()),
               "h2r_advice_check")
-        self._keep = (kd, cd)
+        hold(self, "advice_check", kd, cd)
         return bad, first
 
     def pow_copy_map(self, pl: H2RPowLayout, e: int, row_offset: int = 0):
@@ -613,7 +614,7 @@ class BigIntChip:
         tp = trace_buf.data_ptr() if want_trace else None
         if workspace is None and want_trace:   # kept with the result: audit() reads every mul_mod's operands from it
             workspace = torch.empty(self.workspace_bytes(batch, pl.num_mul_mods), dtype=torch.uint8, device=dev)
-        wp = workspace.data_ptr() if workspace is not None else None
+        wp = ptr(workspace)
         in_field = None
         if check_in_field:
             in_field = self._in_field_trace(batch, in_field_buf) if (want_trace or in_field_buf is not None or workspace is not None) else None
@@ -646,7 +647,7 @@ class BigIntChip:
         status = torch.zeros(batch, dtype=torch.uint8, device=dev)
         tp = trace.data_ptr() if want_trace else None
         ws = torch.empty(self.workspace_bytes(batch, pl.num_mul_mods), dtype=torch.uint8, device=dev) if want_trace else None
-        wp = ws.data_ptr() if ws is not None else None
+        wp = ptr(ws)
         in_field = None
         if check_in_field:
             in_field = self._in_field_trace(batch) if want_trace else None
@@ -677,10 +678,8 @@ class BigIntChip:
                 flags |= _lib.H2R_F_SHARED_MODULUS
             else:
                 check(_lib.H2R_E_SHAPE, name + ": operand batches differ")
-        check(lib().h2r_fresh_op_batch(self._ctx, op, a.data_ptr(), b.data_ptr() if b is not None else None,
-                                       n.data_ptr() if n is not None else None, batch, flags, trace.data_ptr(),
-                                       value.data_ptr() if value is not None else None, flag.data_ptr(), status.data_ptr(),
-                                       self._stream()), name)
+        check(lib().h2r_fresh_op_batch(self._ctx, op, a.data_ptr(), ptr(b), ptr(n), batch, flags, trace.data_ptr(), ptr(value), flag.data_ptr(),
+                                       status.data_ptr(), self._stream()), name)
         return FreshResult(AssignedInteger(value, self.limb_width) if value is not None else None, flag, status, trace,
                            es.value, sb.value, op, self, (a, b, n, flags))
 
@@ -692,10 +691,8 @@ class BigIntChip:
         if rows == 0:
             check(_lib.H2R_E_UNSUPPORTED, "h2r_fresh_op_advice_rows")
         out = torch.empty((batch, self.image_bytes(rows)), dtype=torch.uint8, device=trace.device)
-        check(lib().h2r_fresh_op_emit_advice(self._ctx, op, fl, a.data_ptr(), b.data_ptr() if b is not None else None,
-                                             n.data_ptr() if n is not None else None, trace.data_ptr(), first_off, elem_stride, batch,
-                                             status.data_ptr() if status is not None else None, out.data_ptr(), out.shape[1],
-                                             self._stream()), "h2r_fresh_op_emit_advice")
+        check(lib().h2r_fresh_op_emit_advice(self._ctx, op, fl, a.data_ptr(), ptr(b), ptr(n), trace.data_ptr(), first_off, elem_stride, batch,
+                                             ptr(status), out.data_ptr(), out.shape[1], self._stream()), "h2r_fresh_op_emit_advice")
         return out
 
     def fresh_op_row_kinds(self, op: int, assert_one: bool = False) -> np.ndarray:
@@ -864,7 +861,7 @@ class Pipeline:
         eb = _e_bytes(e)
         check(lib().h2r_pipeline_modpow_public_key(self._p, x.data_ptr(), n.data_ptr(), eb, len(eb), x.batch,
                                                    self.chip._flags(n, x.batch), trace_buf.data_ptr(),
-                                                   in_field_buf.data_ptr() if in_field_buf is not None else None, out.data_ptr(),
+                                                   ptr(in_field_buf), out.data_ptr(),
                                                    status.data_ptr(), workspace.data_ptr(), self.chip._stream()),
               "h2r_pipeline_modpow_public_key")
 
@@ -875,7 +872,7 @@ class Pipeline:
         eb = _e_bytes(e)
         check(lib().h2r_pipeline_modpow_public_key_advice(self._p, x.data_ptr(), n.data_ptr(), eb, len(eb), x.batch, self.chip._flags(n, x.batch),
                                                           in_field_buf.data_ptr(), out.data_ptr(), status.data_ptr(), workspace.data_ptr(),
-                                                          advice_out.data_ptr(), advice_out.shape[-1] if advice_out.dim() > 1 else advice_out.numel() // x.batch,
+                                                          advice_out.data_ptr(), image_stride(advice_out, x.batch),
                                                           self.chip._stream()), "h2r_pipeline_modpow_public_key_advice")
 
     def modpow_public_key_var(self, x: AssignedInteger, e: AssignedInteger, exp_limb_bits: int, n: AssignedInteger, trace_buf, workspace,
@@ -883,7 +880,7 @@ class Pipeline:
         """RSAPubE::Var: per-element exponents `e` ([batch, e_num_limbs] limbs); buffers sized by pow_var_layout."""
         check(lib().h2r_pipeline_modpow_public_key_var(self._p, x.data_ptr(), e.data_ptr(), e.num_limbs(), exp_limb_bits, n.data_ptr(), x.batch,
                                                        self.chip._flags(n, x.batch), trace_buf.data_ptr(),
-                                                       in_field_buf.data_ptr() if in_field_buf is not None else None, out.data_ptr(),
+                                                       ptr(in_field_buf), out.data_ptr(),
                                                        status.data_ptr(), workspace.data_ptr(), self.chip._stream()),
               "h2r_pipeline_modpow_public_key_var")
 
@@ -903,7 +900,7 @@ class Pipeline:
         check(lib().h2r_pipeline_modpow_public_key_var_advice(self._p, x.data_ptr(), e.data_ptr(), e.num_limbs(), exp_limb_bits, n.data_ptr(), x.batch,
                                                               self.chip._flags(n, x.batch), in_field_buf.data_ptr(), witness.data_ptr(), out.data_ptr(),
                                                               status.data_ptr(), workspace.data_ptr(), advice_out.data_ptr(),
-                                                              advice_out.shape[-1] if advice_out.dim() > 1 else advice_out.numel() // x.batch,
+                                                              image_stride(advice_out, x.batch),
                                                               self.chip._stream()), "h2r_pipeline_modpow_public_key_var_advice")
 
     def pow_var_compact_layout(self, e_num_limbs: int, exp_limb_bits: int) -> H2RPowLayout:
@@ -922,7 +919,7 @@ class Pipeline:
         check(lib().h2r_pipeline_verify_pkcs1v15_advice(self._p, sig.data_ptr(), n.data_ptr(), eb, len(eb), hashed.data_ptr(), sig.batch,
                                                         self.chip._flags(n, sig.batch), witness.data_ptr(), powed.data_ptr(), is_valid.data_ptr(),
                                                         status.data_ptr(), workspace.data_ptr(), advice_out.data_ptr(),
-                                                        advice_out.shape[-1] if advice_out.dim() > 1 else advice_out.numel() // sig.batch,
+                                                        image_stride(advice_out, sig.batch),
                                                         self.chip._stream()), "h2r_pipeline_verify_pkcs1v15_advice")
 
     def verify_pkcs1v15_var_advice(self, sig: AssignedInteger, e: AssignedInteger, exp_limb_bits: int, n: AssignedInteger, hashed, witness, workspace, powed,
@@ -931,7 +928,7 @@ class Pipeline:
         check(lib().h2r_pipeline_verify_pkcs1v15_var_advice(self._p, sig.data_ptr(), n.data_ptr(), e.data_ptr(), e.num_limbs(), exp_limb_bits, hashed.data_ptr(),
                                                             sig.batch, self.chip._flags(n, sig.batch), witness.data_ptr(), powed.data_ptr(), is_valid.data_ptr(),
                                                             status.data_ptr(), workspace.data_ptr(), advice_out.data_ptr(),
-                                                            advice_out.shape[-1] if advice_out.dim() > 1 else advice_out.numel() // sig.batch,
+                                                            image_stride(advice_out, sig.batch),
                                                             self.chip._stream()), "h2r_pipeline_verify_pkcs1v15_var_advice")
 
     def verify_compact_layout_var(self, e_num_limbs: int, exp_limb_bits: int):
@@ -957,11 +954,11 @@ class Pipeline:
         `msg_off` int64 [batch + 1] (or None: every message has fixed_len bytes); the SHA-256 / hashed-message step rides on the call's
         step launch.  `hashed`: int64 [batch, 4] output (the verifier's operand), digest uint8 [batch, 32] / hm_trace uint8 [batch, 288] optional."""
         eb = _e_bytes(e)
-        check(lib().h2r_pipeline_signature_verifier(self._p, msgs.data_ptr(), msg_off.data_ptr() if msg_off is not None else None, fixed_len,
+        check(lib().h2r_pipeline_signature_verifier(self._p, msgs.data_ptr(), ptr(msg_off), fixed_len,
                                                     sig.data_ptr(), n.data_ptr(), eb, len(eb), sig.batch, self.chip._flags(n, sig.batch),
-                                                    trace_buf.data_ptr(), hm_trace.data_ptr() if hm_trace is not None else None,
+                                                    trace_buf.data_ptr(), ptr(hm_trace),
                                                     hm_trace.shape[1] if hm_trace is not None else 0,
-                                                    digest.data_ptr() if digest is not None else None, hashed.data_ptr(), powed.data_ptr(),
+                                                    ptr(digest), hashed.data_ptr(), powed.data_ptr(),
                                                     is_valid.data_ptr(), status.data_ptr(), workspace.data_ptr(), self.chip._stream()),
               "h2r_pipeline_signature_verifier")
 
@@ -1012,8 +1009,12 @@ class TraceArena:
         self._a = ctypes.c_void_p()
         check(lib().h2r_arena_create_ex(chip._ctx, elem_stride, first_record_off, records_per_elem, batch, regions, candidates, max_look_bytes,
                                         chip._stream(), ctypes.byref(self._a)), "h2r_arena_create_ex")
+        self._adopt(regions, candidates)
+
+    def _adopt(self, regions: int, candidates: int):
+        """The kept regions as tensors, their times and every candidate's measurement, from the arena just created."""
         nbytes = int(lib().h2r_arena_region_bytes(self._a))
-        dev = "cuda:%d" % chip.device
+        dev = "cuda:%d" % self.chip.device
         self.regions = [torch.as_tensor(TraceArena._Raw(int(lib().h2r_arena_region(self._a, i)), nbytes), device=dev) for i in range(regions)]
         self.region_ms = [float(lib().h2r_arena_region_ms(self._a, i)) for i in range(regions)]
         buf = (ctypes.c_double * (12 * candidates))()   # (further candidates while the kept regions are not of one class, a second round when none stands out)
@@ -1028,13 +1029,7 @@ class TraceArena:
         self._a = ctypes.c_void_p()
         check(lib().h2r_image_arena_create(chip._ctx, region_bytes, regions, candidates, max_look_bytes, chip._stream(), ctypes.byref(self._a)),
               "h2r_image_arena_create")
-        nbytes = int(lib().h2r_arena_region_bytes(self._a))
-        dev = "cuda:%d" % chip.device
-        self.regions = [torch.as_tensor(TraceArena._Raw(int(lib().h2r_arena_region(self._a, i)), nbytes), device=dev) for i in range(regions)]
-        self.region_ms = [float(lib().h2r_arena_region_ms(self._a, i)) for i in range(regions)]
-        buf = (ctypes.c_double * (12 * candidates))()
-        n = int(lib().h2r_arena_measurements(self._a, buf, 12 * candidates))
-        self.measurements_ms = [float(buf[i]) for i in range(n)]
+        self._adopt(regions, candidates)
         return self
 
     @classmethod
@@ -1057,538 +1052,6 @@ class TraceArena:
             self.close()
         except Exception:
             pass
-
-
-class LookupArgument:
-    """halo2's lookup argument for the range checks (h2r_lookup_*): RangeChip's (tag, value) table, the per-argument
-    multiplicities of a batch of circuits and the permuted columns A' / S' for per-circuit challenges theta.
-    Third-party behaviour restated in DESIGN.md section 2c; five arguments: composition_a..d, overflow_a."""
-
-    ARGS = 5
-
-    def __init__(self, chip: BigIntChip, rsa_chip: bool = True, bit_lens: Optional[Sequence[int]] = None,
-                 tags: Optional[Sequence[int]] = None):
-        self.chip = chip
-        self.cfg = _lib.H2RLookupConfig()
-        if bit_lens is None:
-            check(lib().h2r_lookup_config_default(chip._ctx, 1 if rsa_chip else 0, ctypes.byref(self.cfg)), "h2r_lookup_config_default")
-        else:
-            n = len(bit_lens)
-            check(lib().h2r_lookup_config_custom((ctypes.c_uint32 * n)(*bit_lens), (ctypes.c_uint32 * n)(*tags), n, ctypes.byref(self.cfg)),
-                  "h2r_lookup_config_custom")
-        self.n_rows = int(self.cfg.n_rows)
-
-    def table_image(self):
-        """[(tag, value)] as load_table writes them (canonical field elements; small integers)."""
-        t = np.zeros((self.n_rows, 4), dtype=np.uint64)
-        v = np.zeros((self.n_rows, 4), dtype=np.uint64)
-        check(lib().h2r_lookup_table_image(self.chip._ctx, ctypes.byref(self.cfg), t.ctypes.data, v.ctypes.data), "h2r_lookup_table_image")
-        return [(int(a[0]), int(b[0])) for a, b in zip(t, v)]
-
-    def new_hist(self, batch: int) -> torch.Tensor:
-        return torch.zeros((batch, self.ARGS, self.n_rows), dtype=torch.int32, device="cuda:%d" % self.chip.device)
-
-    def hist_records(self, trace: Trace, hist: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Adds the lookups of every mul_mod record of every element (q / r limbs, range-assigned carries)."""
-        off = trace.pow_layout.off_records if trace.pow_layout is not None else 0
-        check(lib().h2r_lookup_hist_records(self.chip._ctx, ctypes.byref(self.cfg), trace.buf.data_ptr(), off, trace.elem_stride, trace.batch,
-                                            trace.num_mul_mods, status.data_ptr() if status is not None else None, hist.data_ptr(),
-                                            self.chip._stream()), "h2r_lookup_hist_records")
-        return hist
-
-    def hist_values(self, values: torch.Tensor, bit_len: int, sublimb_bits: int, hist: torch.Tensor) -> torch.Tensor:
-        """Adds RangeChip::assign(v, sublimb_bits, bit_len) of values[elem][:] (int32 / int64 elements)."""
-        assert values.dim() == 2 and values.is_contiguous()
-        check(lib().h2r_lookup_hist_values(self.chip._ctx, ctypes.byref(self.cfg), values.data_ptr(), values.element_size(), values.shape[1],
-                                           values.shape[0], bit_len, sublimb_bits, hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_values")
-        return hist
-
-    def hist_fresh_op(self, op_name: str, trace_buf: torch.Tensor, elem_stride: int, batch: int, hist: torch.Tensor, first_off: int = 0):
-        """Adds the range assigns inside a Fresh-op witness (e.g. "is_in_field": the assert_in_field witness of modpow_public_key)."""
-        check(lib().h2r_lookup_hist_fresh_op(self.chip._ctx, ctypes.byref(self.cfg), _lib.FRESH_OPS.index(op_name), trace_buf.data_ptr(), first_off,
-                                             elem_stride, batch, hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_fresh_op")
-        return hist
-
-    def hist_advice(self, kinds, image: torch.Tensor, batch: int, hist: torch.Tensor, status: Optional[torch.Tensor] = None, layout=None) -> torch.Tensor:
-        """The multiplicities of an advice image (h2r_lookup_hist_advice): what hist_verify / hist_records / hist_fresh_op count from a trace,
-        for a witness without records.  kinds: uint8 row kinds (numpy or device tensor)."""
-        kd = kinds if isinstance(kinds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(kinds, dtype=np.uint8)).to(image.device)
-        stride = image.shape[1] if image.dim() > 1 else image.numel() // batch
-        check(lib().h2r_lookup_hist_advice(self.chip._ctx, ctypes.byref(self.cfg), ctypes.byref(layout) if layout is not None else None, kd.data_ptr(),
-                                           kd.numel(), image.data_ptr(), stride, batch, status.data_ptr() if status is not None else None,
-                                           hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_advice")
-        self._keep = kd
-        return hist
-
-    def hist_verify(self, res, hist: torch.Tensor) -> torch.Tensor:
-        """Every lookup inside the witness of a verify_pkcs1v15_signature batch (rsa.VerifyResult): assert_in_field's range assigns,
-        the records' limbs and carries, the encoded-message check's two 4-bit range assigns (h2r_lookup_hist_verify)."""
-        check(lib().h2r_lookup_hist_verify(self.chip._ctx, ctypes.byref(self.cfg), ctypes.byref(res.layout), res.trace.data_ptr(),
-                                           res.is_valid.numel(), res.status.data_ptr(), hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_verify")
-        return hist
-
-    def permuted_columns(self, hist: torch.Tensor, thetas: Sequence[int], usable_rows: int, arg_mask: int = 31, out=None):
-        """(A', S', status): uint8 [batch, 5, usable_rows, 32] each -- canonical little-endian field elements."""
-        batch = hist.shape[0]
-        dev = hist.device
-        th = np.array([[(int(t) >> (64 * k)) & (2 ** 64 - 1) for k in range(4)] for t in thetas], dtype=np.uint64)
-        assert th.shape == (batch, 4)
-        th_dev = torch.from_numpy(th.view(np.int64)).to(dev)
-        if out is None:
-            a_perm = torch.empty((batch, self.ARGS, usable_rows, 32), dtype=torch.uint8, device=dev)
-            s_perm = torch.empty((batch, self.ARGS, usable_rows, 32), dtype=torch.uint8, device=dev)
-        else:
-            a_perm, s_perm = out
-        status = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        ws = torch.empty(int(lib().h2r_lookup_workspace_bytes(ctypes.byref(self.cfg), batch)), dtype=torch.uint8, device=dev)
-        check(lib().h2r_lookup_permuted_columns(self.chip._ctx, ctypes.byref(self.cfg), hist.data_ptr(), th_dev.data_ptr(), batch, usable_rows,
-                                                arg_mask, a_perm.data_ptr(), s_perm.data_ptr(), self.ARGS * usable_rows * 32, status.data_ptr(),
-                                                ws.data_ptr(), self.chip._stream()), "h2r_lookup_permuted_columns")
-        self._keep = (th_dev, ws)   # alive until the stream has run the kernels
-        return a_perm, s_perm, status
-
-    def _challenges(self, values: Sequence[int], batch: int, dev) -> torch.Tensor:
-        w = np.array([[(int(t) >> (64 * k)) & (2 ** 64 - 1) for k in range(4)] for t in values], dtype=np.uint64)
-        assert w.shape == (batch, 4)
-        return torch.from_numpy(w.view(np.int64)).to(dev)
-
-    def input_columns(self, kinds, image: torch.Tensor, batch: int, thetas: Sequence[int], usable_rows: int, status: Optional[torch.Tensor] = None,
-                      layout=None, first_row: int = 0, arg_mask: int = 31, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """A: uint8 [batch, 5, usable_rows, 32], the compressed lookup inputs of an advice image in ORIGINAL row order (h2r_lookup_input_columns);
-        the image's rows sit at first_row, every other usable row is 0.  thetas and A in the ctx's representation."""
-        kd = kinds if isinstance(kinds, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(kinds, dtype=np.uint8)).to(image.device)
-        stride = image.shape[1] if image.dim() > 1 else image.numel() // batch
-        th_dev = self._challenges(thetas, batch, image.device)
-        a_in = out if out is not None else torch.empty((batch, self.ARGS, usable_rows, 32), dtype=torch.uint8, device=image.device)
-        check(lib().h2r_lookup_input_columns(self.chip._ctx, ctypes.byref(self.cfg), ctypes.byref(layout) if layout is not None else None, kd.data_ptr(),
-                                             kd.numel(), image.data_ptr(), stride, batch, status.data_ptr() if status is not None else None,
-                                             th_dev.data_ptr(), usable_rows, first_row, arg_mask, a_in.data_ptr(), self.ARGS * usable_rows * 32,
-                                             self.chip._stream()), "h2r_lookup_input_columns")
-        self._keep_in = (kd, th_dev)   # alive until the stream has run the kernel
-        return a_in
-
-    def product_columns(self, a_in: torch.Tensor, a_perm: torch.Tensor, s_perm: torch.Tensor, thetas: Sequence[int], betas: Sequence[int],
-                        gammas: Sequence[int], usable_rows: int, arg_mask: int = 31, out=None):
-        """(Z, status): Z uint8 [batch, 5, usable_rows + 1, 32], halo2's lookup grand product (h2r_lookup_product_columns) in the ctx's
-        representation; status H2R_E_ASSERTION where a denominator is zero or Z[usable_rows] != 1, H2R_E_SHAPE where a challenge is not canonical.
-        out: (z, status) to write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
-        batch, dev = a_in.shape[0], a_in.device
-        ch = [self._challenges(v, batch, dev) for v in (thetas, betas, gammas)]
-        if out is None:
-            z = torch.empty((batch, self.ARGS, usable_rows + 1, 32), dtype=torch.uint8, device=dev)
-            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        else:
-            z, status = out
-        ws = torch.empty(int(lib().h2r_lookup_product_workspace_bytes(usable_rows, batch)), dtype=torch.uint8, device=dev)
-        col = (usable_rows + 1) * 32
-        check(lib().h2r_lookup_product_columns(self.chip._ctx, ctypes.byref(self.cfg), a_in.data_ptr(), a_perm.data_ptr(), s_perm.data_ptr(),
-                                               self.ARGS * usable_rows * 32, ch[0].data_ptr(), ch[1].data_ptr(), ch[2].data_ptr(), batch, usable_rows,
-                                               arg_mask, z.data_ptr(), self.ARGS * col, col, status.data_ptr(), ws.data_ptr(), self.chip._stream()),
-              "h2r_lookup_product_columns")
-        self._keep_prod = (ch, ws)   # alive until the stream has run the kernels
-        return z, status
-
-
-class PermutationArgument:
-    """halo2's permutation (copy-constraint) argument: the grand-product columns Z of permutation::prover::commit for per-circuit
-    challenges beta, gamma (h2r_permutation_product_columns).  Third-party behaviour restated in DESIGN.md section 2e.  The sigma columns
-    belong to the proving key and are the caller's.  column_src: per permutation column 0..4 = physical advice column, 5 + j = extra
-    column j; chunk_len = cs_degree - 2; delta, omega: integers in the chip's representation."""
-
-    def __init__(self, chip: BigIntChip, column_src: Sequence[int], chunk_len: int, delta: int, omega: int):
-        self.chip = chip
-        self.cfg = cfg = _lib.H2RPermutationConfig()
-        cfg.struct_size = ctypes.sizeof(cfg)
-        cfg.num_columns, cfg.chunk_len = len(column_src), chunk_len
-        if len(column_src) > _lib.H2R_PERM_MAX_COLUMNS:
-            check(_lib.H2R_E_SHAPE, "PermutationArgument")
-        cfg.n_extra = max([int(s) - 4 for s in column_src if int(s) >= 5] + [0])
-        for c, s in enumerate(column_src):
-            cfg.column_src[c] = int(s)
-        for k in range(4):
-            cfg.delta[k] = (int(delta) >> (64 * k)) & (2 ** 64 - 1)
-            cfg.omega[k] = (int(omega) >> (64 * k)) & (2 ** 64 - 1)
-        self.sets = int(lib().h2r_permutation_sets(ctypes.byref(cfg)))
-        if self.sets == 0:
-            check(_lib.H2R_E_SHAPE, "h2r_permutation_sets")
-
-    _challenges = LookupArgument._challenges
-
-    def product_columns(self, image: torch.Tensor, batch: int, rows: int, sigma: torch.Tensor, betas: Sequence[int], gammas: Sequence[int],
-                        usable_rows: int, first_row: int = 0, extra: Optional[torch.Tensor] = None, out=None):
-        """(Z, status): Z uint8 [batch, S, usable_rows + 1, 32] in the chip's representation; status H2R_E_ASSERTION where a set's
-        denominators multiply to zero or the last Z does not end at 1, H2R_E_SHAPE where a challenge is not canonical.
-        image: the advice image of `rows` rows per circuit, at first_row of the usable rows; sigma: uint8 [m, >= usable_rows, 32] shared by
-        every circuit; extra: uint8 [batch, n_extra, >= usable_rows, 32]; betas / gammas: integers in the chip's representation.
-        out: (z, status) to write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
-        dev = image.device
-        ch = [self._challenges(v, batch, dev) for v in (betas, gammas)]
-        if out is None:
-            z = torch.empty((batch, self.sets, usable_rows + 1, 32), dtype=torch.uint8, device=dev)
-            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        else:
-            z, status = out
-        assert sigma.dim() == 3 and sigma.stride(2) == 1 and sigma.stride(1) == 32 and sigma.shape[0] == self.cfg.num_columns
-        if extra is not None:
-            assert extra.dim() == 4 and extra.stride(3) == 1 and extra.stride(2) == 32
-        ws = torch.empty(int(lib().h2r_permutation_product_workspace_bytes(ctypes.byref(self.cfg), usable_rows, batch)), dtype=torch.uint8, device=dev)
-        stride = image.shape[1] if image.dim() > 1 else image.numel() // max(batch, 1)
-        check(lib().h2r_permutation_product_columns(self.chip._ctx, ctypes.byref(self.cfg), image.data_ptr(), stride, rows, first_row, batch,
-                                                    extra.data_ptr() if extra is not None else None, extra.stride(0) if extra is not None else 0,
-                                                    extra.stride(1) if extra is not None else 0, sigma.data_ptr(), sigma.stride(0),
-                                                    ch[0].data_ptr(), ch[1].data_ptr(), usable_rows, z.data_ptr(), z.stride(0), z.stride(1),
-                                                    status.data_ptr(), ws.data_ptr(), self.chip._stream()), "h2r_permutation_product_columns")
-        self._keep_prod = (ch, ws, sigma, extra, image)   # alive until the stream has run the kernels
-        return z, status
-
-
-class EvaluationDomain:
-    """halo2's poly::domain::EvaluationDomain on the device (h2r_ntt_columns; third-party behaviour restated in DESIGN.md section 2f):
-    the transforms between Lagrange, coefficient and extended (coset) form of columns of 2^k / 2^extended_k field elements.
-    omega_ext: a primitive 2^extended_k-th root of unity, zeta: the extended domain's coset shift (both integers in the chip's
-    representation); omega at k is omega_ext^(2^(extended_k - k)).  Columns are uint8 tensors [..., rows, 32] (up to two leading
-    dimensions: [batch, columns, rows, 32]) whose last two dimensions are contiguous, in the chip's representation."""
-
-    def __init__(self, chip: BigIntChip, k: int, extended_k: int, omega_ext: int, zeta: int):
-        if not 1 <= k <= extended_k:
-            check(_lib.H2R_E_SHAPE, "EvaluationDomain")
-        self.chip, self.k, self.extended_k, self.omega_ext, self.zeta = chip, int(k), int(extended_k), int(omega_ext), int(zeta)
-        self.one = self._field(6, 1) if chip.montgomery else 1
-        self.omega = self.omega_at(self.k)
-        self._keep = None
-
-    def _field(self, op: int, a: int, b: int = 0) -> int:
-        wa, wb, out = ((ctypes.c_uint64 * 4)(*[(int(v) >> (64 * i)) & (2 ** 64 - 1) for i in range(4)]) for v in (a, b, 0))
-        check(lib().h2r_field_eval(self.chip._ctx, op, wa, wb, out), "h2r_field_eval")
-        return sum(int(out[i]) << (64 * i) for i in range(4))
-
-    def omega_at(self, log_n: int) -> int:
-        """omega_ext^(2^(extended_k - log_n)): the generator of the 2^log_n domain, in the chip's representation."""
-        if not 0 < log_n <= self.extended_k:
-            check(_lib.H2R_E_SHAPE, "EvaluationDomain.omega_at")
-        w = self._field(7, self.omega_ext) if self.chip.montgomery else self.omega_ext
-        for _ in range(self.extended_k - log_n):
-            w = self._field(2, w, w)
-        return self._field(6, w) if self.chip.montgomery else w
-
-    def ntt(self, cols: torch.Tensor, log_n_out: int, inverse: bool = False, shift: Optional[int] = None, out: Optional[torch.Tensor] = None):
-        """The raw transform: forward out[j] = sum_i cols[i] * (shift * omega^j)^i onto 2^log_n_out points (the input zero-padded), or the
-        inverse of it (log_n_out = the input's size).  shift: an integer in the chip's representation (None: 1, no coset).
-        out: a tensor of the input's leading shape with 2^log_n_out rows to write into (it must not overlap the input)."""
-        rows = cols.shape[-2]
-        if cols.dtype != torch.uint8 or cols.dim() < 2 or cols.dim() > 4 or cols.shape[-1] != 32 or rows & (rows - 1) or rows == 0:
-            check(_lib.H2R_E_SHAPE, "EvaluationDomain.ntt")
-        assert cols.stride(-1) == 1 and cols.stride(-2) == 32
-        cfg = _lib.H2RNttConfig()
-        cfg.struct_size = ctypes.sizeof(cfg)
-        cfg.log_n_in, cfg.log_n_out, cfg.flags = rows.bit_length() - 1, log_n_out, _lib.H2R_NTT_INVERSE if inverse else 0
-        omega, shift = self.omega_at(log_n_out), self.one if shift is None else int(shift)
-        for i in range(4):
-            cfg.omega[i] = (omega >> (64 * i)) & (2 ** 64 - 1)
-            cfg.shift[i] = (shift >> (64 * i)) & (2 ** 64 - 1)
-        lead = tuple(cols.shape[:-2])
-        if out is None:
-            out = torch.empty(lead + (1 << log_n_out, 32), dtype=torch.uint8, device=cols.device)
-        assert tuple(out.shape) == lead + (1 << log_n_out, 32) and out.stride(-1) == 1 and out.stride(-2) == 32
-
-        def strides(t):   # (elements, element stride, columns, column stride) of [..., rows, 32]
-            col = t.shape[-2] * 32
-            if t.dim() == 2:
-                return 1, col, 1, col
-            if t.dim() == 3:
-                return 1, max(col, t.shape[0] * t.stride(0)), t.shape[0], t.stride(0)
-            return t.shape[0], t.stride(0), t.shape[1], t.stride(1)
-
-        batch, ies, ncols, ics = strides(cols)
-        _, oes, _, ocs = strides(out)
-        ws = torch.empty(max(int(lib().h2r_ntt_workspace_bytes(ctypes.byref(cfg))), 16), dtype=torch.uint8, device=cols.device)
-        check(lib().h2r_ntt_columns(self.chip._ctx, ctypes.byref(cfg), cols.data_ptr(), ies, ics, out.data_ptr(), oes, ocs, ncols, batch,
-                                    ws.data_ptr(), self.chip._stream()), "h2r_ntt_columns")
-        self._keep = (ws, cols, out)   # alive until the stream has run the kernels
-        return out
-
-    def lagrange_to_coeff(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """2^k evaluations over the domain -> the 2^k coefficients."""
-        return self.ntt(cols, self.k, inverse=True, out=out)
-
-    def coeff_to_extended(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """2^k coefficients -> the 2^extended_k evaluations over the coset zeta * <omega_ext>."""
-        return self.ntt(cols, self.extended_k, shift=self.zeta, out=out)
-
-    def extended_to_coeff(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """2^extended_k evaluations over the coset -> the 2^extended_k coefficients (truncation stays the caller's)."""
-        return self.ntt(cols, self.extended_k, inverse=True, shift=self.zeta, out=out)
-
-    def lagrange_key(self, key: "CommitKey") -> "CommitKey":
-        """The Lagrange-basis key of this domain over the first 2^k bases of `key` (halo2's g_lagrange from g): key.transform(omega, k)."""
-        return key.transform(self.omega, self.k)
-
-    def vanishing_columns(self, blinding_factors: int) -> torch.Tensor:
-        """uint8 [3, 2^extended_k, 32]: l0, l_last and l_active = 1 - l_last - l_blind of the 2^k domain with `blinding_factors` blinding
-        rows, in extended form (lagrange_to_coeff, then coeff_to_extended) -- the `l` columns of quotient()."""
-        n = 1 << self.k
-        u = n - blinding_factors - 1
-        if u < 1:
-            check(_lib.H2R_E_SHAPE, "EvaluationDomain.vanishing_columns")
-        host = np.zeros((3, n, 32), dtype=np.uint8)
-        one = np.frombuffer(int(self.one).to_bytes(32, "little"), dtype=np.uint8)
-        host[0, 0] = one
-        host[1, u] = one
-        host[2, :u] = one
-        lag = torch.from_numpy(host).to("cuda:%d" % self.chip.device)
-        return self.coeff_to_extended(self.lagrange_to_coeff(lag))
-
-    def quotient(self, blinding_factors: int, delta: int, gate_fixed: Sequence[int], column_src: Sequence[int], chunk_len: int, advice: torch.Tensor,
-                 perm_z: torch.Tensor, fixed: torch.Tensor, sigma: torch.Tensor, l: torch.Tensor, thetas: Sequence[int], betas: Sequence[int],
-                 gammas: Sequence[int], ys: Sequence[int], extra: Optional[torch.Tensor] = None, lookup_mask: int = 0,
-                 lookup_advice: Sequence[int] = (0, 1, 2, 3, 0), lookup_tag: Sequence[int] = (0,) * 5, lookup_enable: Sequence[int] = (0,) * 5,
-                 table_tag: int = 0, table_value: int = 0, lookup_a_perm: Optional[torch.Tensor] = None, lookup_s_perm: Optional[torch.Tensor] = None,
-                 lookup_z: Optional[torch.Tensor] = None, out=None):
-        """(h, status): the vanishing argument's quotient on the extended domain (h2r_quotient_columns; halo2's evaluate_h for this circuit's
-        constraint system, restated in DESIGN.md section 2g).  h: uint8 [batch, 2^extended_k, 32] in the chip's representation; status
-        H2R_E_SHAPE where a challenge is not canonical (that circuit's h is left untouched).
-        Every column is in extended form, uint8 with N = 2^extended_k rows whose last two dimensions are contiguous.  Per circuit
-        [batch, columns, N, 32]: advice (5, physical), extra (n_extra), perm_z (S), lookup_a_perm / lookup_s_perm / lookup_z (column k =
-        argument k, up to the highest bit of lookup_mask).  The proving key's [columns, N, 32]: fixed, sigma (one per permutation column), l
-        (vanishing_columns()).  gate_fixed: the indices of sa, sb, sc, sd, se, s_mul_ab, s_mul_cd, se_next, s_const among the fixed columns;
-        column_src / chunk_len as PermutationArgument; lookup_advice / lookup_tag / lookup_enable / table_tag / table_value: per argument
-        the physical advice column and the fixed columns of its input expression theta * tag + enable * advice, and of the table's.
-        delta and the challenges: integers in the chip's representation.  out: (h, status) to write into (h must overlap no input; a
-        status byte that is nonzero on entry skips the circuit; the call never clears it)."""
-        N = 1 << self.extended_k
-        batch = advice.shape[0]
-        cfg = _lib.H2RQuotientConfig()
-        cfg.struct_size = ctypes.sizeof(cfg)
-        cfg.log_n, cfg.log_ext, cfg.blinding_factors = self.k, self.extended_k, blinding_factors
-        for i in range(4):
-            cfg.omega_ext[i] = (self.omega_ext >> (64 * i)) & (2 ** 64 - 1)
-            cfg.zeta[i] = (self.zeta >> (64 * i)) & (2 ** 64 - 1)
-            cfg.delta[i] = (int(delta) >> (64 * i)) & (2 ** 64 - 1)
-        if len(column_src) > _lib.H2R_PERM_MAX_COLUMNS or len(gate_fixed) != 9 or any(len(x) != _lib.H2R_LOOKUP_ARGS for x in (lookup_advice, lookup_tag, lookup_enable)):
-            check(_lib.H2R_E_SHAPE, "EvaluationDomain.quotient")
-        cfg.num_fixed, cfg.num_columns, cfg.chunk_len, cfg.lookup_mask = fixed.shape[0], len(column_src), chunk_len, lookup_mask
-        cfg.n_extra = max([int(s) - 4 for s in column_src if int(s) >= 5] + [0])
-        for i, v in enumerate(gate_fixed):
-            cfg.gate_fixed[i] = int(v)
-        for c, s in enumerate(column_src):
-            cfg.column_src[c] = int(s)
-        for k in range(_lib.H2R_LOOKUP_ARGS):
-            cfg.lookup_advice[k], cfg.lookup_tag[k], cfg.lookup_enable[k] = int(lookup_advice[k]), int(lookup_tag[k]), int(lookup_enable[k])
-        cfg.table_tag, cfg.table_value = int(table_tag), int(table_value)
-        inp = _lib.H2RQuotientInputs()
-
-        def group(name, t, per_circuit):
-            if t is None:
-                return
-            assert t.dtype == torch.uint8 and t.dim() == (4 if per_circuit else 3) and t.shape[-1] == 32 and t.shape[-2] == N, name
-            assert t.stride(-1) == 1 and t.stride(-2) == 32 and (not per_circuit or t.shape[0] == batch), name
-            g = getattr(inp, name)
-            g.base, g.elem_stride, g.col_stride = t.data_ptr(), t.stride(0) if per_circuit else 0, t.stride(1) if per_circuit else t.stride(0)
-
-        for name, t in (("advice", advice), ("extra", extra), ("perm_z", perm_z), ("lookup_a_perm", lookup_a_perm), ("lookup_s_perm", lookup_s_perm),
-                        ("lookup_z", lookup_z)):
-            group(name, t, True)
-        for name, t in (("fixed", fixed), ("sigma", sigma), ("l", l)):
-            group(name, t, False)
-        dev = advice.device
-        ch = [LookupArgument._challenges(self, v, batch, dev) for v in (thetas, betas, gammas, ys)]
-        inp.theta, inp.beta, inp.gamma, inp.y = (c.data_ptr() for c in ch)
-        if out is None:
-            h = torch.empty((batch, N, 32), dtype=torch.uint8, device=dev)
-            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        else:
-            h, status = out
-        assert h.dim() == 3 and h.shape[1:] == (N, 32) and h.stride(2) == 1 and h.stride(1) == 32
-        check(lib().h2r_quotient_columns(self.chip._ctx, ctypes.byref(cfg), ctypes.byref(inp), batch, h.data_ptr(), h.stride(0),
-                                         status.data_ptr() if status is not None else None, self.chip._stream()), "h2r_quotient_columns")
-        self._keep_q = (ch, advice, extra, perm_z, lookup_a_perm, lookup_s_perm, lookup_z, fixed, sigma, l, h, status)   # alive until the stream has run the kernel
-        return h, status
-
-    def fold(self, cols: torch.Tensor, scalars: Sequence[int], out=None):
-        """(folded, status): folded[e][i] = sum_c scalars[e]^c * cols[e][c][i] (h2r_fold_columns), uint8 [batch, n, 32].
-        cols: uint8 [batch, C, n, 32] in coefficient form, last two dimensions contiguous; with the 2^extended_k coefficients of h viewed
-        as [batch, 2^(extended_k - k), 2^k, 32] and scalars = x^n it is the folded h of vanishing::prover::evaluate.  scalars: integers in
-        the chip's representation; status H2R_E_SHAPE where one is not canonical (that circuit is left untouched).  out: (folded, status)
-        to write into (it must overlap no input; a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
-        if cols.dtype != torch.uint8 or cols.dim() != 4 or cols.shape[-1] != 32:
-            check(_lib.H2R_E_SHAPE, "EvaluationDomain.fold")
-        assert cols.stride(-1) == 1 and cols.stride(-2) == 32
-        batch, C, n = cols.shape[:3]
-        s = LookupArgument._challenges(self, scalars, batch, cols.device)
-        if out is None:
-            folded = torch.empty((batch, n, 32), dtype=torch.uint8, device=cols.device)
-            status = torch.zeros(batch, dtype=torch.uint8, device=cols.device)
-        else:
-            folded, status = out
-        assert folded.dim() == 3 and folded.shape[1:] == (n, 32) and folded.stride(2) == 1 and folded.stride(1) == 32
-        check(lib().h2r_fold_columns(self.chip._ctx, cols.data_ptr(), cols.stride(0), cols.stride(1), C, n, s.data_ptr(), batch, folded.data_ptr(),
-                                     folded.stride(0), status.data_ptr() if status is not None else None, self.chip._stream()), "h2r_fold_columns")
-        self._keep_fold = (s, cols, folded, status)   # alive until the stream has run the kernel
-        return folded, status
-
-    def _open_columns(self, columns, batch: int, num_points: int, where: str):
-        """The descriptors of `columns` = [(tensor, point_mask)]: tensors uint8 [batch, n, 32] per circuit or [n, 32] for a key column."""
-        if not 0 < len(columns) <= _lib.H2R_OPEN_MAX_COLUMNS:
-            check(_lib.H2R_E_SHAPE, where)
-        n = columns[0][0].shape[-2]
-        cfg = _lib.H2ROpenConfig()
-        cfg.struct_size, cfg.n_coeffs, cfg.num_cols, cfg.num_points = ctypes.sizeof(cfg), n, len(columns), num_points
-        desc = (_lib.H2ROpenColumn * len(columns))()
-        for d, (t, mask) in zip(desc, columns):
-            assert t.dtype == torch.uint8 and t.dim() in (2, 3) and t.shape[-1] == 32 and t.shape[-2] == n and t.stride(-1) == 1 and t.stride(-2) == 32
-            assert t.dim() == 2 or t.shape[0] == batch
-            d.base, d.elem_stride, d.point_mask = t.data_ptr(), t.stride(0) if t.dim() == 3 else 0, int(mask)
-        return cfg, desc
-
-    def _open_points(self, points, dev) -> torch.Tensor:
-        """[batch][num_points] integers in the chip's representation -> int64 [batch, num_points, 4] on the device."""
-        w = np.array([[[(int(z) >> (64 * k)) & (2 ** 64 - 1) for k in range(4)] for z in row] for row in points], dtype=np.uint64)
-        assert w.ndim == 3 and 0 < w.shape[1] <= _lib.H2R_OPEN_MAX_POINTS
-        return torch.from_numpy(w.view(np.int64)).to(dev)
-
-    def open_eval(self, columns, points, out=None):
-        """(evals, status): evals int64 [batch, Q, 4], the evaluations of columns in coefficient form at per-circuit points
-        (h2r_open_eval_columns; halo2's eval_polynomial), in the chip's representation.
-        columns: a list of (tensor, point_mask) in the caller's transcript order, tensors uint8 [batch, n, 32], or [n, 32] for a proving-key
-        column shared by the batch; bit p of point_mask = "queried at points[e][p]".  The Q queries are the set bits in column order, points
-        ascending within a column.  points: [batch][num_points] integers in the chip's representation (the caller forms the rotations of
-        x).  status H2R_E_SHAPE where a point is not canonical (that circuit's evaluations are left untouched).  out: (evals, status) to
-        write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
-        batch, num_points = len(points), len(points[0])
-        dev = columns[0][0].device
-        cfg, desc = self._open_columns(columns, batch, num_points, "EvaluationDomain.open_eval")
-        Q = int(lib().h2r_open_queries(ctypes.byref(cfg), desc, None))
-        if Q == 0:
-            check(_lib.H2R_E_SHAPE, "h2r_open_queries")
-        pts = self._open_points(points, dev)
-        if out is None:
-            evals = torch.zeros((batch, Q, 4), dtype=torch.int64, device=dev)
-            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        else:
-            evals, status = out
-        assert evals.is_contiguous() and tuple(evals.shape) == (batch, Q, 4)
-        ws = torch.empty(max(int(lib().h2r_open_workspace_bytes(ctypes.byref(cfg), desc, batch)), 16), dtype=torch.uint8, device=dev)
-        check(lib().h2r_open_eval_columns(self.chip._ctx, ctypes.byref(cfg), desc, pts.data_ptr(), batch, evals.data_ptr(),
-                                          status.data_ptr() if status is not None else None, ws.data_ptr(), self.chip._stream()), "h2r_open_eval_columns")
-        self._keep_open = (pts, ws, [t for t, _ in columns], evals, status)   # alive until the stream has run the kernels
-        return evals, status
-
-    def open_witness(self, columns, points, vs: Sequence[int], out=None):
-        """(W, batch_evals, status): the witness polynomials of the GWC multi-open (h2r_open_witness_columns; kate_division of
-        sum_i v^i f_i by X - z per point).  W uint8 [batch, num_points, n, 32]: per point the n coefficients of the
-        quotient (the last one 0), over the columns whose mask names the point, in column order, the powers of v from v^0 for every point; a
-        point that no column queries is left as it was (zeros when the call allocates).  batch_evals int64 [batch, num_points, 4]: the
-        remainders sum v^idx f_c(z).  columns / points as open_eval; vs: per circuit, integers in the chip's representation.  status
-        H2R_E_SHAPE where a point or v is not canonical.  out: (W, batch_evals, status) to write into (W must overlap no column)."""
-        batch, num_points = len(points), len(points[0])
-        dev = columns[0][0].device
-        cfg, desc = self._open_columns(columns, batch, num_points, "EvaluationDomain.open_witness")
-        if int(lib().h2r_open_queries(ctypes.byref(cfg), desc, None)) == 0:
-            check(_lib.H2R_E_SHAPE, "h2r_open_queries")
-        n = cfg.n_coeffs
-        pts, v = self._open_points(points, dev), LookupArgument._challenges(self, vs, batch, dev)
-        if out is None:
-            W = torch.zeros((batch, num_points, n, 32), dtype=torch.uint8, device=dev)
-            be = torch.zeros((batch, num_points, 4), dtype=torch.int64, device=dev)
-            status = torch.zeros(batch, dtype=torch.uint8, device=dev)
-        else:
-            W, be, status = out
-        assert W.dim() == 4 and tuple(W.shape[1:]) == (num_points, n, 32) and W.stride(3) == 1 and W.stride(2) == 32
-        assert be is None or (be.is_contiguous() and tuple(be.shape) == (batch, num_points, 4))
-        ws = torch.empty(max(int(lib().h2r_open_workspace_bytes(ctypes.byref(cfg), desc, batch)), 16), dtype=torch.uint8, device=dev)
-        check(lib().h2r_open_witness_columns(self.chip._ctx, ctypes.byref(cfg), desc, pts.data_ptr(), v.data_ptr(), batch, W.data_ptr(), W.stride(0),
-                                             W.stride(1), be.data_ptr() if be is not None else None, status.data_ptr() if status is not None else None,
-                                             ws.data_ptr(), self.chip._stream()), "h2r_open_witness_columns")
-        self._keep_witness = (pts, v, ws, [t for t, _ in columns], W, be, status)   # alive until the stream has run the kernels
-        return W, be, status
-
-
-class CommitKey:
-    """The bases of the commitments on the device (h2r_msm_columns): n affine points of the curve of the chip's field
-    (bn256 G1 for bn254_fr; every other field is refused), 64 bytes each -- x then y, Fq elements in the chip's representation, (0, 0) the
-    identity -- as halo2curves' `ParamsKZG::g` / `g_lagrange` lie in memory for a Montgomery chip.  The bases are not validated."""
-
-    def __init__(self, chip: BigIntChip, bases: torch.Tensor):
-        if bases.dtype == torch.int64 and bases.dim() == 3 and tuple(bases.shape[1:]) == (2, 4):
-            pass
-        elif bases.dtype == torch.uint8 and bases.dim() == 2 and bases.shape[1] == 64:
-            pass
-        else:
-            check(_lib.H2R_E_SHAPE, "CommitKey")
-        assert bases.is_contiguous() and bases.is_cuda
-        self.chip, self.bases, self.n = chip, bases, int(bases.shape[0])
-
-    def _config(self, num_cols: int):
-        cfg = _lib.H2RMsmConfig()
-        cfg.struct_size, cfg.n, cfg.num_cols, cfg.reserved = ctypes.sizeof(cfg), self.n, num_cols, 0
-        return cfg
-
-    def plan(self, num_cols: int, batch: int) -> "_lib.H2RMsmInfo":
-        """window_bits, num_windows, slice_points, num_slices and workspace_bytes of a call (h2r_msm_plan, a host function)."""
-        info, cfg = _lib.H2RMsmInfo(), self._config(num_cols)
-        if lib().h2r_msm_plan(ctypes.byref(cfg), batch, ctypes.byref(info)) == 0:
-            check(_lib.H2R_E_SHAPE, "h2r_msm_plan")
-        return info
-
-    def commit(self, columns, out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
-               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """int64 [batch, num_cols, 2, 4]: the affine commitments sum_i columns[c][e][i] * bases[i] in the chip's representation, (0, 0) for the
-        identity.  columns: a list of tensors uint8 [batch, n, 32] (scalars in the chip's representation), or [n, 32] for a column the
-        whole batch shares (batch = 1 where every column is such a one).  out: the tensor to write into (it must overlap no input);
-        status: uint8 [batch], a byte that is nonzero on entry skips the circuit (its commitments are left as they were); workspace: uint8,
-        plan(num_cols, batch).workspace_bytes bytes, 16-byte aligned, the call's own until the stream has run it (allocated when None)."""
-        if not 0 < len(columns) <= _lib.H2R_MSM_MAX_COLUMNS:
-            check(_lib.H2R_E_SHAPE, "CommitKey.commit")
-        batch = next((int(t.shape[0]) for t in columns if t.dim() == 3), 1)
-        cfg = self._config(len(columns))
-        desc = (_lib.H2RMsmColumn * len(columns))()
-        for d, t in zip(desc, columns):
-            assert t.dtype == torch.uint8 and t.dim() in (2, 3) and tuple(t.shape[-2:]) == (self.n, 32) and t.stride(-1) == 1 and t.stride(-2) == 32
-            assert t.dim() == 2 or t.shape[0] == batch
-            d.base, d.elem_stride = t.data_ptr(), t.stride(0) if t.dim() == 3 else 0
-        dev = self.bases.device
-        if out is None:
-            out = torch.zeros((batch, len(columns), 2, 4), dtype=torch.int64, device=dev)
-        assert out.is_contiguous() and out.dtype == torch.int64 and tuple(out.shape) == (batch, len(columns), 2, 4)
-        need = int(lib().h2r_msm_workspace_bytes(ctypes.byref(cfg), batch))
-        ws = workspace if workspace is not None else torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
-        check(lib().h2r_msm_columns(self.chip._ctx, ctypes.byref(cfg), desc, self.bases.data_ptr(), batch, out.data_ptr(),
-                                    status.data_ptr() if status is not None else None, ws.data_ptr(), self.chip._stream()), "h2r_msm_columns")
-        self._keep = (ws, list(columns), out, status)   # alive until the stream has run the kernels
-        return out
-
-    def transform(self, omega: int, k: Optional[int] = None, inverse: bool = True, out: Optional[torch.Tensor] = None,
-                  workspace: Optional[torch.Tensor] = None) -> "CommitKey":
-        """A new key over the transform of the first 2^k bases (h2r_curve_ntt): inverse (the default)
-        out[i] = [n^-1] sum_j [omega^(-i j)] bases[j] -- with the powers of tau as bases and the domain's omega, halo2's g_lagrange --,
-        forward out[i] = sum_j [omega^(i j)] bases[j].  omega: a primitive 2^k-th root of unity of the chip's field, an integer in the chip's
-        representation.  k: log2 n by default; a key whose n is no power of two needs an explicit k <= log2 n.  out: the tensor of 2^k
-        points to write into (the layout of `bases`; it must overlap neither the bases nor the workspace); workspace: uint8,
-        h2r_curve_ntt_workspace_bytes bytes, 16-byte aligned, the call's own until the stream has run it (allocated when None)."""
-        if k is None:
-            k = self.n.bit_length() - 1
-            if self.n != 1 << k:
-                check(_lib.H2R_E_SHAPE, "CommitKey.transform")
-        k = int(k)
-        if k < 1 or (1 << k) > self.n:
-            check(_lib.H2R_E_SHAPE, "CommitKey.transform")
-        cfg = _lib.H2RCurveNttConfig()
-        cfg.struct_size, cfg.log_n, cfg.flags, cfg.reserved = ctypes.sizeof(cfg), k, _lib.H2R_CURVE_NTT_INVERSE if inverse else 0, 0
-        for i in range(4):
-            cfg.omega[i] = (int(omega) >> (64 * i)) & (2 ** 64 - 1)
-        n, dev = 1 << k, self.bases.device
-        if out is None:
-            out = torch.zeros((n, 2, 4), dtype=torch.int64, device=dev) if self.bases.dtype == torch.int64 else torch.zeros((n, 64), dtype=torch.uint8, device=dev)
-        assert out.is_contiguous() and out.is_cuda and out.numel() * out.element_size() == 64 * n
-        need = int(lib().h2r_curve_ntt_workspace_bytes(ctypes.byref(cfg)))
-        ws = workspace if workspace is not None else torch.empty(max(need, 16), dtype=torch.uint8, device=dev)
-        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
-        check(lib().h2r_curve_ntt(self.chip._ctx, ctypes.byref(cfg), self.bases.data_ptr(), out.data_ptr(), ws.data_ptr(), self.chip._stream()),
-              "h2r_curve_ntt")
-        key = CommitKey(self.chip, out)
-        key._keep = (ws, self.bases, out)   # alive until the stream has run the kernels
-        return key
 
 
 @dataclass

@@ -1,0 +1,458 @@
+"""The prover stages on the device: halo2's lookup and permutation arguments, the evaluation domain (transforms, quotient, openings) and
+the commitment key.  None of them has a counterpart in the reference's `big_integer` module; `big_integer` re-exports the four classes.
+All arithmetic happens in libh2r.so; every method marshals its arguments with `_marshal` and makes the call.
+A chip is whatever has `_ctx`, `_stream()`, `device` and `montgomery` (big_integer.BigIntChip)."""
+import ctypes
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, lib
+from ._marshal import challenges, column_group, from_words, hold, image_stride, is_columns, kinds_tensor, outputs, ptr, ref, set_words, words, workspace
+
+
+class LookupArgument:
+    """halo2's lookup argument for the range checks (h2r_lookup_*): RangeChip's (tag, value) table, the per-argument
+    multiplicities of a batch of circuits and the permuted columns A' / S' for per-circuit challenges theta.
+    Third-party behaviour restated in DESIGN.md section 2c; five arguments: composition_a..d, overflow_a."""
+
+    ARGS = 5
+
+    def __init__(self, chip: "BigIntChip", rsa_chip: bool = True, bit_lens: Optional[Sequence[int]] = None,
+                 tags: Optional[Sequence[int]] = None):
+        self.chip = chip
+        self.cfg = _lib.H2RLookupConfig()
+        if bit_lens is None:
+            check(lib().h2r_lookup_config_default(chip._ctx, 1 if rsa_chip else 0, ctypes.byref(self.cfg)), "h2r_lookup_config_default")
+        else:
+            n = len(bit_lens)
+            check(lib().h2r_lookup_config_custom((ctypes.c_uint32 * n)(*bit_lens), (ctypes.c_uint32 * n)(*tags), n, ctypes.byref(self.cfg)),
+                  "h2r_lookup_config_custom")
+        self.n_rows = int(self.cfg.n_rows)
+
+    def table_image(self):
+        """[(tag, value)] as load_table writes them (canonical field elements; small integers)."""
+        t = np.zeros((self.n_rows, 4), dtype=np.uint64)
+        v = np.zeros((self.n_rows, 4), dtype=np.uint64)
+        check(lib().h2r_lookup_table_image(self.chip._ctx, ctypes.byref(self.cfg), t.ctypes.data, v.ctypes.data), "h2r_lookup_table_image")
+        return [(int(a[0]), int(b[0])) for a, b in zip(t, v)]
+
+    def new_hist(self, batch: int) -> torch.Tensor:
+        return torch.zeros((batch, self.ARGS, self.n_rows), dtype=torch.int32, device="cuda:%d" % self.chip.device)
+
+    def hist_records(self, trace: "Trace", hist: torch.Tensor, status: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Adds the lookups of every mul_mod record of every element (q / r limbs, range-assigned carries)."""
+        off = trace.pow_layout.off_records if trace.pow_layout is not None else 0
+        check(lib().h2r_lookup_hist_records(self.chip._ctx, ctypes.byref(self.cfg), trace.buf.data_ptr(), off, trace.elem_stride, trace.batch,
+                                            trace.num_mul_mods, ptr(status), hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_records")
+        return hist
+
+    def hist_values(self, values: torch.Tensor, bit_len: int, sublimb_bits: int, hist: torch.Tensor) -> torch.Tensor:
+        """Adds RangeChip::assign(v, sublimb_bits, bit_len) of values[elem][:] (int32 / int64 elements)."""
+        assert values.dim() == 2 and values.is_contiguous()
+        check(lib().h2r_lookup_hist_values(self.chip._ctx, ctypes.byref(self.cfg), values.data_ptr(), values.element_size(), values.shape[1],
+                                           values.shape[0], bit_len, sublimb_bits, hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_values")
+        return hist
+
+    def hist_fresh_op(self, op_name: str, trace_buf: torch.Tensor, elem_stride: int, batch: int, hist: torch.Tensor, first_off: int = 0):
+        """Adds the range assigns inside a Fresh-op witness (e.g. "is_in_field": the assert_in_field witness of modpow_public_key)."""
+        check(lib().h2r_lookup_hist_fresh_op(self.chip._ctx, ctypes.byref(self.cfg), _lib.FRESH_OPS.index(op_name), trace_buf.data_ptr(), first_off,
+                                             elem_stride, batch, hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_fresh_op")
+        return hist
+
+    def hist_advice(self, kinds, image: torch.Tensor, batch: int, hist: torch.Tensor, status: Optional[torch.Tensor] = None, layout=None) -> torch.Tensor:
+        """The multiplicities of an advice image (h2r_lookup_hist_advice): what hist_verify / hist_records / hist_fresh_op count from a trace,
+        for a witness without records.  kinds: uint8 row kinds (numpy or device tensor)."""
+        kd = kinds_tensor(kinds, image.device)
+        check(lib().h2r_lookup_hist_advice(self.chip._ctx, ctypes.byref(self.cfg), ref(layout), kd.data_ptr(), kd.numel(), image.data_ptr(),
+                                           image_stride(image, batch), batch, ptr(status), hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_advice")
+        hold(self, "hist_advice", kd)
+        return hist
+
+    def hist_verify(self, res, hist: torch.Tensor) -> torch.Tensor:
+        """Every lookup inside the witness of a verify_pkcs1v15_signature batch (rsa.VerifyResult): assert_in_field's range assigns,
+        the records' limbs and carries, the encoded-message check's two 4-bit range assigns (h2r_lookup_hist_verify)."""
+        check(lib().h2r_lookup_hist_verify(self.chip._ctx, ctypes.byref(self.cfg), ctypes.byref(res.layout), res.trace.data_ptr(),
+                                           res.is_valid.numel(), res.status.data_ptr(), hist.data_ptr(), self.chip._stream()), "h2r_lookup_hist_verify")
+        return hist
+
+    def permuted_columns(self, hist: torch.Tensor, thetas: Sequence[int], usable_rows: int, arg_mask: int = 31, out=None):
+        """(A', S', status): uint8 [batch, 5, usable_rows, 32] each -- canonical little-endian field elements."""
+        batch, dev = hist.shape[0], hist.device
+        th_dev = challenges(thetas, dev, batch)
+        cols = (torch.empty, torch.uint8, (batch, self.ARGS, usable_rows, 32))
+        a_perm, s_perm = outputs(out, dev, cols, cols)
+        status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+        ws = workspace(lib().h2r_lookup_workspace_bytes(ctypes.byref(self.cfg), batch), dev, floor=0)
+        check(lib().h2r_lookup_permuted_columns(self.chip._ctx, ctypes.byref(self.cfg), hist.data_ptr(), th_dev.data_ptr(), batch, usable_rows,
+                                                arg_mask, a_perm.data_ptr(), s_perm.data_ptr(), self.ARGS * usable_rows * 32, status.data_ptr(),
+                                                ws.data_ptr(), self.chip._stream()), "h2r_lookup_permuted_columns")
+        hold(self, "permuted_columns", th_dev, ws)
+        return a_perm, s_perm, status
+
+    def input_columns(self, kinds, image: torch.Tensor, batch: int, thetas: Sequence[int], usable_rows: int, status: Optional[torch.Tensor] = None,
+                      layout=None, first_row: int = 0, arg_mask: int = 31, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """A: uint8 [batch, 5, usable_rows, 32], the compressed lookup inputs of an advice image in ORIGINAL row order (h2r_lookup_input_columns);
+        the image's rows sit at first_row, every other usable row is 0.  thetas and A in the ctx's representation."""
+        kd = kinds_tensor(kinds, image.device)
+        th_dev = challenges(thetas, image.device, batch)
+        a_in = outputs(out, image.device, (torch.empty, torch.uint8, (batch, self.ARGS, usable_rows, 32)))
+        check(lib().h2r_lookup_input_columns(self.chip._ctx, ctypes.byref(self.cfg), ref(layout), kd.data_ptr(), kd.numel(), image.data_ptr(),
+                                             image_stride(image, batch), batch, ptr(status), th_dev.data_ptr(), usable_rows, first_row, arg_mask,
+                                             a_in.data_ptr(), self.ARGS * usable_rows * 32, self.chip._stream()), "h2r_lookup_input_columns")
+        hold(self, "input_columns", kd, th_dev)
+        return a_in
+
+    def product_columns(self, a_in: torch.Tensor, a_perm: torch.Tensor, s_perm: torch.Tensor, thetas: Sequence[int], betas: Sequence[int],
+                        gammas: Sequence[int], usable_rows: int, arg_mask: int = 31, out=None):
+        """(Z, status): Z uint8 [batch, 5, usable_rows + 1, 32], halo2's lookup grand product (h2r_lookup_product_columns) in the ctx's
+        representation; status H2R_E_ASSERTION where a denominator is zero or Z[usable_rows] != 1, H2R_E_SHAPE where a challenge is not canonical.
+        out: (z, status) to write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        batch, dev = a_in.shape[0], a_in.device
+        ch = [challenges(v, dev, batch) for v in (thetas, betas, gammas)]
+        z, status = outputs(out, dev, (torch.empty, torch.uint8, (batch, self.ARGS, usable_rows + 1, 32)), status=batch)
+        ws = workspace(lib().h2r_lookup_product_workspace_bytes(usable_rows, batch), dev, floor=0)
+        col = (usable_rows + 1) * 32
+        check(lib().h2r_lookup_product_columns(self.chip._ctx, ctypes.byref(self.cfg), a_in.data_ptr(), a_perm.data_ptr(), s_perm.data_ptr(),
+                                               self.ARGS * usable_rows * 32, ch[0].data_ptr(), ch[1].data_ptr(), ch[2].data_ptr(), batch, usable_rows,
+                                               arg_mask, z.data_ptr(), self.ARGS * col, col, status.data_ptr(), ws.data_ptr(), self.chip._stream()),
+              "h2r_lookup_product_columns")
+        hold(self, "product_columns", ch, ws)
+        return z, status
+
+
+def _permutation_columns(cfg, column_src):
+    """column_src (per permutation column 0..4 = physical advice column, 5 + j = extra column j) and what follows from it, into a config."""
+    cfg.num_columns = len(column_src)
+    cfg.n_extra = max([int(s) - 4 for s in column_src if int(s) >= 5] + [0])
+    for c, s in enumerate(column_src):
+        cfg.column_src[c] = int(s)
+
+
+class PermutationArgument:
+    """halo2's permutation (copy-constraint) argument: the grand-product columns Z of permutation::prover::commit for per-circuit
+    challenges beta, gamma (h2r_permutation_product_columns).  Third-party behaviour restated in DESIGN.md section 2e.  The sigma columns
+    belong to the proving key and are the caller's.  column_src: per permutation column 0..4 = physical advice column, 5 + j = extra
+    column j; chunk_len = cs_degree - 2; delta, omega: integers in the chip's representation."""
+
+    def __init__(self, chip: "BigIntChip", column_src: Sequence[int], chunk_len: int, delta: int, omega: int):
+        self.chip = chip
+        self.cfg = cfg = _lib.H2RPermutationConfig(struct_size=ctypes.sizeof(_lib.H2RPermutationConfig), chunk_len=chunk_len)
+        if len(column_src) > _lib.H2R_PERM_MAX_COLUMNS:
+            check(_lib.H2R_E_SHAPE, "PermutationArgument")
+        _permutation_columns(cfg, column_src)
+        set_words(cfg.delta, delta)
+        set_words(cfg.omega, omega)
+        self.sets = int(lib().h2r_permutation_sets(ctypes.byref(cfg)))
+        if self.sets == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_permutation_sets")
+
+    def product_columns(self, image: torch.Tensor, batch: int, rows: int, sigma: torch.Tensor, betas: Sequence[int], gammas: Sequence[int],
+                        usable_rows: int, first_row: int = 0, extra: Optional[torch.Tensor] = None, out=None):
+        """(Z, status): Z uint8 [batch, S, usable_rows + 1, 32] in the chip's representation; status H2R_E_ASSERTION where a set's
+        denominators multiply to zero or the last Z does not end at 1, H2R_E_SHAPE where a challenge is not canonical.
+        image: the advice image of `rows` rows per circuit, at first_row of the usable rows; sigma: uint8 [m, >= usable_rows, 32] shared by
+        every circuit; extra: uint8 [batch, n_extra, >= usable_rows, 32]; betas / gammas: integers in the chip's representation.
+        out: (z, status) to write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        dev = image.device
+        ch = [challenges(v, dev, batch) for v in (betas, gammas)]
+        z, status = outputs(out, dev, (torch.empty, torch.uint8, (batch, self.sets, usable_rows + 1, 32)), status=batch)
+        assert is_columns(sigma, dims=(3,)) and sigma.shape[0] == self.cfg.num_columns
+        assert extra is None or is_columns(extra, dims=(4,))
+        ws = workspace(lib().h2r_permutation_product_workspace_bytes(ctypes.byref(self.cfg), usable_rows, batch), dev, floor=0)
+        check(lib().h2r_permutation_product_columns(self.chip._ctx, ctypes.byref(self.cfg), image.data_ptr(), image_stride(image, batch), rows,
+                                                    first_row, batch, *(column_group(extra, True) if extra is not None else (None, 0, 0)), sigma.data_ptr(), sigma.stride(0),
+                                                    ch[0].data_ptr(), ch[1].data_ptr(), usable_rows, z.data_ptr(), z.stride(0), z.stride(1),
+                                                    status.data_ptr(), ws.data_ptr(), self.chip._stream()), "h2r_permutation_product_columns")
+        hold(self, "product_columns", ch, ws, sigma, extra, image)
+        return z, status
+
+
+class EvaluationDomain:
+    """halo2's poly::domain::EvaluationDomain on the device (h2r_ntt_columns; third-party behaviour restated in DESIGN.md section 2f):
+    the transforms between Lagrange, coefficient and extended (coset) form of columns of 2^k / 2^extended_k field elements.
+    omega_ext: a primitive 2^extended_k-th root of unity, zeta: the extended domain's coset shift (both integers in the chip's
+    representation); omega at k is omega_ext^(2^(extended_k - k)).  Columns are uint8 tensors [..., rows, 32] (up to two leading
+    dimensions: [batch, columns, rows, 32]) whose last two dimensions are contiguous, in the chip's representation."""
+
+    def __init__(self, chip: "BigIntChip", k: int, extended_k: int, omega_ext: int, zeta: int):
+        if not 1 <= k <= extended_k:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain")
+        self.chip, self.k, self.extended_k, self.omega_ext, self.zeta = chip, int(k), int(extended_k), int(omega_ext), int(zeta)
+        self.one = self._field(_lib.FIELD_TO_MONTGOMERY, 1) if chip.montgomery else 1
+        self.omega = self.omega_at(self.k)
+
+    def _field(self, op: int, a: int, b: int = 0) -> int:
+        wa, wb, out = ((ctypes.c_uint64 * 4)(*words(v)) for v in (a, b, 0))
+        check(lib().h2r_field_eval(self.chip._ctx, op, wa, wb, out), "h2r_field_eval")
+        return from_words(out)
+
+    def omega_at(self, log_n: int) -> int:
+        """omega_ext^(2^(extended_k - log_n)): the generator of the 2^log_n domain, in the chip's representation."""
+        if not 0 < log_n <= self.extended_k:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.omega_at")
+        w = self._field(_lib.FIELD_FROM_MONTGOMERY, self.omega_ext) if self.chip.montgomery else self.omega_ext
+        for _ in range(self.extended_k - log_n):
+            w = self._field(_lib.FIELD_MUL, w, w)
+        return self._field(_lib.FIELD_TO_MONTGOMERY, w) if self.chip.montgomery else w
+
+    def ntt(self, cols: torch.Tensor, log_n_out: int, inverse: bool = False, shift: Optional[int] = None, out: Optional[torch.Tensor] = None):
+        """The raw transform: forward out[j] = sum_i cols[i] * (shift * omega^j)^i onto 2^log_n_out points (the input zero-padded), or the
+        inverse of it (log_n_out = the input's size).  shift: an integer in the chip's representation (None: 1, no coset).
+        out: a tensor of the input's leading shape with 2^log_n_out rows to write into (it must not overlap the input)."""
+        rows = cols.shape[-2]
+        if not is_columns(cols, dims=(2, 3, 4), strides=False) or rows & (rows - 1) or rows == 0:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.ntt")
+        assert is_columns(cols)
+        cfg = _lib.H2RNttConfig(struct_size=ctypes.sizeof(_lib.H2RNttConfig), log_n_in=rows.bit_length() - 1, log_n_out=log_n_out,
+                                flags=_lib.H2R_NTT_INVERSE if inverse else 0)
+        set_words(cfg.omega, self.omega_at(log_n_out))
+        set_words(cfg.shift, self.one if shift is None else shift)
+        lead = tuple(cols.shape[:-2])
+        out = outputs(out, cols.device, (torch.empty, torch.uint8, lead + (1 << log_n_out, 32)))
+        assert tuple(out.shape[:-2]) == lead and is_columns(out, rows=1 << log_n_out)
+        (_, ies, ics), (_, oes, ocs) = column_group(cols, len(lead) == 2), column_group(out, len(lead) == 2)
+        batch, ncols = ((1, 1) + lead)[-2:]
+        if len(lead) < 2:   # one element: its stride is the reach of its columns
+            ies, oes = max(rows * 32, ncols * ics), max(32 << log_n_out, ncols * ocs)
+        ws = workspace(lib().h2r_ntt_workspace_bytes(ctypes.byref(cfg)), cols.device)
+        check(lib().h2r_ntt_columns(self.chip._ctx, ctypes.byref(cfg), cols.data_ptr(), ies, ics, out.data_ptr(), oes, ocs, ncols, batch,
+                                    ws.data_ptr(), self.chip._stream()), "h2r_ntt_columns")
+        hold(self, "ntt", ws, cols, out)
+        return out
+
+    def lagrange_to_coeff(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """2^k evaluations over the domain -> the 2^k coefficients."""
+        return self.ntt(cols, self.k, inverse=True, out=out)
+
+    def coeff_to_extended(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """2^k coefficients -> the 2^extended_k evaluations over the coset zeta * <omega_ext>."""
+        return self.ntt(cols, self.extended_k, shift=self.zeta, out=out)
+
+    def extended_to_coeff(self, cols: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """2^extended_k evaluations over the coset -> the 2^extended_k coefficients (truncation stays the caller's)."""
+        return self.ntt(cols, self.extended_k, inverse=True, shift=self.zeta, out=out)
+
+    def lagrange_key(self, key: "CommitKey") -> "CommitKey":
+        """The Lagrange-basis key of this domain over the first 2^k bases of `key` (halo2's g_lagrange from g): key.transform(omega, k)."""
+        return key.transform(self.omega, self.k)
+
+    def vanishing_columns(self, blinding_factors: int) -> torch.Tensor:
+        """uint8 [3, 2^extended_k, 32]: l0, l_last and l_active = 1 - l_last - l_blind of the 2^k domain with `blinding_factors` blinding
+        rows, in extended form (lagrange_to_coeff, then coeff_to_extended) -- the `l` columns of quotient()."""
+        n = 1 << self.k
+        u = n - blinding_factors - 1
+        if u < 1:
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.vanishing_columns")
+        host = np.zeros((3, n, 32), dtype=np.uint8)
+        one = np.frombuffer(int(self.one).to_bytes(32, "little"), dtype=np.uint8)
+        host[0, 0] = one
+        host[1, u] = one
+        host[2, :u] = one
+        lag = torch.from_numpy(host).to("cuda:%d" % self.chip.device)
+        return self.coeff_to_extended(self.lagrange_to_coeff(lag))
+
+    def quotient(self, blinding_factors: int, delta: int, gate_fixed: Sequence[int], column_src: Sequence[int], chunk_len: int, advice: torch.Tensor,
+                 perm_z: torch.Tensor, fixed: torch.Tensor, sigma: torch.Tensor, l: torch.Tensor, thetas: Sequence[int], betas: Sequence[int],
+                 gammas: Sequence[int], ys: Sequence[int], extra: Optional[torch.Tensor] = None, lookup_mask: int = 0,
+                 lookup_advice: Sequence[int] = (0, 1, 2, 3, 0), lookup_tag: Sequence[int] = (0,) * 5, lookup_enable: Sequence[int] = (0,) * 5,
+                 table_tag: int = 0, table_value: int = 0, lookup_a_perm: Optional[torch.Tensor] = None, lookup_s_perm: Optional[torch.Tensor] = None,
+                 lookup_z: Optional[torch.Tensor] = None, out=None):
+        """(h, status): the vanishing argument's quotient on the extended domain (h2r_quotient_columns; halo2's evaluate_h for this circuit's
+        constraint system, restated in DESIGN.md section 2g).  h: uint8 [batch, 2^extended_k, 32] in the chip's representation; status
+        H2R_E_SHAPE where a challenge is not canonical (that circuit's h is left untouched).
+        Every column is in extended form, uint8 with N = 2^extended_k rows whose last two dimensions are contiguous.  Per circuit
+        [batch, columns, N, 32]: advice (5, physical), extra (n_extra), perm_z (S), lookup_a_perm / lookup_s_perm / lookup_z (column k =
+        argument k, up to the highest bit of lookup_mask).  The proving key's [columns, N, 32]: fixed, sigma (one per permutation column), l
+        (vanishing_columns()).  gate_fixed: the indices of sa, sb, sc, sd, se, s_mul_ab, s_mul_cd, se_next, s_const among the fixed columns;
+        column_src / chunk_len as PermutationArgument; lookup_advice / lookup_tag / lookup_enable / table_tag / table_value: per argument
+        the physical advice column and the fixed columns of its input expression theta * tag + enable * advice, and of the table's.
+        delta and the challenges: integers in the chip's representation.  out: (h, status) to write into (h must overlap no input; a
+        status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        N = 1 << self.extended_k
+        batch, dev = advice.shape[0], advice.device
+        cfg = _lib.H2RQuotientConfig(struct_size=ctypes.sizeof(_lib.H2RQuotientConfig), log_n=self.k, log_ext=self.extended_k, blinding_factors=blinding_factors)
+        set_words(cfg.omega_ext, self.omega_ext)
+        set_words(cfg.zeta, self.zeta)
+        set_words(cfg.delta, delta)
+        if len(column_src) > _lib.H2R_PERM_MAX_COLUMNS or len(gate_fixed) != 9 or any(len(x) != _lib.H2R_LOOKUP_ARGS for x in (lookup_advice, lookup_tag, lookup_enable)):
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.quotient")
+        cfg.num_fixed, cfg.chunk_len, cfg.lookup_mask = fixed.shape[0], chunk_len, lookup_mask
+        _permutation_columns(cfg, column_src)
+        for i, v in enumerate(gate_fixed):
+            cfg.gate_fixed[i] = int(v)
+        for k in range(_lib.H2R_LOOKUP_ARGS):
+            cfg.lookup_advice[k], cfg.lookup_tag[k], cfg.lookup_enable[k] = int(lookup_advice[k]), int(lookup_tag[k]), int(lookup_enable[k])
+        cfg.table_tag, cfg.table_value = int(table_tag), int(table_value)
+        inp = _lib.H2RQuotientInputs()
+        per_circuit = {"advice": advice, "extra": extra, "perm_z": perm_z, "lookup_a_perm": lookup_a_perm, "lookup_s_perm": lookup_s_perm,
+                       "lookup_z": lookup_z}
+        for name, t in list(per_circuit.items()) + [("fixed", fixed), ("sigma", sigma), ("l", l)]:
+            if t is not None:
+                pc = name in per_circuit
+                assert is_columns(t, rows=N, dims=(4 if pc else 3,), batch=batch if pc else None), name
+                g = getattr(inp, name)
+                g.base, g.elem_stride, g.col_stride = column_group(t, pc)
+        ch = [challenges(v, dev, batch) for v in (thetas, betas, gammas, ys)]
+        inp.theta, inp.beta, inp.gamma, inp.y = (c.data_ptr() for c in ch)
+        h, status = outputs(out, dev, (torch.empty, torch.uint8, (batch, N, 32)), status=batch)
+        assert is_columns(h, rows=N, dims=(3,))
+        check(lib().h2r_quotient_columns(self.chip._ctx, ctypes.byref(cfg), ctypes.byref(inp), batch, h.data_ptr(), h.stride(0), ptr(status),
+                                         self.chip._stream()), "h2r_quotient_columns")
+        hold(self, "quotient", ch, advice, extra, perm_z, lookup_a_perm, lookup_s_perm, lookup_z, fixed, sigma, l, h, status)
+        return h, status
+
+    def fold(self, cols: torch.Tensor, scalars: Sequence[int], out=None):
+        """(folded, status): folded[e][i] = sum_c scalars[e]^c * cols[e][c][i] (h2r_fold_columns), uint8 [batch, n, 32].
+        cols: uint8 [batch, C, n, 32] in coefficient form, last two dimensions contiguous; with the 2^extended_k coefficients of h viewed
+        as [batch, 2^(extended_k - k), 2^k, 32] and scalars = x^n it is the folded h of vanishing::prover::evaluate.  scalars: integers in
+        the chip's representation; status H2R_E_SHAPE where one is not canonical (that circuit is left untouched).  out: (folded, status)
+        to write into (it must overlap no input; a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        if not is_columns(cols, dims=(4,), strides=False):
+            check(_lib.H2R_E_SHAPE, "EvaluationDomain.fold")
+        assert is_columns(cols)
+        batch, C, n = cols.shape[:3]
+        s = challenges(scalars, cols.device, batch)
+        folded, status = outputs(out, cols.device, (torch.empty, torch.uint8, (batch, n, 32)), status=batch)
+        assert is_columns(folded, rows=n, dims=(3,))
+        check(lib().h2r_fold_columns(self.chip._ctx, cols.data_ptr(), cols.stride(0), cols.stride(1), C, n, s.data_ptr(), batch, folded.data_ptr(),
+                                     folded.stride(0), ptr(status), self.chip._stream()), "h2r_fold_columns")
+        hold(self, "fold", s, cols, folded, status)
+        return folded, status
+
+    def _open_args(self, columns, points, where: str):
+        """(cfg, descriptors, Q, points int64 [batch, num_points, 4] on the device) of `columns` = [(tensor, point_mask)], tensors uint8
+        [batch, n, 32] per circuit or [n, 32] for a key column, and `points` = [batch][num_points] integers in the chip's representation."""
+        batch, num_points, dev = len(points), len(points[0]), columns[0][0].device
+        if not 0 < len(columns) <= _lib.H2R_OPEN_MAX_COLUMNS:
+            check(_lib.H2R_E_SHAPE, where)
+        n = columns[0][0].shape[-2]
+        cfg = _lib.H2ROpenConfig(struct_size=ctypes.sizeof(_lib.H2ROpenConfig), n_coeffs=n, num_cols=len(columns), num_points=num_points)
+        desc = (_lib.H2ROpenColumn * len(columns))()
+        for d, (t, mask) in zip(desc, columns):
+            assert is_columns(t, rows=n, dims=(2, 3), batch=batch)
+            (d.base, d.elem_stride, _), d.point_mask = column_group(t, t.dim() == 3), int(mask)
+        Q = int(lib().h2r_open_queries(ctypes.byref(cfg), desc, None))
+        if Q == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_open_queries")
+        pts = challenges(points, dev)
+        assert pts.dim() == 3 and 0 < pts.shape[1] <= _lib.H2R_OPEN_MAX_POINTS
+        return cfg, desc, Q, pts
+
+    def open_eval(self, columns, points, out=None):
+        """(evals, status): evals int64 [batch, Q, 4], the evaluations of columns in coefficient form at per-circuit points
+        (h2r_open_eval_columns; halo2's eval_polynomial), in the chip's representation.
+        columns: a list of (tensor, point_mask) in the caller's transcript order, tensors uint8 [batch, n, 32], or [n, 32] for a proving-key
+        column shared by the batch; bit p of point_mask = "queried at points[e][p]".  The Q queries are the set bits in column order, points
+        ascending within a column.  points: [batch][num_points] integers in the chip's representation (the caller forms the rotations of
+        x).  status H2R_E_SHAPE where a point is not canonical (that circuit's evaluations are left untouched).  out: (evals, status) to
+        write into (a status byte that is nonzero on entry skips the circuit; the call never clears it)."""
+        cfg, desc, Q, pts = self._open_args(columns, points, "EvaluationDomain.open_eval")
+        batch, dev = pts.shape[0], pts.device
+        evals, status = outputs(out, dev, (torch.zeros, torch.int64, (batch, Q, 4)), status=batch)
+        assert evals.is_contiguous() and tuple(evals.shape) == (batch, Q, 4)
+        ws = workspace(lib().h2r_open_workspace_bytes(ctypes.byref(cfg), desc, batch), dev)
+        check(lib().h2r_open_eval_columns(self.chip._ctx, ctypes.byref(cfg), desc, pts.data_ptr(), batch, evals.data_ptr(), ptr(status),
+                                          ws.data_ptr(), self.chip._stream()), "h2r_open_eval_columns")
+        hold(self, "open_eval", pts, ws, [t for t, _ in columns], evals, status)
+        return evals, status
+
+    def open_witness(self, columns, points, vs: Sequence[int], out=None):
+        """(W, batch_evals, status): the witness polynomials of the GWC multi-open (h2r_open_witness_columns; kate_division of
+        sum_i v^i f_i by X - z per point).  W uint8 [batch, num_points, n, 32]: per point the n coefficients of the
+        quotient (the last one 0), over the columns whose mask names the point, in column order, the powers of v from v^0 for every point; a
+        point that no column queries is left as it was (zeros when the call allocates).  batch_evals int64 [batch, num_points, 4]: the
+        remainders sum v^idx f_c(z).  columns / points as open_eval; vs: per circuit, integers in the chip's representation.  status
+        H2R_E_SHAPE where a point or v is not canonical.  out: (W, batch_evals, status) to write into (W must overlap no column)."""
+        cfg, desc, _, pts = self._open_args(columns, points, "EvaluationDomain.open_witness")
+        (batch, num_points), n, dev = pts.shape[:2], cfg.n_coeffs, pts.device
+        v = challenges(vs, dev, batch)
+        W, be, status = outputs(out, dev, (torch.zeros, torch.uint8, (batch, num_points, n, 32)), (torch.zeros, torch.int64, (batch, num_points, 4)), status=batch)
+        assert is_columns(W, rows=n, dims=(4,)) and W.shape[1] == num_points
+        assert be is None or (be.is_contiguous() and tuple(be.shape) == (batch, num_points, 4))
+        ws = workspace(lib().h2r_open_workspace_bytes(ctypes.byref(cfg), desc, batch), dev)
+        check(lib().h2r_open_witness_columns(self.chip._ctx, ctypes.byref(cfg), desc, pts.data_ptr(), v.data_ptr(), batch, W.data_ptr(), W.stride(0),
+                                             W.stride(1), ptr(be), ptr(status), ws.data_ptr(), self.chip._stream()), "h2r_open_witness_columns")
+        hold(self, "open_witness", pts, v, ws, [t for t, _ in columns], W, be, status)
+        return W, be, status
+
+
+class CommitKey:
+    """The bases of the commitments on the device (h2r_msm_columns): n affine points of the curve of the chip's field
+    (bn256 G1 for bn254_fr; every other field is refused), 64 bytes each -- x then y, Fq elements in the chip's representation, (0, 0) the
+    identity -- as halo2curves' `ParamsKZG::g` / `g_lagrange` lie in memory for a Montgomery chip.  The bases are not validated."""
+
+    def __init__(self, chip: "BigIntChip", bases: torch.Tensor):
+        words_form = bases.dtype == torch.int64 and bases.dim() == 3 and tuple(bases.shape[1:]) == (2, 4)
+        if not words_form and not (bases.dtype == torch.uint8 and bases.dim() == 2 and bases.shape[1] == 64):
+            check(_lib.H2R_E_SHAPE, "CommitKey")
+        assert bases.is_contiguous() and bases.is_cuda
+        self.chip, self.bases, self.n = chip, bases, int(bases.shape[0])
+
+    def _config(self, num_cols: int):
+        return _lib.H2RMsmConfig(struct_size=ctypes.sizeof(_lib.H2RMsmConfig), n=self.n, num_cols=num_cols, reserved=0)
+
+    def _workspace(self, given, need: int):
+        """The caller's workspace, or a new one of `need` bytes."""
+        ws = given if given is not None else workspace(need, self.bases.device)
+        assert ws.dtype == torch.uint8 and ws.is_contiguous() and ws.numel() >= need
+        return ws
+
+    def plan(self, num_cols: int, batch: int) -> "_lib.H2RMsmInfo":
+        """window_bits, num_windows, slice_points, num_slices and workspace_bytes of a call (h2r_msm_plan, a host function)."""
+        info, cfg = _lib.H2RMsmInfo(), self._config(num_cols)
+        if lib().h2r_msm_plan(ctypes.byref(cfg), batch, ctypes.byref(info)) == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_msm_plan")
+        return info
+
+    def commit(self, columns, out: Optional[torch.Tensor] = None, status: Optional[torch.Tensor] = None,
+               workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int64 [batch, num_cols, 2, 4]: the affine commitments sum_i columns[c][e][i] * bases[i] in the chip's representation, (0, 0) for the
+        identity.  columns: a list of tensors uint8 [batch, n, 32] (scalars in the chip's representation), or [n, 32] for a column the
+        whole batch shares (batch = 1 where every column is such a one).  out: the tensor to write into (it must overlap no input);
+        status: uint8 [batch], a byte that is nonzero on entry skips the circuit (its commitments are left as they were); workspace: uint8,
+        plan(num_cols, batch).workspace_bytes bytes, 16-byte aligned, the call's own until the stream has run it (allocated when None)."""
+        if not 0 < len(columns) <= _lib.H2R_MSM_MAX_COLUMNS:
+            check(_lib.H2R_E_SHAPE, "CommitKey.commit")
+        batch = next((int(t.shape[0]) for t in columns if t.dim() == 3), 1)
+        cfg = self._config(len(columns))
+        desc = (_lib.H2RMsmColumn * len(columns))()
+        for d, t in zip(desc, columns):
+            assert is_columns(t, rows=self.n, dims=(2, 3), batch=batch)
+            d.base, d.elem_stride, _ = column_group(t, t.dim() == 3)
+        out = outputs(out, self.bases.device, (torch.zeros, torch.int64, (batch, len(columns), 2, 4)))
+        assert out.is_contiguous() and out.dtype == torch.int64 and tuple(out.shape) == (batch, len(columns), 2, 4)
+        ws = self._workspace(workspace, int(lib().h2r_msm_workspace_bytes(ctypes.byref(cfg), batch)))
+        check(lib().h2r_msm_columns(self.chip._ctx, ctypes.byref(cfg), desc, self.bases.data_ptr(), batch, out.data_ptr(), ptr(status),
+                                    ws.data_ptr(), self.chip._stream()), "h2r_msm_columns")
+        hold(self, "commit", ws, list(columns), out, status)
+        return out
+
+    def transform(self, omega: int, k: Optional[int] = None, inverse: bool = True, out: Optional[torch.Tensor] = None,
+                  workspace: Optional[torch.Tensor] = None) -> "CommitKey":
+        """A new key over the transform of the first 2^k bases (h2r_curve_ntt): inverse (the default)
+        out[i] = [n^-1] sum_j [omega^(-i j)] bases[j] -- with the powers of tau as bases and the domain's omega, halo2's g_lagrange --,
+        forward out[i] = sum_j [omega^(i j)] bases[j].  omega: a primitive 2^k-th root of unity of the chip's field, an integer in the chip's
+        representation.  k: log2 n by default; a key whose n is no power of two needs an explicit k <= log2 n.  out: the tensor of 2^k
+        points to write into (the layout of `bases`; it must overlap neither the bases nor the workspace); workspace: uint8,
+        h2r_curve_ntt_workspace_bytes bytes, 16-byte aligned, the call's own until the stream has run it (allocated when None)."""
+        if k is None:
+            k = self.n.bit_length() - 1
+            if self.n != 1 << k:
+                check(_lib.H2R_E_SHAPE, "CommitKey.transform")
+        k = int(k)
+        if k < 1 or (1 << k) > self.n:
+            check(_lib.H2R_E_SHAPE, "CommitKey.transform")
+        cfg = _lib.H2RCurveNttConfig(struct_size=ctypes.sizeof(_lib.H2RCurveNttConfig), log_n=k, flags=_lib.H2R_CURVE_NTT_INVERSE if inverse else 0, reserved=0)
+        set_words(cfg.omega, omega)
+        n = 1 << k
+        out = outputs(out, self.bases.device, (torch.zeros, torch.int64, (n, 2, 4)) if self.bases.dtype == torch.int64 else (torch.zeros, torch.uint8, (n, 64)))
+        assert out.is_contiguous() and out.is_cuda and out.numel() * out.element_size() == 64 * n
+        ws = self._workspace(workspace, int(lib().h2r_curve_ntt_workspace_bytes(ctypes.byref(cfg))))
+        check(lib().h2r_curve_ntt(self.chip._ctx, ctypes.byref(cfg), self.bases.data_ptr(), out.data_ptr(), ws.data_ptr(), self.chip._stream()),
+              "h2r_curve_ntt")
+        key = CommitKey(self.chip, out)
+        hold(key, "transform", ws, self.bases, out)
+        return key

@@ -383,7 +383,7 @@ def test_capacity_is_refused(H, small):
     from halo2_rsa_amd._lib import lib
     c, usable, (thetas, betas, gammas), want = small
     la, chip = c.la, c.chip
-    th, be, ga = (la._challenges(v, 3, "cuda") for v in (thetas, betas, gammas))
+    th, be, ga = (H._marshal.challenges(v, "cuda", 3) for v in (thetas, betas, gammas))
     kd = torch.from_numpy(c.kinds).cuda()
     a = torch.zeros((3, 5, usable, 32), dtype=torch.uint8, device="cuda")
 

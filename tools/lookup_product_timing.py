@@ -62,7 +62,7 @@ def run(montgomery):
 
     # the C exports themselves on buffers built once: nothing of the host (challenge uploads, allocations) lies inside a timed window
     kd = torch.from_numpy(np.ascontiguousarray(kinds)).cuda()
-    th, be, ga = (la._challenges(v, B, "cuda") for v in ch)
+    th, be, ga = (H._marshal.challenges(v, "cuda", B) for v in ch)
     ws = torch.empty(int(lib().h2r_lookup_product_workspace_bytes(USABLE, B)), dtype=torch.uint8, device="cuda")
     col, stream = (USABLE + 1) * 32, chip._stream()
 

@@ -87,7 +87,7 @@ def run(montgomery):
     sigma = torch.from_numpy(np.stack([fe_bytes([x * scale % P for x in col]) for col in PR.labels(M, USABLE, delta, omega, P)])).cuda()
     extra = torch.zeros((1, 1, USABLE, 32), dtype=torch.uint8, device="cuda")          # one zero column, the same for every circuit (element stride 0)
     ch = [[rng.randrange(P) for _ in range(B)] for _ in range(3)]                      # (field elements in the ctx's representation, whichever it is)
-    th, be, ga = (la._challenges(v, B, "cuda") for v in ch)
+    th, be, ga = (H._marshal.challenges(v, "cuda", B) for v in ch)
     pz = torch.empty((B, SETS, USABLE + 1, 32), dtype=torch.uint8, device="cuda")
     pst = torch.zeros(B, dtype=torch.uint8, device="cuda")
     pws = torch.empty(int(lib().h2r_permutation_product_workspace_bytes(ctypes.byref(pa.cfg), USABLE, B)), dtype=torch.uint8, device="cuda")
