@@ -4025,11 +4025,10 @@ int32_t h2r_lookup_hist_advice(const h2r_ctx *ctx, const h2r_lookup_config *cfg,
 namespace {
 using namespace h2r_stage_args;
 bool ctx_mont(const h2r_ctx *ctx) { return (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) != 0; }
-Fe fe_load(const uint64_t w[4]) { Fe x; for (int k = 0; k < 4; ++k) x.v[k] = w[k]; return x; }
-Fe fe_one(const FieldConsts &f) { return fe_load(f.one); }
-Fe fe_r2(const FieldConsts &f) { return fe_load(f.r2); }
+Fe fe_one(const FieldConsts &f) { return fe_words(f.one); }
+Fe fe_r2(const FieldConsts &f) { return fe_words(f.r2); }
 // a configuration's constant, held in the ctx's representation, in Montgomery form
-Fe cfg_to_mont(const h2r_ctx *ctx, const uint64_t w[4]) { return ctx_mont(ctx) ? fe_load(w) : fe_to_mont(fe_load(w), ctx->fc); }
+Fe cfg_to_mont(const h2r_ctx *ctx, const uint64_t w[4]) { return ctx_mont(ctx) ? fe_words(w) : fe_to_mont(fe_words(w), ctx->fc); }
 Fe fe_pow2k(Fe x, u32 k, const FieldConsts &f) { while (k--) x = fe_mont_mul(x, x, f); return x; }   // x^(2^k)
 // a primitive 2^log_n-th root of unity: omega^(n / 2) = -1
 bool is_primitive_root(const Fe &omega, u32 log_n, const FieldConsts &f) { return fe_is_zero(fe_add(fe_pow2k(omega, log_n - 1, f), fe_one(f), f.p)); }
@@ -4040,13 +4039,14 @@ void fe_squaring_chain(Fe *out, u32 n, Fe base, const FieldConsts &f) {   // out
     for (u32 b = 0; b < n; ++b) { out[b] = base; base = fe_mont_mul(base, base, f); }
 }
 u8 *workspace_256(void *workspace) { return reinterpret_cast<u8 *>(round_up(reinterpret_cast<u64>(workspace), 256)); }
+// both grand products (h2r_grand_product.hpp): the kernels' row arithmetic is 32-bit; halo2 circuits end far below
+constexpr u32 kGrandProductMaxUsableRows = 1u << 28;
 }  // namespace
 
 // ---- the lookup argument's input columns A and grand-product columns Z (h2r_lookup_product.hpp, h2r_tu_lookup_product.hip) ------------
 namespace {
 // The table's rows all lie in the first tile of a column: the product kernels' table branch (and the timing tool's product counts) rest on it.
-static_assert(LOOKUP_MAX_ROWS <= (int)LOOKUP_PRODUCT_TILE, "the compressed table must fit one tile of the grand product");
-constexpr u32 kLookupMaxUsableRows = 1u << 28;   // (the kernels' row arithmetic is 32-bit; halo2 circuits end far below)
+static_assert(LOOKUP_MAX_ROWS <= (int)GRAND_PRODUCT_TILE, "the compressed table must fit one tile of the grand product");
 // a configuration as h2r_lookup_config_default / _custom build it: row 0 = (0, 0), then 2^bit_len rows per length, back to back
 bool lookup_cfg_valid(const h2r_lookup_config *cfg) {
     if (cfg->n_rows == 0 || cfg->n_rows > (u32)LOOKUP_MAX_ROWS || cfg->n_lens == 0 || cfg->n_lens > H2R_LOOKUP_MAX_LENS) return false;
@@ -4069,7 +4069,7 @@ int32_t h2r_lookup_input_columns(const h2r_ctx *ctx, const h2r_lookup_config *cf
     h2r_advice_layout ident;
     if (!layout) { h2r_advice_layout_default(&ident); layout = &ident; }
     else if (const int32_t rc = layout_lookup_valid(layout)) return rc;
-    if (!usable_rows || usable_rows > kLookupMaxUsableRows) return H2R_E_SHAPE;
+    if (!usable_rows || usable_rows > kGrandProductMaxUsableRows) return H2R_E_SHAPE;
     if ((u64)first_row + rows > usable_rows) return H2R_E_SHAPE;   // the image's rows occupy [first_row, first_row + rows) of the usable rows
     if (out_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 || misaligned(a_in_out, out_elem_stride)) return H2R_E_SHAPE;
     LookupInputArgs ia;
@@ -4111,7 +4111,7 @@ int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *
     if (!ctx || !cfg || !a_in || !a_perm || !s_perm || !theta || !beta || !gamma || !z_out || !workspace) return H2R_E_NULL;
     if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
     if (!lookup_cfg_valid(cfg)) return H2R_E_SHAPE;
-    if (!usable_rows || usable_rows > kLookupMaxUsableRows || in_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 ||
+    if (!usable_rows || usable_rows > kGrandProductMaxUsableRows || in_elem_stride < (u64)LOOKUP_ARGS * usable_rows * 32 ||
         misaligned(a_in, in_elem_stride) || misaligned(a_perm) || misaligned(s_perm)) return H2R_E_SHAPE;
     const u64 zcol = ((u64)usable_rows + 1) * 32;
     if (z_col_stride < zcol || (z_col_stride & 31) || misaligned(z_out, z_elem_stride)) return H2R_E_SHAPE;
@@ -4121,7 +4121,7 @@ int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *
     if (num_elems == 0 || !(arg_mask & 31u)) return H2R_OK;
     LookupProductArgs pa;
     std::memset(static_cast<void *>(&pa), 0, sizeof pa);
-    pa.in_elem_stride = in_elem_stride; pa.usable_rows = usable_rows; pa.n_tiles = lookup_product_tiles(usable_rows); pa.arg_mask = arg_mask & 31u;
+    pa.in_elem_stride = in_elem_stride; pa.usable_rows = usable_rows; pa.n_tiles = grand_product_tiles(usable_rows); pa.arg_mask = arg_mask & 31u;
     pa.mont = ctx_mont(ctx);
     pa.n_rows = cfg->n_rows; pa.n_lens = cfg->n_lens;
     for (u32 i = 0; i < cfg->n_lens; ++i) { pa.tag[i] = cfg->tag[i]; pa.row_off[i] = cfg->row_off[i]; }
@@ -4183,7 +4183,7 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
     if (cfg->n_extra && cfg->n_extra <= H2R_PERM_MAX_EXTRA && !extra) return H2R_E_NULL;
     if (!perm_cfg_valid(cfg)) return H2R_E_SHAPE;
     if (ge_p(cfg->delta, ctx->fc.p) || ge_p(cfg->omega, ctx->fc.p)) return H2R_E_SHAPE;
-    if (!usable_rows || usable_rows > kLookupMaxUsableRows) return H2R_E_SHAPE;
+    if (!usable_rows || usable_rows > kGrandProductMaxUsableRows) return H2R_E_SHAPE;
     if ((u64)first_row + rows > usable_rows) return H2R_E_SHAPE;   // the image's rows occupy [first_row, first_row + rows) of the usable rows
     if (misaligned(image, image_stride) || misaligned(sigma, sigma_col_stride) || misaligned(z_out, z_elem_stride, z_col_stride)) return H2R_E_SHAPE;
     if (cfg->n_extra && misaligned(extra, extra_elem_stride, extra_col_stride)) return H2R_E_SHAPE;
@@ -4200,7 +4200,7 @@ int32_t h2r_permutation_product_columns(const h2r_ctx *ctx, const h2r_permutatio
     if (batch == 0) return H2R_OK;
     const FieldConsts &f = ctx->fc;
     pa.mont = pa.img.mont;
-    pa.rows = rows; pa.first_row = first_row; pa.usable_rows = usable_rows; pa.n_tiles = perm_product_tiles(usable_rows);
+    pa.rows = rows; pa.first_row = first_row; pa.usable_rows = usable_rows; pa.n_tiles = grand_product_tiles(usable_rows);
     pa.m = cfg->num_columns; pa.chunk_len = std::min<u32>(cfg->chunk_len, cfg->num_columns); pa.n_sets = S;
     for (u32 c = 0; c < cfg->num_columns; ++c) pa.src[c] = cfg->column_src[c];
     // delta^c and omega^(2^b) in Montgomery form, whichever form the configuration holds them in
@@ -4674,7 +4674,7 @@ int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const
     const FieldConsts &f = cv->fq;
     bool ok = true;
     auto coord = [&](const uint64_t *w) {   // a canonical coordinate -> the Montgomery form
-        const Fe x = fe_load(w);
+        const Fe x = fe_words(w);
         if (ge_p(x.v, f.p)) { ok = false; return fe_zero(); }
         return fe_to_mont(x, f);
     };

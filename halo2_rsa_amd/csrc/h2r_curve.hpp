@@ -24,8 +24,13 @@ struct CurveConsts {
 struct PtProj { Fe x, y, z; };
 struct PtAff { Fe x, y; };
 
-H2R_FD Fe fe_load_one(const FieldConsts &f) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = f.one[k]; return r; }
+H2R_FD Fe fe_load_one(const FieldConsts &f) { return fe_words(f.one); }
 H2R_FD PtProj pt_identity(const CurveConsts &c) { PtProj r; r.x = fe_zero(); r.y = fe_load_one(c.fq); r.z = fe_zero(); return r; }
+#if defined(__HIPCC__)
+// device only: a projective point in memory is its three coordinates back to back (96 bytes on a 16-byte boundary)
+__device__ __forceinline__ PtProj pt_load(const uint8_t *p) { PtProj r; r.x = fe_load(p); r.y = fe_load(p + 32); r.z = fe_load(p + 64); return r; }
+__device__ __forceinline__ void pt_store(uint8_t *p, const PtProj &x) { fe_store(p, x.x); fe_store(p + 32, x.y); fe_store(p + 64, x.z); }
+#endif
 H2R_FD bool pt_aff_is_identity(const PtAff &p) { return fe_is_zero(p.x) && fe_is_zero(p.y); }
 // 3 b * t with additions
 H2R_FD Fe fe_mul_b3(const Fe &t, const CurveConsts &c) { return fe_mul_small(t, c.b3, c.fq.p); }

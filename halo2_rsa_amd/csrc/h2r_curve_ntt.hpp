@@ -130,19 +130,6 @@ H2R_FD PtProj pt_mul_window2(const PtProj &p, const u64 (&k)[4], const CurveCons
 
 #ifdef H2R_TU_CURVE_NTT
 
-__device__ __forceinline__ Fe cntt_load_fe(const u8 *p) {
-    const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(p);
-    const ulonglong2 lo = q[0], hi = q[1];
-    Fe r; r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = hi.x; r.v[3] = hi.y;
-    return r;
-}
-__device__ __forceinline__ void cntt_store_fe(u8 *p, const Fe &x) {
-    *reinterpret_cast<ulonglong2 *>(p) = make_ulonglong2(x.v[0], x.v[1]);
-    *reinterpret_cast<ulonglong2 *>(p + 16) = make_ulonglong2(x.v[2], x.v[3]);
-}
-__device__ __forceinline__ PtProj cntt_load_pt(const u8 *p) { PtProj r; r.x = cntt_load_fe(p); r.y = cntt_load_fe(p + 32); r.z = cntt_load_fe(p + 64); return r; }
-__device__ __forceinline__ void cntt_store_pt(u8 *p, const PtProj &x) { cntt_store_fe(p, x.x); cntt_store_fe(p + 32, x.y); cntt_store_fe(p + 64, x.z); }
-
 // grid (blocks of 256 over n / 2 twiddles): tw[t] = w^t, the product of the squaring chain's entries at t's bits, as a canonical integer
 __global__ __launch_bounds__(256) void curve_ntt_twiddle_kernel(CurveNttArgs a) {
     const u64 t = ((u64)a.block0 + blockIdx.x) * 256 + threadIdx.x;
@@ -152,7 +139,7 @@ __global__ __launch_bounds__(256) void curve_ntt_twiddle_kernel(CurveNttArgs a) 
     for (u32 b = 0; b < CNTT_MAX_LOG - 1; ++b)
         if ((t >> b) & 1u) acc = fe_mont_mul(acc, a.wpow[b], a.fr);
     acc = fe_from_mont(acc, a.fr);
-    cntt_store_fe(reinterpret_cast<u8 *>(a.tw + 4 * t), acc);
+    fe_store(reinterpret_cast<u8 *>(a.tw + 4 * t), acc);
 }
 
 // grid (blocks of 256 over n points)
@@ -160,14 +147,14 @@ __global__ __launch_bounds__(256) void curve_ntt_load_kernel(CurveNttArgs a) {
     const u64 j = ((u64)a.block0 + blockIdx.x) * 256 + threadIdx.x;
     if (j >= (1ull << a.log_n)) return;
     PtProj p;
-    p.x = cntt_load_fe(a.in + j * 64); p.y = cntt_load_fe(a.in + j * 64 + 32);
+    p.x = fe_load(a.in + j * 64); p.y = fe_load(a.in + j * 64 + 32);
     if (fe_is_zero(p.x) && fe_is_zero(p.y)) p = pt_identity(a.cv);
     else {
         if (!a.mont) { p.x = fe_to_mont(p.x, a.cv.fq); p.y = fe_to_mont(p.y, a.cv.fq); }
         p.z = fe_load_one(a.cv.fq);
     }
     const u64 r = (u64)(__brev((u32)j) >> (32 - a.log_n));
-    cntt_store_pt(a.pts + r * CNTT_POINT_BYTES, p);
+    pt_store(a.pts + r * CNTT_POINT_BYTES, p);
 }
 
 // grid (blocks of 256 over n / 2 butterflies), stage a.stage = 1 .. log_n
@@ -181,11 +168,11 @@ __global__ __launch_bounds__(256) void curve_ntt_stage_kernel(CurveNttArgs a) {
     if (twiddle_major) { k = t >> log_groups; g = t & ((1ull << log_groups) - 1); }
     else { k = t & (half - 1); g = t >> (s - 1); }
     u8 *lo = a.pts + ((g << s) + k) * CNTT_POINT_BYTES, *hi = lo + half * CNTT_POINT_BYTES;
-    PtProj v = cntt_load_pt(hi);
+    PtProj v = pt_load(hi);
 #ifdef H2R_DEV_KNOBS
     if (a.form == CNTT_FORM_PER_LANE) {
         if (k) {
-            const Fe w = cntt_load_fe(reinterpret_cast<const u8 *>(a.tw + 4 * (k << log_groups)));
+            const Fe w = fe_load(reinterpret_cast<const u8 *>(a.tw + 4 * (k << log_groups)));
             v = pt_mul_binary(v, w.v, a.cv);
         }
     } else
@@ -199,23 +186,23 @@ __global__ __launch_bounds__(256) void curve_ntt_stage_kernel(CurveNttArgs a) {
             v = pt_mul_uniform(v, kk, a.cv);
         }
     } else if (k) {
-        const Fe w = cntt_load_fe(reinterpret_cast<const u8 *>(a.tw + 4 * (k << log_groups)));
+        const Fe w = fe_load(reinterpret_cast<const u8 *>(a.tw + 4 * (k << log_groups)));
         v = pt_mul_window2(v, w.v, a.cv);
     }
-    const PtProj u = cntt_load_pt(lo);
-    cntt_store_pt(lo, pt_add(u, v, a.cv));
-    cntt_store_pt(hi, pt_add(u, pt_neg(v, a.cv), a.cv));
+    const PtProj u = pt_load(lo);
+    pt_store(lo, pt_add(u, v, a.cv));
+    pt_store(hi, pt_add(u, pt_neg(v, a.cv), a.cv));
 }
 
 // grid (blocks of 256 over n points)
 __global__ __launch_bounds__(256) void curve_ntt_store_kernel(CurveNttArgs a) {
     const u64 i = ((u64)a.block0 + blockIdx.x) * 256 + threadIdx.x;
     if (i >= (1ull << a.log_n)) return;
-    PtProj p = cntt_load_pt(a.pts + i * CNTT_POINT_BYTES);
+    PtProj p = pt_load(a.pts + i * CNTT_POINT_BYTES);
     if (a.inverse) p = pt_mul_uniform(p, a.ninv, a.cv);    // (n^-1 is the same for every lane of the call)
     PtAff r = pt_to_affine(p, a.cv);
     if (!a.mont) { r.x = fe_from_mont(r.x, a.cv.fq); r.y = fe_from_mont(r.y, a.cv.fq); }
-    cntt_store_fe(a.out + i * 64, r.x); cntt_store_fe(a.out + i * 64 + 32, r.y);
+    fe_store(a.out + i * 64, r.x); fe_store(a.out + i * 64 + 32, r.y);
 }
 
 #endif  // H2R_TU_CURVE_NTT

@@ -37,6 +37,7 @@ H2R_FD bool ge_p(const uint64_t (&x)[4], const uint64_t (&p)[4]) {
 }
 H2R_FD Fe fe_zero() { Fe r; r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0; return r; }
 H2R_FD Fe fe_small(uint64_t x) { Fe r; r.v[0] = x; r.v[1] = r.v[2] = r.v[3] = 0; return r; }
+H2R_FD Fe fe_words(const uint64_t *w) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = w[k]; return r; }
 
 // a + b mod p (a, b < p < 2^255: no carry out of 256 bits)
 H2R_FD Fe fe_add(const Fe &a, const Fe &b, const uint64_t (&p)[4]) {
@@ -125,6 +126,29 @@ H2R_FD Fe fe_to_mont(const Fe &a, const FieldConsts &f) { Fe r2; for (int k = 0;
 H2R_FD Fe fe_from_mont(const Fe &a, const FieldConsts &f) { return fe_mont_mul(a, fe_small(1), f); }
 // canonical a * b mod p
 H2R_FD Fe fe_mul(const Fe &a, const Fe &b, const FieldConsts &f) { return fe_mont_mul(fe_to_mont(a, f), b, f); }
+
+#if defined(__HIPCC__)
+// Device only, for every prover stage: an element in memory is 32 bytes on a 16-byte boundary and moves as two 16-byte accesses (plain
+// ones: a stage that wants non-temporal stores spells st16 out), and the lanes of a wave exchange one word by word.
+__device__ __forceinline__ Fe fe_load(const uint8_t *p) {
+    const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(p)[0], hi = reinterpret_cast<const ulonglong2 *>(p)[1];
+    Fe r; r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = hi.x; r.v[3] = hi.y;
+    return r;
+}
+__device__ __forceinline__ void fe_store(uint8_t *p, const Fe &x) {
+    reinterpret_cast<ulonglong2 *>(p)[0] = make_ulonglong2(x.v[0], x.v[1]);
+    reinterpret_cast<ulonglong2 *>(p)[1] = make_ulonglong2(x.v[2], x.v[3]);
+}
+// an element held in the ctx's representation (mont: already x * R), in Montgomery form.  A site that needs several elements at once
+// keeps fe_load and converts them under ONE branch: a branch per element would put each load behind the previous conversion.
+__device__ __forceinline__ Fe fe_load_mont(const uint8_t *p, uint32_t mont, const FieldConsts &f) {
+    const Fe r = fe_load(p);
+    return mont ? r : fe_to_mont(r, f);
+}
+__device__ __forceinline__ Fe fe_shfl(const Fe &x, int src) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = __shfl(x.v[k], src); return r; }
+__device__ __forceinline__ Fe fe_shfl_up(const Fe &x, uint32_t d) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = __shfl_up(x.v[k], d); return r; }
+__device__ __forceinline__ Fe fe_shfl_down(const Fe &x, uint32_t d) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = __shfl_down(x.v[k], d); return r; }
+#endif
 // a^(p-2) by square-and-multiply: ~380 Montgomery products (kept as the cross-check of fe_inv: h2r_field_eval op 4)
 H2R_FD Fe fe_inv_fermat(const Fe &a, const FieldConsts &f) {
     uint64_t e[4] = {f.p[0] - 2, f.p[1], f.p[2], f.p[3]};   // p is odd and > 2: no borrow

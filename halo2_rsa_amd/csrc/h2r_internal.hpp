@@ -7,8 +7,8 @@
 //   h2r_tu_step.hip    step_kernel<K, NW, LW, L>   (records of call k + chains of call k+1 in one launch)
 //   h2r_tu_chain_keyed.hip, h2r_tu_step_keyed.hip   the same two families' builds for keyed calls (H2R_F_KEYED_MODULI)
 //   h2r_tu_cells.hip   cells_kernel<LW, ABL, MONT, NWV> (the advice image directly from the operands)
-//   h2r_tu_lookup_product.hip   the lookup argument's input columns and grand product (h2r_lookup_product.hpp)
-//   h2r_tu_permutation_product.hip   the permutation argument's grand product (h2r_permutation_product.hpp)
+//   h2r_tu_lookup_product.hip   the lookup argument's input columns and grand product (h2r_lookup_product.hpp over h2r_grand_product.hpp)
+//   h2r_tu_permutation_product.hip   the permutation argument's grand product (h2r_permutation_product.hpp over h2r_grand_product.hpp)
 //   h2r_tu_ntt.hip     the evaluation domain's transforms (h2r_ntt.hpp)
 //   h2r_tu_quotient.hip   the vanishing argument's quotient on the extended domain (h2r_quotient.hpp)
 //   h2r_tu_open.hip    the openings: evaluations at x, GWC witness polynomials, the fold of h's pieces (h2r_open.hpp)
@@ -112,12 +112,14 @@ hipError_t launch_step_shape_keyed(const StepShape &s, u32 num_cus, const ChainA
 u32 step_shared_bytes_shape(const StepShape &s);
 // h2r_tu_cells.hip.  `lds` = the dynamic LDS request (residency rule applied by the caller); nwv = waves per workgroup (Montgomery, long shapes).
 hipError_t launch_cells_shape(u32 w, bool mont, u32 nwv, u32 lds, const CellsArgs &ca, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
-// h2r_tu_lookup_product.hip (argument structs: h2r_lookup_product.hpp).  phase 0 = the tiles' products, 1 = the carry-ins per column, 2 = the scans that write Z.
+// h2r_tu_lookup_product.hip (argument structs: h2r_lookup_product.hpp).  The grand product's three phases (h2r_grand_product.hpp): 0 = the tiles'
+// products, 1 = the carry-ins per column, 2 = the scans that write Z.
 struct LookupInputArgs;
 struct LookupProductArgs;
 hipError_t launch_lookup_input(const LookupInputArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 hipError_t launch_lookup_product(u32 phase, const LookupProductArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
-// h2r_tu_permutation_product.hip (argument struct: h2r_permutation_product.hpp).  The same three phases: per tile of a set, per element, per tile of a set.
+// h2r_tu_permutation_product.hip (argument struct: h2r_permutation_product.hpp).  The same three phases of the same core: per tile of a set, per
+// element (one wave walks its sets), per tile of a set.
 struct PermProductArgs;
 hipError_t launch_perm_product(u32 phase, const PermProductArgs &a, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 // h2r_tu_ntt.hip (argument structs: h2r_ntt.hpp).  The twiddle tables of one call, then one pass (a.pass) over num_cols x num_elems columns.

@@ -60,31 +60,19 @@ __host__ __device__ inline u64 msm_workspace_bytes(u32 n, u32 num_cols, u64 batc
 
 #ifdef H2R_TU_MSM
 
-__device__ __forceinline__ Fe msm_load_fe(const u8 *p) {
-    const ulonglong2 *q = reinterpret_cast<const ulonglong2 *>(p);
-    const ulonglong2 lo = q[0], hi = q[1];
-    Fe r; r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = hi.x; r.v[3] = hi.y;
-    return r;
-}
-__device__ __forceinline__ PtProj msm_load_pt(const u8 *p) { PtProj r; r.x = msm_load_fe(p); r.y = msm_load_fe(p + 32); r.z = msm_load_fe(p + 64); return r; }
-__device__ __forceinline__ void msm_store_fe(u8 *p, const Fe &x) {
-    *reinterpret_cast<ulonglong2 *>(p) = make_ulonglong2(x.v[0], x.v[1]);
-    *reinterpret_cast<ulonglong2 *>(p + 16) = make_ulonglong2(x.v[2], x.v[3]);
-}
-__device__ __forceinline__ void msm_store_pt(u8 *p, const PtProj &x) { msm_store_fe(p, x.x); msm_store_fe(p + 32, x.y); msm_store_fe(p + 64, x.z); }
 __device__ __forceinline__ u8 *msm_partial(const MsmArgs &a, u64 elem, u32 col, u32 window, u32 slice) {
     return a.ws + (((elem * a.num_cols + col) * MSM_WINDOWS + window) * a.num_slices + slice) * MSM_PARTIAL_BYTES;
 }
 // the digit of scalar j of the slice in `window`: a byte of the integer the 32 bytes mean
 __device__ __forceinline__ u32 msm_digit(const MsmArgs &a, const u8 *scal, u32 j, u32 window) {
     if (!a.mont) return scal[(u64)j * 32 + window];
-    const Fe s = fe_from_mont(msm_load_fe(scal + (u64)j * 32), a.fr);
+    const Fe s = fe_from_mont(fe_load(scal + (u64)j * 32), a.fr);
     const u32 k = window >> 3;
     const u64 w = k == 0 ? s.v[0] : k == 1 ? s.v[1] : k == 2 ? s.v[2] : s.v[3];
     return (u32)(w >> ((window & 7u) * 8)) & 0xffu;
 }
 __device__ __forceinline__ PtAff msm_load_base(const MsmArgs &a, u64 i) {
-    PtAff b; b.x = msm_load_fe(a.bases + i * 64); b.y = msm_load_fe(a.bases + i * 64 + 32);
+    PtAff b; b.x = fe_load(a.bases + i * 64); b.y = fe_load(a.bases + i * 64 + 32);
     if (!a.mont) { b.x = fe_to_mont(b.x, a.cv.fq); b.y = fe_to_mont(b.y, a.cv.fq); }   // ((0, 0) stays (0, 0))
     return b;
 }
@@ -110,7 +98,7 @@ __global__ __launch_bounds__(256) void msm_bucket_kernel(MsmArgs a) {
     const PtProj ident = pt_identity(a.cv);
 
     hist[tid] = 0;
-    msm_store_pt(bucket + tid * MSM_PARTIAL_BYTES, ident);
+    pt_store(bucket + tid * MSM_PARTIAL_BYTES, ident);
     __syncthreads();
     for (u32 j = tid; j < cnt; j += 256) {
         const u32 d = msm_digit(a, scal, j, window);
@@ -146,7 +134,7 @@ __global__ __launch_bounds__(256) void msm_bucket_kernel(MsmArgs a) {
         if (d != cur) {
             if (cur) {
                 if (!head_key) { head = acc; head_key = cur; }                 // the run's first group: it may continue in the lane before
-                else msm_store_pt(bucket + cur * MSM_PARTIAL_BYTES, acc);     // a group that lies whole inside this lane
+                else pt_store(bucket + cur * MSM_PARTIAL_BYTES, acc);     // a group that lies whole inside this lane
             }
             cur = d; acc = ident;
         }
@@ -155,8 +143,8 @@ __global__ __launch_bounds__(256) void msm_bucket_kernel(MsmArgs a) {
     __syncthreads();                                      // the sort's arrays are dead from here on
     {   // entries 2 tid and 2 tid + 1 of the list: (first group, last group); a run of one group adds (its digit, identity)
         u8 *e0 = pool + (2 * tid) * MSM_PARTIAL_BYTES, *e1 = e0 + MSM_PARTIAL_BYTES;
-        if (!head_key) { msm_store_pt(e0, acc); msm_store_pt(e1, ident); pkey[2 * tid] = cur; pkey[2 * tid + 1] = cur; }   // (cur = 0: an empty run)
-        else { msm_store_pt(e0, head); msm_store_pt(e1, acc); pkey[2 * tid] = head_key; pkey[2 * tid + 1] = cur; }
+        if (!head_key) { pt_store(e0, acc); pt_store(e1, ident); pkey[2 * tid] = cur; pkey[2 * tid + 1] = cur; }   // (cur = 0: an empty run)
+        else { pt_store(e0, head); pt_store(e1, acc); pkey[2 * tid] = head_key; pkey[2 * tid + 1] = cur; }
     }
     __syncthreads();
     // segmented inclusive scan keyed by digit; the upper half of a stride first: its reads of the lower half see the stride's old values
@@ -166,29 +154,29 @@ __global__ __launch_bounds__(256) void msm_bucket_kernel(MsmArgs a) {
         const u32 key = pkey[i];
         const bool need = i >= s && key != 0 && pkey[i - s] == key;
         PtProj left = ident;
-        if (need) left = msm_load_pt(pool + (i - s) * MSM_PARTIAL_BYTES);
+        if (need) left = pt_load(pool + (i - s) * MSM_PARTIAL_BYTES);
         __syncthreads();
-        if (need) msm_store_pt(pool + i * MSM_PARTIAL_BYTES, pt_add(msm_load_pt(pool + i * MSM_PARTIAL_BYTES), left, a.cv));
+        if (need) pt_store(pool + i * MSM_PARTIAL_BYTES, pt_add(pt_load(pool + i * MSM_PARTIAL_BYTES), left, a.cv));
         __syncthreads();
     }
     for (u32 h = 0; h < 2; ++h) {   // a group's last entry holds its sum
         const u32 i = tid + 256 * h, key = pkey[i];
-        if (key && (i == 511 || pkey[i + 1] != key)) msm_store_pt(bucket + key * MSM_PARTIAL_BYTES, msm_load_pt(pool + i * MSM_PARTIAL_BYTES));
+        if (key && (i == 511 || pkey[i + 1] != key)) pt_store(bucket + key * MSM_PARTIAL_BYTES, pt_load(pool + i * MSM_PARTIAL_BYTES));
     }
     __syncthreads();
     // lane b: b * B_b, then the workgroup's sum
-    acc = pt_mul_digit(msm_load_pt(bucket + tid * MSM_PARTIAL_BYTES), tid, a.cv);
-    msm_store_pt(bucket + tid * MSM_PARTIAL_BYTES, acc);
+    acc = pt_mul_digit(pt_load(bucket + tid * MSM_PARTIAL_BYTES), tid, a.cv);
+    pt_store(bucket + tid * MSM_PARTIAL_BYTES, acc);
     __syncthreads();
 #pragma unroll 1
     for (u32 s = 128; s >= 1; s >>= 1) {
         if (tid < s) {
-            acc = pt_add(acc, msm_load_pt(bucket + (tid + s) * MSM_PARTIAL_BYTES), a.cv);
-            msm_store_pt(bucket + tid * MSM_PARTIAL_BYTES, acc);
+            acc = pt_add(acc, pt_load(bucket + (tid + s) * MSM_PARTIAL_BYTES), a.cv);
+            pt_store(bucket + tid * MSM_PARTIAL_BYTES, acc);
         }
         __syncthreads();
     }
-    if (tid == 0) msm_store_pt(msm_partial(a, elem, col, window, slice), acc);
+    if (tid == 0) pt_store(msm_partial(a, elem, col, window, slice), acc);
 }
 
 // grid (num_cols, circuits of one launch)
@@ -200,25 +188,25 @@ __global__ __launch_bounds__(256) void msm_fold_kernel(MsmArgs a) {
     if (a.status && a.status[elem]) return;               // skipped: no workspace result is consumed
     PtProj acc = pt_identity(a.cv);
 #pragma unroll 1
-    for (u32 s = g; s < a.num_slices; s += MSM_FOLD_GROUPS) acc = pt_add(acc, msm_load_pt(msm_partial(a, elem, col, window, s)), a.cv);
-    msm_store_pt(sh + tid * MSM_PARTIAL_BYTES, acc);
+    for (u32 s = g; s < a.num_slices; s += MSM_FOLD_GROUPS) acc = pt_add(acc, pt_load(msm_partial(a, elem, col, window, s)), a.cv);
+    pt_store(sh + tid * MSM_PARTIAL_BYTES, acc);
     __syncthreads();
 #pragma unroll 1
     for (u32 s = MSM_FOLD_GROUPS / 2; s >= 1; s >>= 1) {
         if (g < s) {
-            acc = pt_add(acc, msm_load_pt(sh + (tid + s * MSM_WINDOWS) * MSM_PARTIAL_BYTES), a.cv);
-            msm_store_pt(sh + tid * MSM_PARTIAL_BYTES, acc);
+            acc = pt_add(acc, pt_load(sh + (tid + s * MSM_WINDOWS) * MSM_PARTIAL_BYTES), a.cv);
+            pt_store(sh + tid * MSM_PARTIAL_BYTES, acc);
         }
         __syncthreads();
     }
     if (tid != 0) return;
-    acc = msm_load_pt(sh + (MSM_WINDOWS - 1) * MSM_PARTIAL_BYTES);
+    acc = pt_load(sh + (MSM_WINDOWS - 1) * MSM_PARTIAL_BYTES);
 #pragma unroll 1
-    for (u32 w = MSM_WINDOWS - 1; w > 0; --w) acc = pt_add(pt_shift_window(acc, a.cv), msm_load_pt(sh + (w - 1) * MSM_PARTIAL_BYTES), a.cv);
+    for (u32 w = MSM_WINDOWS - 1; w > 0; --w) acc = pt_add(pt_shift_window(acc, a.cv), pt_load(sh + (w - 1) * MSM_PARTIAL_BYTES), a.cv);
     PtAff r = pt_to_affine(acc, a.cv);
     if (!a.mont) { r.x = fe_from_mont(r.x, a.cv.fq); r.y = fe_from_mont(r.y, a.cv.fq); }
     u8 *o = reinterpret_cast<u8 *>(a.out) + (elem * a.num_cols + col) * 64;
-    msm_store_fe(o, r.x); msm_store_fe(o + 32, r.y);
+    fe_store(o, r.x); fe_store(o + 32, r.y);
 }
 
 #endif  // H2R_TU_MSM

@@ -83,11 +83,6 @@ struct NttArgs {
 
 #ifdef H2R_TU_NTT
 
-__device__ __forceinline__ Fe ntt_load(const u8 *p) {
-    const ulonglong2 lo = reinterpret_cast<const ulonglong2 *>(p)[0], hi = reinterpret_cast<const ulonglong2 *>(p)[1];
-    Fe r; r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = hi.x; r.v[3] = hi.y;
-    return r;
-}
 // base^E of a two-level table pair, E < 2^24; `wide`: exponents reach beyond the low table (uniform per launch)
 __device__ __forceinline__ Fe ntt_pow(const Fe *lo, const Fe *hi, u32 e, bool wide, const FieldConsts &f) {
     const Fe l = lo[e & (NTT_SPLIT - 1)];
@@ -132,12 +127,12 @@ __global__ __launch_bounds__(256) void ntt_pass_kernel(NttArgs a) {
         if (first) {
             const u32 i = line + d * lines;
             if (i < (1u << a.log_m)) {
-                v = ntt_load(src + (u64)i * 32);
+                v = fe_load(src + (u64)i * 32);
                 if (a.load_mode == NTT_F_CONST) v = fe_mont_mul(v, a.load_const, a.f);
                 else if (a.load_mode == NTT_F_TABLE) v = fe_mont_mul(v, ntt_pow(glo, ghi, i, a.log_m > NTT_SPLIT_LOG, a.f), a.f);
             }
         } else {
-            v = ntt_load(src + (u64)place(line, d) * 32);
+            v = fe_load(src + (u64)place(line, d) * 32);
             const u32 e = (d * (line & ((1u << lb) - 1))) << (a.log_n - lb - s);   // omega_(n_q)^(d * J) as a power of omega
             v = fe_mont_mul(v, ntt_pow(wlo, whi, e, a.log_n > NTT_SPLIT_LOG, a.f), a.f);
         }

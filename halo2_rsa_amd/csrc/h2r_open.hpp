@@ -8,7 +8,8 @@
 //   witness   g_p = sum_{c in Q_p} v^idx(c) f_c  (Q_p: the columns with bit p, in column order; idx: the position within Q_p, from 0),
 //             W_p[i - 1] = g_p[i] + z_p W_p[i] for i = n_coeffs - 1 .. 1, W_p[n_coeffs - 1] = 0, batch_evals[e][p] = g_p[0] + z_p W_p[0]
 // Synthetic division is a suffix scan of the affine maps t -> g[i] + z t, and the evaluation is the value that falls out of its low end, so
-// both calls have the shape of the grand products (h2r_permutation_product.hpp): three launches, and NO workgroup ever waits for another one.
+// both calls have the shape of the grand products (h2r_grand_product.hpp): three launches, and NO workgroup ever waits for another one.
+// (The scan here composes affine maps, not factors, so only the Fe helpers of h2r_field.hpp are shared with them.)
 // With OPEN_TILE = 1,024 coefficients per tile, Z = z^1024, T_t = sum_{i in tile t} f[i] z^(i - 1024 t):
 //   open_tiles_kernel   per (circuit, tile): a thread takes four consecutive coefficients (adjacent lanes load adjacent 128 bytes); per
 //                       column and per masked point the lane's 4-term Horner, the wave with __shfl_down and z^4, z^8 .. z^128, the four
@@ -77,25 +78,17 @@ __host__ __device__ inline u64 open_slot_bytes(u32 n_coeffs, u32 slots) { return
 
 #ifdef H2R_TU_OPEN
 
-__device__ __forceinline__ Fe open_words(const u64 *w) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = w[k]; return r; }
-__device__ __forceinline__ Fe open_load(const u8 *col, u32 i) {
-    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(col + (u64)i * 32);
-    const ulonglong2 lo = p[0], hi = p[1];
-    Fe r; r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = hi.x; r.v[3] = hi.y;
-    return r;
-}
-__device__ __forceinline__ Fe open_shfl_down(const Fe &x, u32 d) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = __shfl_down(x.v[k], d); return r; }
 __device__ __forceinline__ u8 *open_slot(const OpenArgs &a, u64 elem) { return a.ws + elem * a.slot_bytes; }
 __device__ __forceinline__ Fe *open_slot_tiles(u8 *slot, const OpenArgs &a, u32 s) { return reinterpret_cast<Fe *>(slot + OPEN_HDR_BYTES) + (u64)s * a.n_tiles; }
 // every point of the circuit, and v for the witness, is a canonical element
 __device__ __forceinline__ bool open_scalars_ok(const OpenArgs &a, u64 elem) {
     bool ok = true;
     for (u32 p = 0; p < a.num_points; ++p) {
-        const Fe z = open_words(a.points + (elem * a.num_points + p) * 4);
+        const Fe z = fe_words(a.points + (elem * a.num_points + p) * 4);
         if (ge_p(z.v, a.f.p)) ok = false;
     }
     if (a.witness) {
-        const Fe v = open_words(a.v + elem * 4);
+        const Fe v = fe_words(a.v + elem * 4);
         if (ge_p(v.v, a.f.p)) ok = false;
     }
     return ok;
@@ -103,12 +96,12 @@ __device__ __forceinline__ bool open_scalars_ok(const OpenArgs &a, u64 elem) {
 // what a workgroup of the tiles / scan kernels starts with: z_p^(2^b) of every point and v, Montgomery form.  The caller synchronises.
 __device__ __forceinline__ void open_prologue(const OpenArgs &a, u64 elem, u32 tid, Fe (*zp)[OPEN_POW_BITS], Fe *vm) {
     if (tid < a.num_points) {
-        Fe z = open_words(a.points + (elem * a.num_points + tid) * 4);
+        Fe z = fe_words(a.points + (elem * a.num_points + tid) * 4);
         if (!a.mont) z = fe_to_mont(z, a.f);
         for (u32 b = 0; b < OPEN_POW_BITS; ++b) { zp[tid][b] = z; z = fe_mont_mul(z, z, a.f); }
     }
     if (tid == 64 && a.witness) {
-        const Fe v = open_words(a.v + elem * 4);
+        const Fe v = fe_words(a.v + elem * 4);
         *vm = a.mont ? v : fe_to_mont(v, a.f);
     }
 }
@@ -117,10 +110,7 @@ __device__ __forceinline__ void open_coeffs(const OpenArgs &a, const u8 *col, u3
 #pragma unroll
     for (u32 j = 0; j < OPEN_LANE_COEFFS; ++j) {
         f[j] = fe_zero();
-        if (i0 + j < a.n_coeffs) {
-            f[j] = open_load(col, i0 + j);
-            if (!a.mont) f[j] = fe_to_mont(f[j], a.f);
-        }
+        if (i0 + j < a.n_coeffs) f[j] = fe_load_mont(col + (u64)(i0 + j) * 32, a.mont, a.f);
     }
 }
 // g_p's four coefficients, Montgomery form: a Horner in v over the point's columns from the last one down
@@ -136,7 +126,7 @@ __device__ __forceinline__ void open_form_g(const OpenArgs &a, u64 elem, u32 p, 
 #pragma unroll
         for (u32 j = 0; j < OPEN_LANE_COEFFS; ++j) {
             if (!first) g[j] = fe_mont_mul(g[j], vm, a.f);
-            if (i0 + j < a.n_coeffs) g[j] = fe_add(g[j], open_load(col, i0 + j), a.f.p);
+            if (i0 + j < a.n_coeffs) g[j] = fe_add(g[j], fe_load(col + (u64)(i0 + j) * 32), a.f.p);
         }
         first = false;
     }
@@ -153,7 +143,7 @@ __device__ __forceinline__ Fe open_horner4(const Fe (&f)[4], const Fe &z, const 
 }
 // lane 0: sum_l x_l z^(4 l) over the wave (zp = z^(2^b) of the point); the other lanes hold partial sums that nobody reads
 __device__ __forceinline__ Fe open_wave_sum(Fe x, const Fe *zp, const FieldConsts &fc) {
-    for (u32 s = 0; s < 6; ++s) x = fe_add(x, fe_mont_mul(open_shfl_down(x, 1u << s), zp[2 + s], fc), fc.p);
+    for (u32 s = 0; s < 6; ++s) x = fe_add(x, fe_mont_mul(fe_shfl_down(x, 1u << s), zp[2 + s], fc), fc.p);
     return x;
 }
 // the four waves' sums -> the tile's
@@ -226,7 +216,7 @@ __global__ __launch_bounds__(64) void open_carry_kernel(OpenArgs a) {
     if (lane == 0 && s == 0) hdr[1] = 1;
     const u32 p = a.witness ? s : a.qpoint[s];
     if (a.witness && !a.point_cols[p]) return;
-    Fe Z = open_words(a.points + (elem * a.num_points + p) * 4);
+    Fe Z = fe_words(a.points + (elem * a.num_points + p) * 4);
     if (!a.mont) Z = fe_to_mont(Z, a.f);
     for (u32 b = 0; b < OPEN_TILE_LOG; ++b) Z = fe_mont_mul(Z, Z, a.f);   // z^1024
     const u32 T = a.n_tiles, per = (T + 63) / 64;
@@ -234,19 +224,19 @@ __global__ __launch_bounds__(64) void open_carry_kernel(OpenArgs a) {
     Fe *tp = open_slot_tiles(slot, a, s);
     Fe run = fe_zero();                        // sum_{t in the run} T_t Z^(t - lo)
     for (u32 t = hi; t > lo; --t) run = fe_add(fe_mont_mul(run, Z, a.f), tp[t - 1], a.f.p);
-    Fe pw = open_words(a.f.one);               // Z^per: every run before the last nonempty one has `per` tiles
+    Fe pw = fe_words(a.f.one);               // Z^per: every run before the last nonempty one has `per` tiles
     for (u32 b = 32 - (u32)__clz(per); b > 0; --b) {
         pw = fe_mont_mul(pw, pw, a.f);
         if ((per >> (b - 1)) & 1u) pw = fe_mont_mul(pw, Z, a.f);
     }
     Fe inc = run;                              // suffix scan: inc_l = sum_{m >= l} run_m (Z^per)^(m - l)
     for (u32 d = 1; d < 64; d <<= 1) {
-        const Fe m = fe_add(inc, fe_mont_mul(open_shfl_down(inc, d), pw, a.f), a.f.p);
+        const Fe m = fe_add(inc, fe_mont_mul(fe_shfl_down(inc, d), pw, a.f), a.f.p);
         if (lane + d < 64) inc = m;
         pw = fe_mont_mul(pw, pw, a.f);
     }
     if (a.witness) {
-        Fe k = open_shfl_down(inc, 1);         // K of the run's top tile: what lies above the run
+        Fe k = fe_shfl_down(inc, 1);         // K of the run's top tile: what lies above the run
         if (lane == 63) k = fe_zero();
         for (u32 t = hi; t > lo; --t) { const Fe x = tp[t - 1]; tp[t - 1] = k; k = fe_add(fe_mont_mul(k, Z, a.f), x, a.f.p); }
     }
@@ -276,14 +266,14 @@ __global__ __launch_bounds__(256) void open_scan_kernel(OpenArgs a) {
     // across the wave: inc_l = sum_{m >= l} (the lane's 4-term Horner)_m z^(4 (m - l)); across the waves through LDS
     Fe inc = open_horner4(g, z[0], a.f);
     for (u32 s = 0; s < 6; ++s) {
-        const Fe m = fe_add(inc, fe_mont_mul(open_shfl_down(inc, 1u << s), z[2 + s], a.f), a.f.p);
+        const Fe m = fe_add(inc, fe_mont_mul(fe_shfl_down(inc, 1u << s), z[2 + s], a.f), a.f.p);
         if (lane + (1u << s) < 64) inc = m;
     }
     if (lane == 0) wt[wave] = inc;
     __syncthreads();
     Fe cw = open_slot_tiles(slot, a, p)[tile];   // K_t, then what lies above this wave: W[the wave's top coefficient]
     for (u32 w = 3; w > wave; --w) cw = fe_add(fe_mont_mul(cw, z[8], a.f), wt[w], a.f.p);
-    Fe cin = open_shfl_down(inc, 1);             // what lies above the lane's four coefficients: W[i0 + 3]
+    Fe cin = fe_shfl_down(inc, 1);             // what lies above the lane's four coefficients: W[i0 + 3]
     if (lane == 63) cin = cw;
     else {
         Fe zl = z[2];                            // z^(4 (63 - lane)), 63 - lane >= 1
@@ -331,7 +321,7 @@ __global__ __launch_bounds__(256) void fold_kernel(FoldArgs a) {
     if (tid == 0) {
         u32 st = a.status && a.status[elem] ? 1u : 0u;
         if (!st) {
-            const Fe s = open_words(a.s + elem * 4);
+            const Fe s = fe_words(a.s + elem * 4);
             if (ge_p(s.v, a.f.p)) {
                 st = 1u;
                 if (a.status && tile == 0) a.status[elem] = (u8)H2R_E_SHAPE;   // not a canonical scalar: nothing is written for this circuit
@@ -348,8 +338,8 @@ __global__ __launch_bounds__(256) void fold_kernel(FoldArgs a) {
 #pragma unroll 1
     for (u32 q = 0; q < FOLD_LANE_ELEMS && i < a.n_coeffs; ++q, i += 256) {
         // (the accumulator stays in the representation of the columns: s is the only Montgomery-form factor of every product)
-        Fe acc = open_load(in + (u64)(a.num_cols - 1) * a.in_col_stride, i);
-        for (u32 c = a.num_cols - 1; c > 0; --c) acc = fe_add(fe_mont_mul(acc, s, a.f), open_load(in + (u64)(c - 1) * a.in_col_stride, i), a.f.p);
+        Fe acc = fe_load(in + (u64)(a.num_cols - 1) * a.in_col_stride + (u64)i * 32);
+        for (u32 c = a.num_cols - 1; c > 0; --c) acc = fe_add(fe_mont_mul(acc, s, a.f), fe_load(in + (u64)(c - 1) * a.in_col_stride + (u64)i * 32), a.f.p);
         st16(out + (u64)i * 32, acc.v[0], acc.v[1]);
         st16(out + (u64)i * 32 + 16, acc.v[2], acc.v[3]);
     }

@@ -63,14 +63,8 @@ __host__ __device__ inline u32 quotient_tiles(u32 log_ext) { return (u32)(((1ull
 
 #ifdef H2R_TU_QUOTIENT
 
-__device__ __forceinline__ Fe quot_words(const u64 *w) { Fe r; for (int k = 0; k < 4; ++k) r.v[k] = w[k]; return r; }
 // element j of a column in Montgomery form
-__device__ __forceinline__ Fe quot_load(const u8 *col, u32 j, const QuotientArgs &a) {
-    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(col + (u64)j * 32);
-    const ulonglong2 lo = p[0], hi = p[1];
-    Fe r; r.v[0] = lo.x; r.v[1] = lo.y; r.v[2] = hi.x; r.v[3] = hi.y;
-    return a.mont ? r : fe_to_mont(r, a.f);
-}
+__device__ __forceinline__ Fe quot_at(const u8 *col, u32 j, const QuotientArgs &a) { return fe_load_mont(col + (u64)j * 32, a.mont, a.f); }
 
 // grid (circuits, tiles of one launch): the circuits of a tile next to each other
 __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
@@ -83,7 +77,7 @@ __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
         u32 st = a.status && a.status[elem] ? 1u : 0u;
         if (!st) {
             auto take = [&](const u64 *w, u32 k) __attribute__((always_inline)) {
-                const Fe c = quot_words(w + elem * 4);
+                const Fe c = fe_words(w + elem * 4);
                 if (ge_p(c.v, a.f.p)) st = 1u;
                 else ch[k] = a.mont ? c : fe_to_mont(c, a.f);
             };
@@ -103,7 +97,7 @@ __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
     Fe X = a.zeta;                                // X_j = zeta * omega_ext^j from the set bits of j
     for (u32 b = 0; b < a.log_ext; ++b)
         if ((j >> b) & 1u) X = fe_mont_mul(X, a.wpow[b], a.f);
-    const Fe one = quot_words(a.f.one);
+    const Fe one = fe_words(a.f.one);
     const u8 *adv_e = a.advice.base + elem * a.advice.elem_stride, *ext_e = a.extra.base + elem * a.extra.elem_stride;
     const u8 *pz_e = a.perm_z.base + elem * a.perm_z.elem_stride;
     const u8 *ap_e = a.a_perm.base + elem * a.a_perm.elem_stride, *sp_e = a.s_perm.base + elem * a.s_perm.elem_stride;
@@ -113,8 +107,8 @@ __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
 #pragma unroll 1
     for (u32 q = 0; q < QUOT_LANE_POINTS && j < N; ++q, j += 256) {
         const u32 j_next = (j + r) & mask, j_prev = (j - r) & mask, j_last = (j - a.last_rot * r) & mask;
-        auto adv = [&](u32 c, u32 jj) __attribute__((always_inline)) { return quot_load(adv_e + (u64)c * a.advice.col_stride, jj, a); };
-        auto fix = [&](u32 c) __attribute__((always_inline)) { return quot_load(a.fixed.base + (u64)c * a.fixed.col_stride, j, a); };
+        auto adv = [&](u32 c, u32 jj) __attribute__((always_inline)) { return quot_at(adv_e + (u64)c * a.advice.col_stride, jj, a); };
+        auto fix = [&](u32 c) __attribute__((always_inline)) { return quot_at(a.fixed.base + (u64)c * a.fixed.col_stride, j, a); };
         auto mul = [&](const Fe &x, const Fe &w) __attribute__((always_inline)) { return fe_mont_mul(x, w, a.f); };
         auto add = [&](const Fe &x, const Fe &w) __attribute__((always_inline)) { return fe_add(x, w, a.f.p); };
         auto sub = [&](const Fe &x, const Fe &w) __attribute__((always_inline)) { return fe_sub(x, w, a.f.p); };
@@ -133,11 +127,11 @@ __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
             acc = add(acc, fix(a.gate_fixed[8]));
         }
         auto push = [&](const Fe &t) __attribute__((always_inline)) { acc = add(mul(acc, ch[3]), t); };
-        const Fe l0 = quot_load(a.l.base, j, a), l_last = quot_load(a.l.base + a.l.col_stride, j, a);
-        const Fe l_active = quot_load(a.l.base + 2 * a.l.col_stride, j, a);
+        const Fe l0 = quot_at(a.l.base, j, a), l_last = quot_at(a.l.base + a.l.col_stride, j, a);
+        const Fe l_active = quot_at(a.l.base + 2 * a.l.col_stride, j, a);
         // ---- the permutation argument ----
         {
-            auto Z = [&](u32 s, u32 jj) __attribute__((always_inline)) { return quot_load(pz_e + (u64)s * a.perm_z.col_stride, jj, a); };
+            auto Z = [&](u32 s, u32 jj) __attribute__((always_inline)) { return quot_at(pz_e + (u64)s * a.perm_z.col_stride, jj, a); };
             push(mul(l0, sub(one, Z(0, j))));
             {
                 const Fe z = Z(a.n_sets - 1, j);
@@ -149,9 +143,9 @@ __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
                 Fe left = Z(s, j_next), right = Z(s, j);
                 for (u32 c = c0; c < c1; ++c) {
                     const u32 src = a.src[c];
-                    const Fe v = src < 5 ? adv(src, j) : quot_load(ext_e + (u64)(src - 5) * a.extra.col_stride, j, a);
+                    const Fe v = src < 5 ? adv(src, j) : quot_at(ext_e + (u64)(src - 5) * a.extra.col_stride, j, a);
                     const Fe vg = add(v, ch[2]);
-                    left = mul(left, add(vg, mul(ch[1], quot_load(a.sigma.base + (u64)c * a.sigma.col_stride, j, a))));
+                    left = mul(left, add(vg, mul(ch[1], quot_at(a.sigma.base + (u64)c * a.sigma.col_stride, j, a))));
                     right = mul(right, add(vg, mul(bl[c], X)));
                 }
                 push(mul(l_active, sub(left, right)));
@@ -164,19 +158,19 @@ __global__ __launch_bounds__(256) void quotient_kernel(QuotientArgs a) {
                 if (!((a.lookup_mask >> k) & 1u)) continue;
                 const u8 *apc = ap_e + (u64)k * a.a_perm.col_stride, *spc = sp_e + (u64)k * a.s_perm.col_stride;
                 const u8 *zc = lz_e + (u64)k * a.look_z.col_stride;
-                const Fe z = quot_load(zc, j, a);
+                const Fe z = quot_at(zc, j, a);
                 push(mul(l0, sub(one, z)));
                 push(mul(l_last, sub(mul(z, z), z)));
-                const Fe ap = quot_load(apc, j, a), sp = quot_load(spc, j, a);
+                const Fe ap = quot_at(apc, j, a), sp = quot_at(spc, j, a);
                 {
                     const Fe ak = add(mul(ch[0], fix(a.lookup_tag[k])), mul(fix(a.lookup_enable[k]), adv(a.lookup_advice[k], j)));
-                    const Fe left = mul(mul(quot_load(zc, j_next, a), add(ap, ch[1])), add(sp, ch[2]));
+                    const Fe left = mul(mul(quot_at(zc, j_next, a), add(ap, ch[1])), add(sp, ch[2]));
                     const Fe right = mul(mul(z, add(ak, ch[1])), sg);
                     push(mul(l_active, sub(left, right)));
                 }
                 const Fe d = sub(ap, sp);
                 push(mul(l0, d));
-                push(mul(l_active, mul(d, sub(ap, quot_load(apc, j_prev, a)))));
+                push(mul(l_active, mul(d, sub(ap, quot_at(apc, j_prev, a)))));
             }
         }
         const Fe h = mul(acc, a.xinv[j & (r - 1)]);

@@ -30,8 +30,8 @@ import advice_ref as AR
 import pyref
 
 FIELDS = dict(pyref.FIELD_MODULI)
-with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_lookup_product.hpp")) as _f:
-    TILE = int(re.search(r"LOOKUP_PRODUCT_TILE = (\d+);", _f.read()).group(1))
+with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_grand_product.hpp")) as _f:
+    TILE = int(re.search(r"GRAND_PRODUCT_TILE = (\d+);", _f.read()).group(1))
 R256 = 1 << 256
 
 # ---- configurations ------------------------------------------------------------------------------------------------------------------

@@ -3,7 +3,7 @@ grand-product column Z of halo2's plonk::lookup::prover::commit_product [3P, res
 
 The plain model: A = AR.compress(AR.lookup_inputs(cells decoded from the GPU image itself, AR.fixed_row of every row's kind)), S =
 AR.table_column, A' / S' = AR.permute_expression_pair, Z by the recurrence Z[i+1] = Z[i] * (A+beta)(S+gamma) * ((A'+beta)(S'+gamma))^-1 with
-pow(den, -1, P).  The kernels work in tiles of LOOKUP_PRODUCT_TILE rows (read from csrc/h2r_lookup_product.hpp: 1,024); the usable rows are
+pow(den, -1, P).  The kernels work in tiles of GRAND_PRODUCT_TILE rows (read from csrc/h2r_grand_product.hpp: 1,024); the usable rows are
 chosen against it: a column shorter than one tile (1,018), columns of 8 and 32 tiles with a ragged last tile (8,186, 32,762), and -- since
 2^k - 6 is never a multiple of a power-of-two tile -- one circuit with usable_rows = 2 * tile exactly, where Z[usable_rows] is the first row
 of a tile that no column row starts (the "length + 1 crosses a tile boundary" case)."""
@@ -27,8 +27,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R256 = 1 << 256
 M64 = (1 << 64) - 1
 SENTINEL = 0xAB
-with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_lookup_product.hpp")) as _f:
-    TILE = int(re.search(r"LOOKUP_PRODUCT_TILE = (\d+);", _f.read()).group(1))
+with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_grand_product.hpp")) as _f:
+    TILE = int(re.search(r"GRAND_PRODUCT_TILE = (\d+);", _f.read()).group(1))
 
 
 @pytest.fixture(scope="module")

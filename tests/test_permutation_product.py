@@ -3,7 +3,7 @@ restated in DESIGN.md section 2e]) against the plain model of tests/permutation_
 
 Images are the modpow_public_key elements of tests/test_lookup_product.py ([assert_in_field rows][pow rows], three circuits); the copy pairs
 are h2r_pow_copy_map's, the sigma columns the model's (union-find over the pairs), and h2r_advice_check must accept the same pairs on the
-same image.  The kernels work in tiles of PERM_PRODUCT_TILE rows (read from csrc/h2r_permutation_product.hpp); the usable rows are chosen
+same image.  The kernels work in tiles of GRAND_PRODUCT_TILE rows (read from csrc/h2r_grand_product.hpp); the usable rows are chosen
 against it: under one tile (1,018), eight tiles with a ragged last one (8,186), exactly two tiles (Z[u] behind the last tile), and for the
 carry wave 65 tiles + 3 rows (a lane of the carry wave holds two tiles) and 129 tiles - 1 row (three tiles per lane, and lanes without any)."""
 import os
@@ -25,8 +25,8 @@ from test_lookup_product import _P, bytes_of, in_repr, rand_modulus, usable_for
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 R256 = 1 << 256
 SENTINEL = 0xAB
-with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_permutation_product.hpp")) as _f:
-    TILE = int(re.search(r"PERM_PRODUCT_TILE = (\d+);", _f.read()).group(1))
+with open(os.path.join(ROOT, "halo2_rsa_amd", "csrc", "h2r_grand_product.hpp")) as _f:
+    TILE = int(re.search(r"GRAND_PRODUCT_TILE = (\d+);", _f.read()).group(1))
 
 
 @pytest.fixture(scope="module")

@@ -28,8 +28,8 @@ HBM = 8.0e12
 # clock, not read from the device), so the issue-rate fractions below are lower bounds of what the kernels reach at the clock they really ran at.
 CLOCK, MADS_PER_PRODUCT = 2.4e9, 136
 PEAK_PRODUCTS = 256 * 4 * 64 * CLOCK / 4.8 / MADS_PER_PRODUCT
-with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2_rsa_amd", "csrc", "h2r_lookup_product.hpp")) as f:
-    TILE = int(re.search(r"LOOKUP_PRODUCT_TILE = (\d+);", f.read()).group(1))
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2_rsa_amd", "csrc", "h2r_grand_product.hpp")) as f:
+    TILE = int(re.search(r"GRAND_PRODUCT_TILE = (\d+);", f.read()).group(1))
 # Montgomery products per lane (four rows) that the algorithm needs, (Montgomery ctx, + the conversions of a canonical ctx):
 #   tiles: n, d of four rows 8 (+12 loads into the domain), the lane's two products 6, the wave's two reductions 12
 #   scan:  n, d 8 (+12), serial scans 6, wave scans 12, the waves' carries 3, the lane's carries 2, Z of four rows 11 (+4 stores out of the domain)

@@ -31,8 +31,8 @@ R256 = 1 << 256
 HBM = 8.0e12
 SRC, CHUNK = (0, 1, 2, 3, 4, 5), 2
 M, SETS = len(SRC), 3
-with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2_rsa_amd", "csrc", "h2r_permutation_product.hpp")) as f:
-    TILE = int(re.search(r"PERM_PRODUCT_TILE = (\d+);", f.read()).group(1))
+with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "halo2_rsa_amd", "csrc", "h2r_grand_product.hpp")) as f:
+    TILE = int(re.search(r"GRAND_PRODUCT_TILE = (\d+);", f.read()).group(1))
 PERM = [("tiles", _lib.KERNEL_PERM_PRODUCT_TILES), ("carry", _lib.KERNEL_PERM_PRODUCT_CARRY), ("scan", _lib.KERNEL_PERM_PRODUCT_SCAN)]
 LOOKUP = [("tiles", _lib.KERNEL_LOOKUP_PRODUCT_TILES), ("carry", _lib.KERNEL_LOOKUP_PRODUCT_CARRY), ("scan", _lib.KERNEL_LOOKUP_PRODUCT_SCAN)]
 
