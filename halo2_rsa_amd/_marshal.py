@@ -24,7 +24,13 @@ def set_words(field, v):
 
 def challenges(values, dev, batch=None) -> torch.Tensor:
     """int64 [values' shape..., 4] on `dev`: the words of a per-circuit list of integers (batch: how many it must hold), or of the
-    nested [batch][num_points] list of opening points."""
+    nested [batch][num_points] list of opening points.  An int64 tensor already on a device ([batch, 4] or [batch, num_points, 4]: what
+    prover.Transcript draws) passes through where it lies; a strided view of one is made contiguous there."""
+    if isinstance(values, torch.Tensor) and values.is_cuda and values.dtype == torch.int64:
+        assert values.dim() in (2, 3) and values.shape[-1] == 4
+        assert batch is None or tuple(values.shape) == (batch, 4)
+        return values if values.is_contiguous() else values.contiguous()
+
     def nest(v):
         return [nest(x) for x in v] if isinstance(v, (list, tuple, range)) or getattr(v, "ndim", 0) else words(v)
     w = np.array(nest(values), dtype=np.uint64)

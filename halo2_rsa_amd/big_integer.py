@@ -5,7 +5,7 @@ for the methods on the hot path -- `assign_integer`, `mul_mod`, `square_mod`, `p
 `pow_mod_fixed_exp` -- in batch form: every integer argument is a batch of integers (one per
 independent circuit), resident in HBM.  All arithmetic happens in libh2r.so (hand-written HIP);
 this module only moves pointers.  There is no CPU fallback.
-The prover stages that the reference's module has no counterpart of (LookupArgument, PermutationArgument, EvaluationDomain, CommitKey)
+The prover stages that the reference's module has no counterpart of (LookupArgument, PermutationArgument, EvaluationDomain, CommitKey, Transcript)
 live in `prover` and are re-exported here; `_marshal` holds what both modules do between an argument and a pointer.
 """
 import ctypes
@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import H2RLayout, H2RParams, H2RPowLayout, check, lib
 from ._marshal import hold, image_stride, kinds_tensor, ptr, ref
-from .prover import CommitKey, EvaluationDomain, LookupArgument, PermutationArgument  # noqa: F401  (re-exported: they lived here once)
+from .prover import CommitKey, EvaluationDomain, LookupArgument, PermutationArgument, Transcript  # noqa: F401  (re-exported: they lived here once)
 
 
 def _e_bytes(e: int) -> bytes:

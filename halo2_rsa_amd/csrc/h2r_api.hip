@@ -30,6 +30,7 @@
 #include "h2r_open.hpp"
 #include "h2r_msm.hpp"
 #include "h2r_curve_ntt.hpp"
+#include "h2r_transcript.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4456,7 +4457,7 @@ namespace {
 static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_OPEN_SCAN == H2R_KERNEL_OPEN_TILES + 2 &&
               H2R_KERNEL_MSM_BUCKET == H2R_KERNEL_FOLD + 1 && H2R_KERNEL_MSM_FOLD == H2R_KERNEL_MSM_BUCKET + 1 &&
               H2R_KERNEL_CURVE_NTT_TWIDDLE == H2R_KERNEL_MSM_FOLD + 1 && H2R_KERNEL_CURVE_NTT_STORE == H2R_KERNEL_CURVE_NTT_TWIDDLE + 3 &&
-              H2R_KERNEL_COUNT == H2R_KERNEL_CURVE_NTT_STORE + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_TRANSCRIPT + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -4771,6 +4772,154 @@ int32_t h2r_curve_ntt(const h2r_ctx *ctx, const h2r_curve_ntt_config *cfg, const
     for (ca.stage = 1; ca.stage <= log_n; ++ca.stage)
         if (const int32_t rc = launch(H2R_KERNEL_CURVE_NTT_STAGE, 2, n / 2)) return rc;
     return launch(H2R_KERNEL_CURVE_NTT_STORE, 3, n);
+} H2R_CATCH_STATUS
+
+// ---- the Fiat-Shamir transcript: a batch of BLAKE2b states, one launch per round (h2r_transcript.hpp, h2r_tu_transcript.hip) --------------
+namespace {
+static_assert(H2R_TRANSCRIPT_MAX_ITEMS == TR_MAX_ITEMS && H2R_TRANSCRIPT_MAX_SQUEEZE == TR_MAX_SQUEEZE && H2R_TRANSCRIPT_MAX_DERIVE == TR_MAX_DERIVE &&
+              H2R_TRANSCRIPT_MAX_COUNT == TR_MAX_COUNT && H2R_TRANSCRIPT_POINT == TR_POINT && H2R_TRANSCRIPT_SCALAR == TR_SCALAR &&
+              H2R_TRANSCRIPT_COMMON == TR_COMMON, "h2r.h and the kernel's argument struct");
+// the constants of a ctx whose field has a curve; R^3 = R^2 * R^2 * R^-1, formed here once per call
+TrConsts transcript_consts(const h2r_ctx *ctx, const CurveConsts &cv) {
+    TrConsts c;
+    std::memset(static_cast<void *>(&c), 0, sizeof c);
+    c.fr = ctx->fc; c.fq = cv.fq; c.mont = ctx_mont(ctx);
+    const Fe r3 = fe_mont_mul(fe_r2(ctx->fc), fe_r2(ctx->fc), ctx->fc);
+    for (int k = 0; k < 4; ++k) c.r3[k] = r3.v[k];
+    return c;
+}
+u64 transcript_item_bytes(const h2r_transcript_item &it) { return (u64)it.count * (it.kind == TR_POINT ? 64u : 32u); }
+}  // namespace
+
+uint64_t h2r_transcript_state_bytes(void) try { return TR_STATE_BYTES; } H2R_CATCH_ZERO
+
+int32_t h2r_transcript_round(const h2r_ctx *ctx, const h2r_transcript_config *cfg, const h2r_transcript_item *items, const h2r_transcript_derive *derive,
+                             void *states, uint64_t batch, uint64_t *challenges, uint64_t *derived, void *proof, uint64_t proof_stride,
+                             uint64_t proof_off, uint8_t *status, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !states) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_transcript_config) || (cfg->flags & ~H2R_TRANSCRIPT_INIT)) return H2R_E_UNSUPPORTED;
+    const bool items_ok = cfg->num_items <= TR_MAX_ITEMS, derive_ok = cfg->num_derive <= TR_MAX_DERIVE;
+    if ((items_ok && cfg->num_items && !items) || (derive_ok && cfg->num_derive && !derive)) return H2R_E_NULL;
+    if ((cfg->num_squeeze && !challenges) || (cfg->num_derive && !derived)) return H2R_E_NULL;   // a count with no output to go to
+    u64 written = 0;   // items that go to the proof
+    if (items_ok)
+        for (u32 i = 0; i < cfg->num_items; ++i) {
+            if (!items[i].base) return H2R_E_NULL;
+            if (!(items[i].flags & TR_COMMON)) written += items[i].count;
+        }
+    if (written && !proof) return H2R_E_NULL;
+    if (!items_ok || !derive_ok || cfg->num_squeeze > TR_MAX_SQUEEZE || cfg->reserved) return H2R_E_SHAPE;
+    for (u32 i = 0; i < cfg->num_items; ++i) {
+        const h2r_transcript_item &it = items[i];
+        if ((it.kind != TR_POINT && it.kind != TR_SCALAR) || (it.flags & ~TR_COMMON) || it.count == 0 || it.count > TR_MAX_COUNT || it.reserved) return H2R_E_SHAPE;
+    }
+    TranscriptArgs ta;
+    std::memset(static_cast<void *>(&ta), 0, sizeof ta);
+    for (u32 j = 0; j < cfg->num_derive; ++j) {
+        if (derive[j].src >= cfg->num_squeeze || derive[j].log2_pow > TR_MAX_LOG2_POW || ge_p(derive[j].mult, ctx->fc.p)) return H2R_E_SHAPE;
+        const Fe m = cfg_to_mont(ctx, derive[j].mult);
+        for (int k = 0; k < 4; ++k) ta.derive[j].mult[k] = m.v[k];
+        ta.derive[j].src = derive[j].src; ta.derive[j].log2_pow = derive[j].log2_pow;
+    }
+    if (misaligned(states) || misaligned(challenges) || misaligned(derived) || misaligned(proof, proof_stride, proof_off)) return H2R_E_SHAPE;
+    for (u32 i = 0; i < cfg->num_items; ++i)
+        if (misaligned(items[i].base, items[i].elem_stride) || (items[i].elem_stride && items[i].elem_stride < transcript_item_bytes(items[i]))) return H2R_E_SHAPE;
+    const u128 w_bytes = (u128)32 * written;
+    if (written && (u128)proof_off + w_bytes > proof_stride) return H2R_E_SHAPE;
+    if (batch == 0) return H2R_E_SHAPE;
+    {   // what the round writes may share no byte with what it reads, nor with another output
+        struct Range { const void *p; u128 n; };
+        const ColumnBlock pr{static_cast<const u8 *>(proof) + proof_off, (u64)w_bytes, proof_stride, (u64)w_bytes, 1, batch};
+        const Range outs[5] = {{states, (u128)batch * TR_STATE_BYTES}, {challenges, (u128)batch * cfg->num_squeeze * 32}, {derived, (u128)batch * cfg->num_derive * 32},
+                               {written ? pr.base : nullptr, written ? pr.extent() : 0}, {status, status ? (u128)batch : 0}};
+        for (u32 x = 0; x < 5; ++x) {
+            if (!outs[x].p || !outs[x].n) continue;
+            for (u32 y = x + 1; y < 5; ++y)
+                if (outs[y].p && outs[y].n && overlaps(outs[x].p, outs[x].n, outs[y].p, outs[y].n)) return H2R_E_SHAPE;
+            for (u32 i = 0; i < cfg->num_items; ++i) {
+                const u64 nb = transcript_item_bytes(items[i]);
+                if (const ColumnBlock s{items[i].base, nb, items[i].elem_stride, nb, 1, batch}; overlaps(s, outs[x].p, outs[x].n)) return H2R_E_SHAPE;
+            }
+        }
+    }
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    for (u32 i = 0; i < cfg->num_items; ++i)
+        ta.items[i] = TrItem{static_cast<const u8 *>(items[i].base), items[i].elem_stride, items[i].count, items[i].kind | (items[i].flags << 8)};
+    ta.states = static_cast<u8 *>(states); ta.challenges = challenges; ta.derived = derived; ta.proof = static_cast<u8 *>(proof); ta.status = status;
+    ta.proof_stride = proof_stride; ta.proof_off = proof_off; ta.batch = batch;
+    ta.num_items = cfg->num_items; ta.num_squeeze = cfg->num_squeeze; ta.num_derive = cfg->num_derive; ta.init = (cfg->flags & H2R_TRANSCRIPT_INIT) != 0;
+    ta.c = transcript_consts(ctx, *cv);
+    // slices of workgroups of 64 circuits, below the 2^32 global size and the 65,535 of a grid dimension
+    const u64 blocks = (batch + TR_LANES - 1) / TR_LANES;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return for_each_slice(blocks, slice_items(1, blocks), [&](u64 b0, u64 nb) {
+        ta.block0 = (u32)b0;
+        return stage_launch(H2R_KERNEL_TRANSCRIPT, st, [&](hipEvent_t a, hipEvent_t b) { return launch_transcript(ta, (u32)nb, st, a, b); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_transcript_eval(const h2r_ctx *ctx, uint32_t op, void *state, const uint8_t *in, uint64_t in_len, uint64_t *out) try {
+    if (!ctx || (op <= 2 && !state) || (op != 0 && op != 2 && !in) || (op >= 2 && op <= 5 && !out)) return H2R_E_NULL;
+    if (op > 5) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    const TrConsts c = transcript_consts(ctx, *cv);
+    u64 w[TR_STATE_WORDS];
+    TrHash s;
+    const TrBlock blk{w + TR_W_BLOCK, 1};
+    auto load = [&] {
+        std::memcpy(w, state, sizeof w);
+        for (int i = 0; i < 8; ++i) s.h[i] = w[i];
+        s.t = w[TR_W_T]; s.fill = (u32)w[TR_W_FILL];
+        return s.fill <= 128 && w[TR_W_FILL] <= 128;
+    };
+    auto store = [&] {
+        for (int i = 0; i < 8; ++i) w[i] = s.h[i];
+        w[TR_W_T] = s.t; w[TR_W_FILL] = s.fill;
+        std::memcpy(state, w, sizeof w);
+    };
+    auto fe_at = [&](const uint8_t *p) { Fe x; std::memcpy(x.v, p, 32); return x; };
+    auto put = [&](const Fe &x) { for (int k = 0; k < 4; ++k) out[k] = x.v[k]; };
+    if (op == 0) {          // the empty transcript
+        std::memset(w, 0, sizeof w);
+        tr_init(s);
+        store();
+    } else if (op == 1) {   // absorb a list of records: a kind byte (1 point, 2 scalar), then 64 or 32 bytes in the ctx's representation
+        if (!load()) return H2R_E_SHAPE;
+        for (int pass = 0; pass < 2; ++pass)   // as the kernel: every item is checked before the first one is absorbed
+            for (u64 off = 0; off < in_len;) {
+                const u32 kind = in[off];
+                const u64 size = kind == TR_POINT ? 64 : 32;
+                if ((kind != TR_POINT && kind != TR_SCALAR) || in_len - off - 1 < size) return H2R_E_SHAPE;
+                Fe x = fe_at(in + off + 1), y = kind == TR_POINT ? fe_at(in + off + 33) : fe_zero();
+                if (pass == 0) { if (const u32 bad = tr_check_item(kind, x, y, c)) return (int32_t)bad; }
+                else { tr_canonical(kind, x, y, c); tr_absorb_item(s, blk, kind, x, y); }
+                off += 1 + size;
+            }
+        store();
+    } else if (op == 2) {   // squeeze one challenge
+        if (!load()) return H2R_E_SHAPE;
+        put(tr_to_repr(tr_squeeze(s, blk, c), c));
+        store();
+    } else if (op == 3) {   // derive: in = c, mult (32 bytes each, the ctx's representation), log2_pow (4 bytes, little-endian)
+        if (in_len != 68) return H2R_E_SHAPE;
+        const Fe ch = fe_at(in), mult = fe_at(in + 32);
+        u32 l; std::memcpy(&l, in + 64, 4);
+        if (ge_p(ch.v, c.fr.p) || ge_p(mult.v, c.fr.p) || l > TR_MAX_LOG2_POW) return H2R_E_SHAPE;
+        const Fe cm = c.mont ? ch : fe_to_mont(ch, c.fr), mm = c.mont ? mult : fe_to_mont(mult, c.fr);
+        put(tr_to_repr(tr_derive(cm, mm, l, c.fr), c));
+    } else {                // the 32 proof bytes of one item: 4 = a point (in = 64 bytes), 5 = a scalar (in = 32 bytes)
+        const u32 kind = op == 4 ? TR_POINT : TR_SCALAR;
+        if (in_len != (kind == TR_POINT ? 64u : 32u)) return H2R_E_SHAPE;
+        Fe x = fe_at(in), y = kind == TR_POINT ? fe_at(in + 32) : fe_zero();
+        if (const u32 bad = tr_check_item(kind, x, y, c)) return (int32_t)bad;
+        tr_canonical(kind, x, y, c);
+        put(tr_encode(kind, x, y));
+    }
+    return H2R_OK;
 } H2R_CATCH_STATUS
 
 // The copy constraints of one fixed-exponent pow element (h2r_pow_trace_emit_advice's image: CONST1, CONST0, then the records), rows

@@ -14,6 +14,7 @@
 //   h2r_tu_open.hip    the openings: evaluations at x, GWC witness polynomials, the fold of h's pieces (h2r_open.hpp)
 //   h2r_tu_msm.hip     the commitments: multi-scalar multiplications over the curve of the ctx's field (h2r_msm.hpp, h2r_curve.hpp)
 //   h2r_tu_curve_ntt.hip   the Lagrange-basis commitment key: the transform over the curve's points (h2r_curve_ntt.hpp, h2r_curve.hpp)
+//   h2r_tu_transcript.hip   the Fiat-Shamir transcript: one round of a batch of BLAKE2b states per launch (h2r_transcript.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -144,5 +145,8 @@ hipError_t launch_msm(u32 phase, const MsmArgs &a, u32 num_elems, hipStream_t st
 // workgroups [a.block0, a.block0 + num_blocks) of 256 twiddles / points / butterflies / points.
 struct CurveNttArgs;
 hipError_t launch_curve_ntt(u32 phase, const CurveNttArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_transcript.hip (argument struct: h2r_transcript.hpp).  One round of the workgroups [a.block0, a.block0 + num_blocks) of 64 circuits.
+struct TranscriptArgs;
+hipError_t launch_transcript(const TranscriptArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

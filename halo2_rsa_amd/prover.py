@@ -1,5 +1,6 @@
 """The prover stages on the device: halo2's lookup and permutation arguments, the evaluation domain (transforms, quotient, openings) and
-the commitment key.  None of them has a counterpart in the reference's `big_integer` module; `big_integer` re-exports the four classes.
+the commitment key, and the Fiat-Shamir transcript that joins them.  None of them has a counterpart in the reference's `big_integer`
+module; `big_integer` re-exports the five classes.
 All arithmetic happens in libh2r.so; every method marshals its arguments with `_marshal` and makes the call.
 A chip is whatever has `_ctx`, `_stream()`, `device` and `montgomery` (big_integer.BigIntChip)."""
 import ctypes
@@ -456,3 +457,95 @@ class CommitKey:
         key = CommitKey(self.chip, out)
         hold(key, "transform", ws, self.bases, out)
         return key
+
+
+class Transcript:
+    """halo2's Fiat-Shamir transcript for a batch of circuits on the device (h2r_transcript_round):
+    `Blake2bWrite<_, G1Affine, Challenge255<_>>`, one launch per round, no host synchronisation between the stages.  Owns the per-circuit
+    states and the proof buffer uint8 [batch, proof_bytes] (proof_bytes a multiple of 32) and keeps the running write offset: a round
+    writes 32 bytes per written item, the same for every circuit.  Only a chip whose field has a curve (bn254_fr)."""
+
+    POINT, SCALAR = "point", "scalar"
+
+    def __init__(self, chip: "BigIntChip", batch: int, proof_bytes: int):
+        if batch < 1 or proof_bytes < 0 or proof_bytes % 32:
+            check(_lib.H2R_E_SHAPE, "Transcript")
+        dev = "cuda:%d" % chip.device
+        self.chip, self.batch, self.offset, self.started = chip, int(batch), 0, False
+        self.states = torch.zeros((batch, int(lib().h2r_transcript_state_bytes())), dtype=torch.uint8, device=dev)
+        # (a transcript that only draws challenges has proof_bytes = 0: its rows still get a 16-byte aligned stride)
+        self.buffer = torch.zeros((batch, max(int(proof_bytes), 32)), dtype=torch.uint8, device=dev)[:, :proof_bytes]
+
+    def _item(self, item, common: bool) -> "_lib.H2RTranscriptItem":
+        """A tensor, or (tensor, POINT | SCALAR), as a descriptor.  Points: int64 [batch, count, 2, 4] or uint8 [batch, count, 64] per
+        circuit; with a kind also int64 [count, 2, 4] / [2, 4] or uint8 [count, 64] / [64] for one copy the batch shares.  Scalars: int64
+        [batch, count, 4] or uint8 [batch, count, 32] per circuit, int64 [count, 4] / [4] or uint8 [count, 32] / [32] shared.  Without a
+        kind the dimensions decide: int64 with four is points, uint8 by its last dimension, everything else scalars."""
+        t, kind = item if isinstance(item, (tuple, list)) else (item, None)
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in (torch.int64, torch.uint8) or t.dim() == 0:
+            check(_lib.H2R_E_SHAPE, "Transcript.round")
+        words_form = t.dtype == torch.int64
+        if kind is None:
+            kind = self.POINT if (words_form and t.dim() == 4) or (not words_form and t.shape[-1] == 64) else self.SCALAR
+        tail = ((2, 4) if kind == self.POINT else (4,)) if words_form else ((64,) if kind == self.POINT else (32,))
+        lead = t.dim() - len(tail)
+        if kind not in (self.POINT, self.SCALAR) or lead not in (0, 1, 2) or tuple(t.shape[lead:]) != tail or (lead == 2 and t.shape[0] != self.batch):
+            check(_lib.H2R_E_SHAPE, "Transcript.round")
+        count = int(t.shape[lead - 1]) if lead else 1
+        assert t[0].is_contiguous() if lead == 2 else t.is_contiguous(), "the entries of an item lie back to back"
+        d = _lib.H2RTranscriptItem()
+        d.base, d.elem_stride, d.count = t.data_ptr(), t.stride(0) * t.element_size() if lead == 2 else 0, count
+        d.kind, d.flags = _lib.H2R_TRANSCRIPT_POINT if kind == self.POINT else _lib.H2R_TRANSCRIPT_SCALAR, _lib.H2R_TRANSCRIPT_COMMON if common else 0
+        return d
+
+    def round(self, items=(), squeeze: int = 0, derive=(), common: bool = False, status: Optional[torch.Tensor] = None, out=None):
+        """(challenges, derived): int64 [batch, squeeze, 4] and int64 [batch, len(derive), 4] on the device, in the chip's representation
+        -- every stage method takes them (or a view such as challenges[:, 0]) for its thetas, betas, gammas, ys, scalars, points and vs.
+        items: tensors (see _item) absorbed in order and, unless `common`, appended to the proof; derive: (src, mult, log2_pow) triples,
+        derived[e][j] = mult * challenges[e][src]^(2^log2_pow), mult an integer in the chip's representation (x * omega^rot for the opening
+        points, x^n for the fold).  status: uint8 [batch]; a byte that is nonzero on entry skips the circuit (state, proof and outputs
+        untouched; the call never clears it), H2R_E_ASSERTION marks a (0, 0) point, H2R_E_SHAPE a value that is not canonical.  out:
+        (challenges, derived) to write into.  The first round initialises the states."""
+        items, derive, dev = list(items), list(derive), self.states.device
+        if len(items) > _lib.H2R_TRANSCRIPT_MAX_ITEMS or not 0 <= squeeze <= _lib.H2R_TRANSCRIPT_MAX_SQUEEZE or len(derive) > _lib.H2R_TRANSCRIPT_MAX_DERIVE:
+            check(_lib.H2R_E_SHAPE, "Transcript.round")
+        cfg = _lib.H2RTranscriptConfig(struct_size=ctypes.sizeof(_lib.H2RTranscriptConfig), num_items=len(items), num_squeeze=squeeze,
+                                       num_derive=len(derive), flags=0 if self.started else _lib.H2R_TRANSCRIPT_INIT, reserved=0)
+        desc = (_lib.H2RTranscriptItem * max(len(items), 1))(*[self._item(it, common) for it in items])
+        dv = (_lib.H2RTranscriptDerive * max(len(derive), 1))()
+        for d, (src, mult, log2_pow) in zip(dv, derive):
+            d.src, d.log2_pow = int(src), int(log2_pow)
+            set_words(d.mult, mult)
+        nbytes = 0 if common else 32 * sum(int(d.count) for d in desc[:len(items)])
+        if self.offset + nbytes > self.buffer.shape[1]:
+            check(_lib.H2R_E_SHAPE, "Transcript.round")
+        challenges_out, derived = outputs(out, dev, (torch.zeros, torch.int64, (self.batch, squeeze, 4)), (torch.zeros, torch.int64, (self.batch, len(derive), 4)))
+        for t, n in ((challenges_out, squeeze), (derived, len(derive))):
+            assert t.is_contiguous() and t.dtype == torch.int64 and tuple(t.shape) == (self.batch, n, 4)
+        check(lib().h2r_transcript_round(self.chip._ctx, ctypes.byref(cfg), desc if items else None, dv if derive else None, self.states.data_ptr(),
+                                         self.batch, challenges_out.data_ptr() if squeeze else None, derived.data_ptr() if derive else None,
+                                         self.buffer.data_ptr() if nbytes else None, self.buffer.stride(0), self.offset, ptr(status), self.chip._stream()),
+              "h2r_transcript_round")
+        self.started, self.offset = True, self.offset + nbytes
+        hold(self, "round", [it[0] if isinstance(it, (tuple, list)) else it for it in items], challenges_out, derived, status)
+        return challenges_out, derived
+
+    def write_points(self, points: torch.Tensor, squeeze: int = 0, derive=(), status: Optional[torch.Tensor] = None):
+        """Absorbs and writes points (CommitKey.commit's output as it is); round()'s return."""
+        return self.round([(points, self.POINT)], squeeze, derive, False, status)
+
+    def write_scalars(self, scalars: torch.Tensor, squeeze: int = 0, derive=(), status: Optional[torch.Tensor] = None):
+        """Absorbs and writes scalars (open_eval's evaluations as they are); round()'s return."""
+        return self.round([(scalars, self.SCALAR)], squeeze, derive, False, status)
+
+    def common_points(self, points: torch.Tensor, squeeze: int = 0, derive=(), status: Optional[torch.Tensor] = None):
+        """Absorbs points without writing them; round()'s return."""
+        return self.round([(points, self.POINT)], squeeze, derive, True, status)
+
+    def common_scalars(self, scalars: torch.Tensor, squeeze: int = 0, derive=(), status: Optional[torch.Tensor] = None):
+        """Absorbs scalars without writing them (the verifying key's digest, the instances); round()'s return."""
+        return self.round([(scalars, self.SCALAR)], squeeze, derive, True, status)
+
+    def proof(self) -> torch.Tensor:
+        """uint8 [batch, offset]: the proof bytes written so far (a view of the buffer)."""
+        return self.buffer[:, :self.offset]

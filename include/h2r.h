@@ -1121,6 +1121,65 @@ int32_t h2r_curve_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *a, const
 typedef struct h2r_curve_ntt_config { uint32_t struct_size, log_n, flags, reserved; uint64_t omega[4]; } h2r_curve_ntt_config;
 uint64_t h2r_curve_ntt_workspace_bytes(const h2r_curve_ntt_config *cfg);
 int32_t h2r_curve_ntt(const h2r_ctx *ctx, const h2r_curve_ntt_config *cfg, const void *in, void *out, void *workspace, h2r_stream_t stream);
+/* ---- the Fiat-Shamir transcript: a batch of BLAKE2b states on the device, one launch per round ----
+ * THIRD-PARTY behaviour (halo2's Blake2bWrite over G1Affine with Challenge255, the transcript of the reference's only prover configuration),
+ * restated in DESIGN.md section 2l.  The HASH is pinned: BLAKE2b, 64-byte digest, no key, no salt, personalisation "Halo2-Transcript", byte
+ * for byte against Python's hashlib (tests/transcript_ref.py).  The FRAMING is a restatement of halo2 and halo2curves, not pinned against
+ * them: a point absorbs the byte 0x01, then x, then y; a scalar absorbs 0x02, then its value; every field element as its 32 little-endian
+ * canonical bytes.  A squeeze absorbs 0x00, finalises a copy of the state (the running state keeps the 0x00 and goes on), reads the 64
+ * digest bytes as a little-endian 512-bit integer and reduces it modulo r.  A written scalar is its 32 canonical bytes; a written point
+ * the 32 canonical bytes of x with bit 7 of byte 31 set to the lowest bit of canonical y.  Only a ctx whose field has a curve
+ * (h2r_msm_columns above): x and y are elements of the curve's coordinate field, scalars and challenges of the ctx's field.
+ * h2r_transcript_round does, per circuit e and in this order: (1) with H2R_TRANSCRIPT_INIT in cfg->flags the state becomes the empty
+ * transcript; (2) every item is absorbed, in item order; (3) the items without H2R_TRANSCRIPT_COMMON are written to
+ * proof + e * proof_stride + proof_off, 32 bytes each, in item order; (4) num_squeeze challenges are drawn into challenges[e][k][4];
+ * (5) derived[e][j] = mult * c_src^(2^log2_pow) for the round's own challenges c.
+ *  - states: batch records of h2r_transcript_state_bytes bytes (a host function), opaque, 16-byte aligned, the caller's between rounds.
+ *  - items: a host array of cfg->num_items descriptors.  An item names `count` consecutive entries at base + e * elem_stride on the device:
+ *    kind H2R_TRANSCRIPT_POINT = affine points of 64 bytes, x then y (h2r_msm_columns' out[batch][num_cols][2][4] is named in place),
+ *    kind H2R_TRANSCRIPT_SCALAR = field elements of 32 bytes (h2r_open_eval_columns' evals[batch][Q][4] likewise), all in the ctx's
+ *    representation; elem_stride = 0 is one copy for the whole batch.  A common item (the verifying key's digest, the instances) is
+ *    absorbed and not written.
+ *  - The bytes a round writes are 32 * the sum of the counts of its written items, the same for every circuit: the write offset is the
+ *    caller's host argument and no length lives on the device.
+ *  - challenges, derived: uint64 [batch][num_squeeze][4] and [batch][num_derive][4] on the device, in the ctx's representation: every
+ *    stage's theta / beta / gamma / y / points / v / s argument takes them where they lie.  derive[j].mult is in the ctx's representation
+ *    (x * omega^rot for the opening points and x^n for the fold in the same launch).
+ *  - status (nullable, [batch]) is never cleared: a circuit whose byte is nonzero on entry is skipped -- state, proof and outputs stay
+ *    untouched.  H2R_E_ASSERTION for the point at infinity, (0, 0), among the items (upstream returns an error), H2R_E_SHAPE for a
+ *    coordinate >= q or a scalar >= r; the first such item in item order decides.  A circuit that gets a status in a round leaves its
+ *    state, its proof bytes and its outputs untouched for that round.
+ *  - One launch per call, one lane per circuit, 64 circuits per workgroup, enqueued on `stream`, never synchronising; no workgroup waits
+ *    for another; launches are sliced internally below the 2^32 global size.
+ *  - H2R_E_NULL for a NULL ctx, cfg or states, a NULL items / derive array or item base, a nonzero num_squeeze / num_derive with a NULL
+ *    challenges / derived, a written item with a NULL proof; H2R_E_UNSUPPORTED for another struct_size or unknown flag bits, a field
+ *    without a curve, or a host-only ctx (that one after every other check); H2R_E_SHAPE for num_items > 64, num_squeeze > 8, num_derive
+ *    > 16, a nonzero `reserved`, an item's kind, flags or count (0 or > H2R_TRANSCRIPT_MAX_COUNT) out of range, src >= num_squeeze,
+ *    log2_pow > 24, mult >= p, a pointer, stride or proof_off that is not 16-byte aligned, a nonzero elem_stride smaller than the item,
+ *    proof_off plus the round's bytes above proof_stride, batch = 0, and states, challenges, derived, the written proof bytes or status
+ *    overlapping an item or each other.
+ *  - h2r_transcript_eval (host only; works on a host-only ctx) runs for ONE circuit the very functions the kernel inlines, on a state
+ *    record in host memory.  op 0 = the empty transcript -> state; 1 = absorb `in`, a list of records of one kind byte (1 or 2) followed
+ *    by the item's 64 or 32 bytes in the ctx's representation (a status leaves the state untouched); 2 = squeeze: out[4] = the challenge;
+ *    3 = derive: in = c, mult (32 bytes each) and log2_pow (4 bytes, little-endian), out[4] = mult * c^(2^log2_pow); 4 / 5 = the proof
+ *    bytes of a point (in = 64 bytes) / a scalar (in = 32 bytes) -> out[4].  Values in and out in the ctx's representation.
+ *    H2R_E_SHAPE for another op, a list that does not parse, another in_len, a value >= its modulus; H2R_E_ASSERTION for (0, 0). */
+#define H2R_TRANSCRIPT_MAX_ITEMS   64
+#define H2R_TRANSCRIPT_MAX_SQUEEZE 8
+#define H2R_TRANSCRIPT_MAX_DERIVE  16
+#define H2R_TRANSCRIPT_MAX_COUNT   65536u
+#define H2R_TRANSCRIPT_INIT   1u     /* h2r_transcript_config.flags */
+#define H2R_TRANSCRIPT_POINT  1u     /* h2r_transcript_item.kind */
+#define H2R_TRANSCRIPT_SCALAR 2u
+#define H2R_TRANSCRIPT_COMMON 1u     /* h2r_transcript_item.flags */
+typedef struct h2r_transcript_config { uint32_t struct_size, num_items, num_squeeze, num_derive, flags, reserved; } h2r_transcript_config;
+typedef struct h2r_transcript_item { const void *base; uint64_t elem_stride; uint32_t count, kind, flags, reserved; } h2r_transcript_item;
+typedef struct h2r_transcript_derive { uint32_t src, log2_pow; uint64_t mult[4]; } h2r_transcript_derive;
+uint64_t h2r_transcript_state_bytes(void);
+int32_t h2r_transcript_round(const h2r_ctx *ctx, const h2r_transcript_config *cfg, const h2r_transcript_item *items,
+                             const h2r_transcript_derive *derive, void *states, uint64_t batch, uint64_t *challenges, uint64_t *derived,
+                             void *proof, uint64_t proof_stride, uint64_t proof_off, uint8_t *status, h2r_stream_t stream);
+int32_t h2r_transcript_eval(const h2r_ctx *ctx, uint32_t op, void *state, const uint8_t *in, uint64_t in_len, uint64_t *out);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1422,7 +1481,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_MSM_BUCKET = 23, H2R_KERNEL_MSM_FOLD = 24 /* the commitments' two launches: msm_bucket_kernel, msm_fold_kernel */,
        H2R_KERNEL_CURVE_NTT_TWIDDLE = 25, H2R_KERNEL_CURVE_NTT_LOAD = 26, H2R_KERNEL_CURVE_NTT_STAGE = 27 /* one launch per stage */,
        H2R_KERNEL_CURVE_NTT_STORE = 28 /* h2r_curve_ntt's launches: the twiddle table, affine -> projective, the stages, projective -> affine */,
-       H2R_KERNEL_COUNT = 29 };
+       H2R_KERNEL_TRANSCRIPT = 29 /* transcript_kernel: one round of the Fiat-Shamir transcript */,
+       H2R_KERNEL_COUNT = 30 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
