@@ -180,6 +180,18 @@ class H2RTranscriptDerive(ctypes.Structure):
     _fields_ = [("src", ctypes.c_uint32), ("log2_pow", ctypes.c_uint32), ("mult", ctypes.c_uint64 * 4)]
 
 
+H2R_RANDOM_MAX_COLUMNS = 64
+
+
+class H2RRandomConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_cols", ctypes.c_uint32), ("row_begin", ctypes.c_uint64), ("row_end", ctypes.c_uint64),
+                ("first_circuit", ctypes.c_uint64), ("reserved", ctypes.c_uint64), ("seed", ctypes.c_uint8 * 32)]
+
+
+class H2RRandomColumn(ctypes.Structure):
+    _fields_ = [("base", ctypes.c_void_p), ("elem_stride", ctypes.c_uint64), ("tag", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -232,6 +244,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_msm_plan", "h2r_msm_workspace_bytes", "h2r_msm_columns", "h2r_curve_eval",
            "h2r_curve_ntt_workspace_bytes", "h2r_curve_ntt",
            "h2r_transcript_state_bytes", "h2r_transcript_round", "h2r_transcript_eval",
+           "h2r_random_columns", "h2r_random_eval",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -247,6 +260,7 @@ KERNEL_OPEN_TILES, KERNEL_OPEN_CARRY, KERNEL_OPEN_SCAN, KERNEL_FOLD = 19, 20, 21
 KERNEL_MSM_BUCKET, KERNEL_MSM_FOLD = 23, 24
 KERNEL_CURVE_NTT_TWIDDLE, KERNEL_CURVE_NTT_LOAD, KERNEL_CURVE_NTT_STAGE, KERNEL_CURVE_NTT_STORE = 25, 26, 27, 28
 KERNEL_TRANSCRIPT = 29
+KERNEL_RANDOM = 30
 FIELD_MUL, FIELD_TO_MONTGOMERY, FIELD_FROM_MONTGOMERY = 2, 6, 7   # h2r_field_eval's operations a * b, a * R and a * R^-1 mod p (include/h2r.h)
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
@@ -477,6 +491,8 @@ def lib():
     L.h2r_transcript_round.argtypes = [vp, ctypes.POINTER(H2RTranscriptConfig), ctypes.POINTER(H2RTranscriptItem), ctypes.POINTER(H2RTranscriptDerive),
                                        vp, u64, vp, vp, vp, u64, u64, vp, vp]
     L.h2r_transcript_eval.argtypes = [vp, u32, vp, ctypes.c_char_p, u64, pu64]
+    L.h2r_random_columns.argtypes = [vp, ctypes.POINTER(H2RRandomConfig), ctypes.POINTER(H2RRandomColumn), u64, vp]
+    L.h2r_random_eval.argtypes = [vp, ctypes.c_char_p, u64, u32, u64, pu64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.h2r_dist_destroy.argtypes = [vp]

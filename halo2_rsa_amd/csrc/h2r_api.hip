@@ -31,6 +31,7 @@
 #include "h2r_msm.hpp"
 #include "h2r_curve_ntt.hpp"
 #include "h2r_transcript.hpp"
+#include "h2r_random.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4457,7 +4458,7 @@ namespace {
 static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_OPEN_SCAN == H2R_KERNEL_OPEN_TILES + 2 &&
               H2R_KERNEL_MSM_BUCKET == H2R_KERNEL_FOLD + 1 && H2R_KERNEL_MSM_FOLD == H2R_KERNEL_MSM_BUCKET + 1 &&
               H2R_KERNEL_CURVE_NTT_TWIDDLE == H2R_KERNEL_MSM_FOLD + 1 && H2R_KERNEL_CURVE_NTT_STORE == H2R_KERNEL_CURVE_NTT_TWIDDLE + 3 &&
-              H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_TRANSCRIPT + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_RANDOM == H2R_KERNEL_TRANSCRIPT + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_RANDOM + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -4919,6 +4920,62 @@ int32_t h2r_transcript_eval(const h2r_ctx *ctx, uint32_t op, void *state, const 
         tr_canonical(kind, x, y, c);
         put(tr_encode(kind, x, y));
     }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the prover's randomness: a counter-based generator over the transcript's BLAKE2b (h2r_random.hpp, h2r_tu_random.hip) ----------------
+namespace {
+static_assert(H2R_RANDOM_MAX_COLUMNS == RND_MAX_COLUMNS && sizeof(h2r_random_config) == 72 && sizeof(h2r_random_column) == 24, "h2r.h and the kernel's argument struct");
+// the 32 seed bytes as the message's first four little-endian words
+void random_seed_words(const uint8_t *seed, u64 (&w)[4]) {
+    for (int k = 0; k < 4; ++k) {
+        w[k] = 0;
+        for (int b = 7; b >= 0; --b) w[k] = (w[k] << 8) | seed[8 * k + b];
+    }
+}
+}  // namespace
+
+int32_t h2r_random_columns(const h2r_ctx *ctx, const h2r_random_config *cfg, const h2r_random_column *cols, uint64_t batch, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !cols) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_random_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->num_cols == 0 || cfg->num_cols > RND_MAX_COLUMNS || cfg->reserved || cfg->row_end < cfg->row_begin || cfg->row_end > RND_MAX_ROW) return H2R_E_SHAPE;
+    for (u32 c = 0; c < cfg->num_cols; ++c)
+        if (!cols[c].base) return H2R_E_NULL;
+    if (batch == 0 || cfg->first_circuit + (batch - 1) < cfg->first_circuit) return H2R_E_SHAPE;   // the last circuit's index fits 64 bits
+    const u64 count = cfg->row_end - cfg->row_begin;
+    for (u32 c = 0; c < cfg->num_cols; ++c)
+        if (cols[c].reserved || misaligned(cols[c].base, cols[c].elem_stride) || (cols[c].elem_stride && cols[c].elem_stride < 32 * count)) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_SHAPE;                       // no wide-reduce constants for this field
+    if (count == 0) return H2R_OK;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    RandomArgs ra;
+    std::memset(static_cast<void *>(&ra), 0, sizeof ra);
+    for (u32 c = 0; c < cfg->num_cols; ++c) ra.cols[c] = RndColumn{static_cast<u8 *>(cols[c].base), cols[c].elem_stride, cols[c].tag, 0};
+    random_seed_words(cfg->seed, ra.seed);
+    ra.row_begin = cfg->row_begin; ra.row_count = count; ra.first_circuit = cfg->first_circuit;
+    ra.c = transcript_consts(ctx, *cv);
+    // slices of row tiles (grid.x), then of circuits (grid.z); the columns are grid.y
+    const u64 tiles = (count + RND_LANES - 1) / RND_LANES, tiles_per = slice_items(cfg->num_cols, tiles), elems_per = slice_items(tiles_per * cfg->num_cols, batch);
+    if (!tiles_per || !elems_per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return for_each_slice(batch, elems_per, [&](u64 e0, u64 ne) {
+        return for_each_slice(tiles, tiles_per, [&](u64 t0, u64 nt) {
+            ra.elem0 = e0; ra.tile0 = t0;
+            return stage_launch(H2R_KERNEL_RANDOM, st, [&](hipEvent_t a, hipEvent_t b) { return launch_random(ra, (u32)nt, cfg->num_cols, (u32)ne, st, a, b); });
+        });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_random_eval(const h2r_ctx *ctx, const uint8_t seed[32], uint64_t circuit, uint32_t tag, uint64_t row, uint64_t out[4]) try {
+    if (!ctx || !seed || !out) return H2R_E_NULL;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_SHAPE;
+    u64 sw[4], block[RND_MSG_WORDS];
+    random_seed_words(seed, sw);
+    const Fe x = rnd_element(sw, circuit, tag, row, TrBlock{block, 1}, transcript_consts(ctx, *cv));
+    for (int k = 0; k < 4; ++k) out[k] = x.v[k];
     return H2R_OK;
 } H2R_CATCH_STATUS
 

@@ -15,6 +15,7 @@
 //   h2r_tu_msm.hip     the commitments: multi-scalar multiplications over the curve of the ctx's field (h2r_msm.hpp, h2r_curve.hpp)
 //   h2r_tu_curve_ntt.hip   the Lagrange-basis commitment key: the transform over the curve's points (h2r_curve_ntt.hpp, h2r_curve.hpp)
 //   h2r_tu_transcript.hip   the Fiat-Shamir transcript: one round of a batch of BLAKE2b states per launch (h2r_transcript.hpp)
+//   h2r_tu_random.hip  the prover's blinding values: a counter-based generator over the transcript's BLAKE2b (h2r_random.hpp)
 //   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
@@ -148,5 +149,9 @@ hipError_t launch_curve_ntt(u32 phase, const CurveNttArgs &a, u32 num_blocks, hi
 // h2r_tu_transcript.hip (argument struct: h2r_transcript.hpp).  One round of the workgroups [a.block0, a.block0 + num_blocks) of 64 circuits.
 struct TranscriptArgs;
 hipError_t launch_transcript(const TranscriptArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_random.hip (argument struct: h2r_random.hpp).  The row tiles [a.tile0, a.tile0 + num_tiles) of num_cols columns of the circuits
+// [a.elem0, a.elem0 + num_elems).
+struct RandomArgs;
+hipError_t launch_random(const RandomArgs &a, u32 num_tiles, u32 num_cols, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

@@ -1,9 +1,10 @@
 """The prover stages on the device: halo2's lookup and permutation arguments, the evaluation domain (transforms, quotient, openings) and
-the commitment key, and the Fiat-Shamir transcript that joins them.  None of them has a counterpart in the reference's `big_integer`
+the commitment key, the Fiat-Shamir transcript that joins them, the generator of the blinding values, and create_proof, which runs them in halo2's order.  None of them has a counterpart in the reference's `big_integer`
 module; `big_integer` re-exports the five classes.
 All arithmetic happens in libh2r.so; every method marshals its arguments with `_marshal` and makes the call.
 A chip is whatever has `_ctx`, `_stream()`, `device` and `montgomery` (big_integer.BigIntChip)."""
 import ctypes
+import os
 from typing import Optional, Sequence
 
 import numpy as np
@@ -459,6 +460,29 @@ class CommitKey:
         return key
 
 
+def random_columns(chip: "BigIntChip", columns, tags: Sequence[int], rows, seed: bytes, first_circuit: int = 0) -> None:
+    """Fills rows [rows[0], rows[1]) of every column with uniform field elements drawn from `seed` (h2r_random_columns; DESIGN.md section
+    2m): element(seed, circuit, tag, row) = BLAKE2b-512(person "H2R-Blinding-v1\\0", seed | le64(circuit) | le32(tag) | le32(0) | le64(row))
+    as a little-endian integer modulo r, in the chip's representation -- the same values whatever the representation and however a batch
+    or a row range is cut into calls.  columns: up to 64 tensors uint8 [batch, n, 32] (circuit e draws with index first_circuit + e), or
+    [n, 32] for a column the batch shares (drawn once, with index first_circuit), last two dimensions contiguous; tags: one integer per
+    column (the caller's table of column kinds); seed: 32 bytes, passed by value.  Nothing but the named rows is written; the columns'
+    ranges are the caller's to keep apart.  Only a chip whose field has a curve (bn254_fr)."""
+    columns, tags, (row_begin, row_end) = list(columns), list(tags), rows
+    if not 0 < len(columns) <= _lib.H2R_RANDOM_MAX_COLUMNS or len(tags) != len(columns) or len(seed) != 32 or not 0 <= row_begin <= row_end:
+        check(_lib.H2R_E_SHAPE, "random_columns")
+    batch = next((int(t.shape[0]) for t in columns if t.dim() == 3), 1)
+    cfg = _lib.H2RRandomConfig(struct_size=ctypes.sizeof(_lib.H2RRandomConfig), num_cols=len(columns), row_begin=row_begin, row_end=row_end,
+                               first_circuit=first_circuit, reserved=0)
+    cfg.seed[:] = bytes(seed)
+    desc = (_lib.H2RRandomColumn * len(columns))()
+    for d, t, tag in zip(desc, columns, tags):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and is_columns(t, dims=(2, 3), batch=batch) and t.shape[-2] >= row_end):
+            check(_lib.H2R_E_SHAPE, "random_columns")     # (no assert: a column shorter than row_end must never reach the kernel)
+        (d.base, d.elem_stride, _), d.tag = column_group(t, t.dim() == 3), int(tag)
+    check(lib().h2r_random_columns(chip._ctx, ctypes.byref(cfg), desc, batch, chip._stream()), "h2r_random_columns")
+
+
 class Transcript:
     """halo2's Fiat-Shamir transcript for a batch of circuits on the device (h2r_transcript_round):
     `Blake2bWrite<_, G1Affine, Challenge255<_>>`, one launch per round, no host synchronisation between the stages.  Owns the per-circuit
@@ -549,3 +573,153 @@ class Transcript:
     def proof(self) -> torch.Tensor:
         """uint8 [batch, offset]: the proof bytes written so far (a view of the buffer)."""
         return self.buffer[:, :self.offset]
+
+
+# column kind x index of the generator's tags: tag = kind * 256 + index (DESIGN.md section 2m)
+TAG_ADVICE, TAG_LOOKUP_A_PERM, TAG_LOOKUP_S_PERM, TAG_PERM_Z, TAG_LOOKUP_Z, TAG_RANDOM_POLY = (kind * 256 for kind in range(6))
+
+
+class ProvingKey:
+    """What create_proof needs of one circuit shape, built once and held on the device: the domain, the monomial and
+    the Lagrange CommitKey, the fixed and sigma columns in Lagrange, coefficient and extended form, vanishing_columns, the row kinds, the
+    lookup, permutation and quotient configurations, first_row, the image's rows, the number of h pieces and the caller's vk_repr.
+    fixed: uint8 [F, 2^k, 32], sigma: uint8 [m, 2^k, 32], Lagrange form, the chip's representation; kinds: the image's row kinds; delta and
+    vk_repr: integers in the chip's representation (this library derives neither sigma nor vk_repr).  commit_key: the monomial key, at
+    least 2^k bases; lagrange_key: dom.lagrange_key(commit_key) when None."""
+
+    def __init__(self, chip, dom: EvaluationDomain, commit_key: CommitKey, la: LookupArgument, fixed: torch.Tensor, sigma: torch.Tensor, kinds,
+                 blinding_factors: int, delta: int, gate_fixed: Sequence[int], column_src: Sequence[int], chunk_len: int, lookup_advice: Sequence[int],
+                 lookup_tag: Sequence[int], lookup_enable: Sequence[int], table_tag: int, table_value: int, vk_repr: int, first_row: int = 0,
+                 lookup_mask: int = 31, h_pieces: int = 4, lagrange_key: Optional[CommitKey] = None):
+        n = 1 << dom.k
+        dev = fixed.device
+        if (h_pieces != 4 or dom.extended_k != dom.k + 3 or commit_key.n < n or not is_columns(fixed, rows=n, dims=(3,)) or not is_columns(sigma, rows=n, dims=(3,))
+                or sigma.shape[0] != len(column_src) or any(int(s) >= 5 for s in column_src) or n - blinding_factors - 1 < 1):
+            check(_lib.H2R_E_SHAPE, "ProvingKey")     # (four pieces: the constraint system's degree 5 at extended_k = k + 3; no extra columns)
+        self.chip, self.dom, self.la, self.n, self.u, self.blinding_factors = chip, dom, la, n, n - blinding_factors - 1, int(blinding_factors)
+        self.ck = commit_key if commit_key.n == n else CommitKey(chip, commit_key.bases[:n])
+        self.lk = lagrange_key if lagrange_key is not None else dom.lagrange_key(self.ck)
+        self.delta, self.gate_fixed, self.column_src, self.chunk_len = int(delta), list(gate_fixed), list(column_src), int(chunk_len)
+        self.lookup = dict(lookup_mask=lookup_mask, lookup_advice=list(lookup_advice), lookup_tag=list(lookup_tag), lookup_enable=list(lookup_enable),
+                           table_tag=int(table_tag), table_value=int(table_value))
+        self.lookup_args = [a for a in range(LookupArgument.ARGS) if (lookup_mask >> a) & 1]
+        if self.lookup_args != list(range(LookupArgument.ARGS)):
+            check(_lib.H2R_E_SHAPE, "ProvingKey")     # (the lookup stages' wrappers pack all five arguments)
+        self.pa = PermutationArgument(chip, column_src, chunk_len, delta, dom.omega)
+        self.h_pieces, self.first_row = int(h_pieces), int(first_row)
+        self.kinds = kinds_tensor(kinds, dev)
+        self.rows = int(self.kinds.numel())
+        self.fixed_lag, self.sigma_lag = fixed, sigma
+        self.fixed_coeff, self.sigma_coeff = dom.lagrange_to_coeff(fixed), dom.lagrange_to_coeff(sigma)
+        self.fixed_ext, self.sigma_ext = dom.coeff_to_extended(self.fixed_coeff), dom.coeff_to_extended(self.sigma_coeff)
+        self.l_ext = dom.vanishing_columns(blinding_factors)
+        self.vk = challenges([vk_repr], dev)
+        # x * omega, x * omega^-(blinding_factors + 1), x * omega^-1 and x^n: the derived values of the round that draws x
+        mont = chip.montgomery
+        w = dom._field(_lib.FIELD_FROM_MONTGOMERY, dom.omega) if mont else dom.omega
+        wi = dom._field(3, w)
+        wl = wi
+        for _ in range(blinding_factors):
+            wl = dom._field(_lib.FIELD_MUL, wl, wi)
+        rep = (lambda v: dom._field(_lib.FIELD_TO_MONTGOMERY, v)) if mont else (lambda v: v)
+        self.derive = [(0, dom.omega, 0), (0, rep(wl), 0), (0, rep(wi), 0), (0, dom.one, dom.k)]
+        # the evaluations in transcript order and the GWC query list: (group, index, point mask); point sets x, omega x, omega^-(bf+1) x, omega^-1 x
+        S, A = self.pa.sets, self.lookup_args
+        adv = [("advice", c, 3 if c == 4 else 1) for c in range(5)]
+        fx, sg = [("fixed", i, 1) for i in range(fixed.shape[0])], [("sigma", c, 1) for c in range(sigma.shape[0])]
+        pz = [("perm_z", s, 3 | (4 if s < S - 1 else 0)) for s in range(S)]
+        lk = [q for a in A for q in (("lookup_z", a, 3), ("lookup_a_perm", a, 9), ("lookup_s_perm", a, 1))]
+        self.eval_plan = adv + fx + [("random", 0, 1)] + sg + pz + lk
+        self.open_plan = adv + pz + lk + fx + sg + [("h", 0, 1), ("random", 0, 1)]
+        self.num_evals = sum(bin(m).count("1") for _, _, m in self.eval_plan)
+        self.proof_bytes = 32 * (5 + 2 * len(A) + S + len(A) + 1 + self.h_pieces + self.num_evals + 4)
+
+
+def create_proof(key: ProvingKey, image: torch.Tensor, batch: int, seed: Optional[bytes] = None, instances: Optional[torch.Tensor] = None,
+                 group: Optional[int] = None):
+    """(proof uint8 [batch, key.proof_bytes], status uint8 [batch]): `batch` independent one-circuit proofs, each with its own transcript
+    (unlike upstream's several circuits under one transcript), from the advice image to the proof bytes with no host synchronisation in
+    between (DESIGN.md section 2m holds the round order).  image: the chip's advice image of key.rows rows per circuit, [batch, bytes];
+    a planar image with col_stride = 2^k * 32 IS the advice columns and gets its rows u..n written in place.  seed: 32 bytes, os.urandom(32)
+    when None -- A SEED REUSED WITH ANOTHER WITNESS REUSES THE BLINDING.  instances: int64 [batch, I, 4] on the device, absorbed as common
+    scalars.  group: how many circuits' columns are alive at once (the whole batch when None); circuit e always draws with index e, so the
+    proofs do not depend on it.  One status is threaded through every stage: a circuit that a stage flags is skipped by the later ones and
+    ends with its code (H2R_E_ASSERTION where a grand product does not close: the image does not satisfy the circuit)."""
+    chip, dom, la, n, u = key.chip, key.dom, key.la, key.n, key.u
+    seed = os.urandom(32) if seed is None else bytes(seed)
+    if batch < 1 or len(seed) != 32 or image.dim() != 2 or image.shape[0] != batch or (group is not None and group < 1):
+        check(_lib.H2R_E_SHAPE, "create_proof")
+    dev, A, S, fr, rows, N = image.device, len(key.lookup_args), key.pa.sets, key.first_row, key.rows, 1 << dom.extended_k
+    planar = bool(getattr(chip, "columns", False))
+    if (planar and (image.shape[1] != 5 * n * 32 or getattr(chip, "col_stride", 0) != n * 32)) or (not planar and image.shape[1] != rows * 160) or fr + rows > u:
+        check(_lib.H2R_E_SHAPE, "create_proof")
+    proof = torch.zeros((batch, key.proof_bytes), dtype=torch.uint8, device=dev)
+    status = torch.zeros(batch, dtype=torch.uint8, device=dev)
+    group = batch if group is None else min(int(group), batch)
+
+    def zeros(*shape):
+        return torch.zeros(shape + (32,), dtype=torch.uint8, device=dev)
+
+    def split(t):
+        return [t[:, c] for c in range(t.shape[1])]
+
+    def tags(base, count):
+        return [base + i for i in range(count)]
+
+    for g0 in range(0, batch, group):
+        B = min(group, batch - g0)
+        img, st = image[g0:g0 + B], status[g0:g0 + B]
+        tr = Transcript(chip, B, key.proof_bytes)
+        # 1. the verifying key and the instances
+        tr.round([(key.vk, tr.SCALAR)] + ([(instances[g0:g0 + B], tr.SCALAR)] if instances is not None and instances.shape[1] else []), common=True, status=st)
+        # 2. advice: rows u..n from the generator, committed in Lagrange form; theta
+        if planar:
+            adv = img.view(B, 5, n, 32)
+        else:
+            adv = zeros(B, 5, n)
+            adv[:, :, fr:fr + rows] = img.view(B, rows, 5, 32).permute(0, 2, 1, 3)
+        random_columns(chip, split(adv), tags(TAG_ADVICE, 5), (u, n), seed, first_circuit=g0)
+        theta = tr.write_points(key.lk.commit(split(adv), status=st), squeeze=1, status=st)[0][:, 0]
+        # 3. the lookups' A' and S'; beta, gamma
+        hist = la.hist_advice(key.kinds, img, B, la.new_hist(B), status=st)
+        a_perm, s_perm, st_perm = la.permuted_columns(hist, theta, u)
+        st.copy_(torch.where(st == 0, st_perm, st))
+        a_in = la.input_columns(key.kinds, img, B, theta, u, status=st, first_row=fr)
+        AP, SP = zeros(B, la.ARGS, n), zeros(B, la.ARGS, n)
+        AP[:, :, :u], SP[:, :, :u] = a_perm, s_perm
+        random_columns(chip, split(AP) + split(SP), tags(TAG_LOOKUP_A_PERM, A) + tags(TAG_LOOKUP_S_PERM, A), (u, n), seed, first_circuit=g0)
+        pairs = [t[:, a] for a in range(A) for t in (AP, SP)]
+        bg = tr.write_points(key.lk.commit(pairs, status=st), squeeze=2, status=st)[0]
+        beta, gamma = bg[:, 0], bg[:, 1]
+        # 4. both families of Z and the random polynomial; y
+        PZ, LZ, RP = zeros(B, S, n), zeros(B, la.ARGS, n), zeros(B, n)
+        key.pa.product_columns(img, B, rows, key.sigma_lag, beta, gamma, u, first_row=fr, out=(PZ, st))
+        lz, _ = la.product_columns(a_in, a_perm, s_perm, theta, beta, gamma, u, out=(zeros(B, la.ARGS, u + 1), st))
+        LZ[:, :, :u + 1] = lz
+        random_columns(chip, split(PZ) + split(LZ), tags(TAG_PERM_Z, S) + tags(TAG_LOOKUP_Z, A), (u + 1, n), seed, first_circuit=g0)
+        random_columns(chip, [RP], [TAG_RANDOM_POLY], (0, n), seed, first_circuit=g0)
+        y = tr.round([(key.lk.commit(split(PZ) + split(LZ), status=st), tr.POINT), (key.ck.commit([RP], status=st), tr.POINT)], squeeze=1, status=st)[0][:, 0]
+        # 5. the quotient and its pieces; x, its rotations and x^n
+        coeff = {name: dom.lagrange_to_coeff(t) for name, t in (("advice", adv), ("perm_z", PZ), ("lookup_a_perm", AP), ("lookup_s_perm", SP), ("lookup_z", LZ))}
+        ext = {name: dom.coeff_to_extended(t) for name, t in coeff.items()}
+        h, _ = dom.quotient(key.blinding_factors, key.delta, key.gate_fixed, key.column_src, key.chunk_len, ext["advice"], ext["perm_z"], key.fixed_ext,
+                            key.sigma_ext, key.l_ext, theta, beta, gamma, y, lookup_a_perm=ext["lookup_a_perm"], lookup_s_perm=ext["lookup_s_perm"],
+                            lookup_z=ext["lookup_z"], out=(zeros(B, N), st), **key.lookup)
+        del ext
+        pieces = dom.extended_to_coeff(h)[:, :key.h_pieces * n].unflatten(1, (key.h_pieces, n))
+        xs, dv = tr.write_points(key.ck.commit(split(pieces), status=st), squeeze=1, derive=key.derive, status=st)
+        points, xn = torch.cat([xs, dv[:, :3]], dim=1), dv[:, 3]
+        # 6. the evaluations, in transcript order; v
+        coeff["random"], coeff["fixed"], coeff["sigma"] = RP.unsqueeze(1), key.fixed_coeff, key.sigma_coeff
+        coeff["h"] = dom.fold(pieces, xn, out=(zeros(B, n), st))[0].unsqueeze(1)
+
+        def columns(plan):
+            return [(coeff[g][i] if g in ("fixed", "sigma") else coeff[g][:, i], mask) for g, i, mask in plan]
+
+        evals, _ = dom.open_eval(columns(key.eval_plan), points, out=(torch.zeros((B, key.num_evals, 4), dtype=torch.int64, device=dev), st))
+        v = tr.write_scalars(evals, squeeze=1, status=st)[0][:, 0]
+        # 7. the GWC witness polynomials
+        W, _, _ = dom.open_witness(columns(key.open_plan), points, v, out=(zeros(B, 4, n), torch.zeros((B, 4, 4), dtype=torch.int64, device=dev), st))
+        tr.write_points(key.ck.commit(split(W), status=st), status=st)
+        proof[g0:g0 + B] = tr.proof()
+    return proof, status

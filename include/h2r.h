@@ -1180,6 +1180,40 @@ int32_t h2r_transcript_round(const h2r_ctx *ctx, const h2r_transcript_config *cf
                              const h2r_transcript_derive *derive, void *states, uint64_t batch, uint64_t *challenges, uint64_t *derived,
                              void *proof, uint64_t proof_stride, uint64_t proof_off, uint8_t *status, h2r_stream_t stream);
 int32_t h2r_transcript_eval(const h2r_ctx *ctx, uint32_t op, void *state, const uint8_t *in, uint64_t in_len, uint64_t *out);
+/* ---- the prover's randomness: uniform field elements from a seed, on the device ------------------
+ * halo2 fills the unusable rows of every advice, A', S' and Z column with random scalars and commits to a random polynomial per proof;
+ * here those values come from a COUNTER-BASED generator, so that every element is a pure function of
+ * (seed, circuit, tag, row), a proof is reproducible from its seed, and the result does not depend on how a batch or a row range is cut
+ * into calls:
+ *     element(seed, circuit, tag, row) = reduce_wide( BLAKE2b-512( person = "H2R-Blinding-v1\0",
+ *                                           msg = seed[32] | le64(circuit) | le32(tag) | le32(0) | le64(row) ) )
+ * BLAKE2b (RFC 7693) with a 64-byte digest, no key, no salt, that 16-byte personalisation, pinned byte for byte against Python's hashlib
+ * (tests/create_proof_ref.py); the message is 56 bytes, one compression per element.  reduce_wide reads the 64 digest bytes as a
+ * little-endian 512-bit integer and reduces it modulo r, as the transcript's challenges (above) and Fr::random's from_bytes_wide do.
+ * The value is stored in the ctx's representation: one seed gives the same VALUES on a canonical and on a Montgomery ctx.
+ * h2r_random_columns writes the rows [row_begin, row_end) of every named column of every circuit, and nothing else:
+ *  - cols: a host array of cfg->num_cols (1..64) descriptors; row i of circuit e of a column lies at base + e * elem_stride + i * 32 on the
+ *    device and is drawn with circuit index first_circuit + e and the column's tag (the caller's table of column kinds).  elem_stride = 0
+ *    is a column the batch shares: it is written once, with circuit index first_circuit.  The named ranges are the caller's to keep apart.
+ *  - cfg->seed is held by value: it travels in the kernel arguments and never lies in device memory.
+ *  - One launch per call (sliced internally below the 2^32 global size), one lane per element, grid (row tile of 256, column, circuit),
+ *    enqueued on `stream`, never synchronising; no workgroup waits for another.  An empty row range is success with no launch.
+ *  - H2R_E_NULL for a NULL ctx, cfg, cols or column base; H2R_E_UNSUPPORTED for another struct_size or a host-only ctx (that one after every
+ *    other check, and after the empty range's success); H2R_E_SHAPE for num_cols = 0 or > 64, row_end < row_begin, row_end > 2^58, a nonzero
+ *    `reserved` (the config's or a column's), batch = 0, a last circuit index first_circuit + batch - 1 above 2^64 - 1, a base or stride that is not 16-byte aligned, a
+ *    nonzero elem_stride smaller than the rows written, and a ctx whose field has no wide-reduce constants (the fields the transcript
+ *    serves: those with a curve).
+ *  - h2r_random_eval (host only; works on a host-only ctx) runs for ONE element the very functions the kernel inlines: out[4] = the
+ *    element in the ctx's representation.  Any circuit, tag and row; H2R_E_SHAPE for a field without wide-reduce constants. */
+#define H2R_RANDOM_MAX_COLUMNS 64
+typedef struct h2r_random_config {
+    uint32_t struct_size, num_cols;
+    uint64_t row_begin, row_end, first_circuit, reserved;
+    uint8_t seed[32];
+} h2r_random_config;
+typedef struct h2r_random_column { void *base; uint64_t elem_stride; uint32_t tag, reserved; } h2r_random_column;
+int32_t h2r_random_columns(const h2r_ctx *ctx, const h2r_random_config *cfg, const h2r_random_column *cols, uint64_t batch, h2r_stream_t stream);
+int32_t h2r_random_eval(const h2r_ctx *ctx, const uint8_t seed[32], uint64_t circuit, uint32_t tag, uint64_t row, uint64_t out[4]);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1482,7 +1516,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_CURVE_NTT_TWIDDLE = 25, H2R_KERNEL_CURVE_NTT_LOAD = 26, H2R_KERNEL_CURVE_NTT_STAGE = 27 /* one launch per stage */,
        H2R_KERNEL_CURVE_NTT_STORE = 28 /* h2r_curve_ntt's launches: the twiddle table, affine -> projective, the stages, projective -> affine */,
        H2R_KERNEL_TRANSCRIPT = 29 /* transcript_kernel: one round of the Fiat-Shamir transcript */,
-       H2R_KERNEL_COUNT = 30 };
+       H2R_KERNEL_RANDOM = 30 /* random_kernel: the prover's blinding values */,
+       H2R_KERNEL_COUNT = 31 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
