@@ -1,4 +1,5 @@
-// C ABI of libh2r (see include/h2r.h).  Host side: context, layouts, kernel launches, flatten.
+// C ABI of libh2r (see include/h2r.h).  Host code only: context, layouts, checks and argument structs, flatten, the host twins.  Every
+// kernel is defined and launched in a unit of its family, behind a launch_* of h2r_internal.hpp.
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <dlfcn.h>
@@ -16,7 +17,6 @@
 #include <new>
 #include <vector>
 
-#define H2R_TU_API 1   // this unit defines the plain kernels of the shared headers
 #include "h2r.h"
 #include "h2r_internal.hpp"
 #include "h2r_varrows.hpp"
@@ -85,7 +85,7 @@ u32 g_prof_cap = 0;
 u32 g_prof_gen = 0;   // bumped whenever the recorded events are destroyed (h2r_profile_enable)
 struct ProfScope {  // start/stop events of one launch when profiling is armed
     // ext == false: the events are recorded around the launch (two marker packets on the stream).
-    // ext == true:  the caller hands a/b to hipExtLaunchKernelGGL, which stamps them from the dispatch packet's own
+    // ext == true:  the caller hands a/b to a launch_* whose launch takes events and stamps them from the dispatch packet's own
     //               completion signal -- no extra packets (each marker costs ~5 us of queue time between kernels).
     hipStream_t st; hipEvent_t a = nullptr, b = nullptr; u32 kernel; bool on = false, ext;
     ProfScope(u32 k, hipStream_t s, bool ext_ = false) : st(s), kernel(k), ext(ext_) {
@@ -624,6 +624,24 @@ int32_t verify_layout(const h2r_ctx *ctx, const Exponent &e, h2r_verify_layout *
     return H2R_OK;
 }
 
+// The address ranges of regions that were unmapped.  They are RETIRED, not given back with hipMemAddressFree: a range that is freed and
+// then reserved and mapped again -- by the look's next candidate, by the next arena -- was seen to keep its old translation on the device
+// for a while.  Records written into the new region then went to the old, released chunks, and the region read back as the zero fill or the
+// look had left it: 33 of 40 small arenas created and closed in turn lost records of a call that way, 0 of 40 with the ranges retired
+// (5 of 40 when the physical chunks were kept and the range reused).  An unmapped reservation costs address space only; if a reservation
+// fails, the retired ranges are given back and it is tried once more.
+struct RetiredRanges {
+    std::mutex mu;
+    std::vector<std::pair<void *, size_t>> ranges;
+    void add(void *va, size_t bytes) { std::lock_guard<std::mutex> lk(mu); ranges.emplace_back(va, bytes); }
+    void give_back() {
+        std::lock_guard<std::mutex> lk(mu);
+        for (auto &r : ranges) (void)hipMemAddressFree(r.first, r.second);
+        ranges.clear();
+    }
+};
+RetiredRanges &retired_ranges() { static RetiredRanges r; return r; }
+
 }  // namespace
 
 extern "C" {
@@ -658,9 +676,8 @@ int32_t h2r_key_table_expand(const h2r_ctx *ctx, const void *table, uint64_t num
     if (digits >= (1ull << 39)) return H2R_E_UNSUPPORTED;   // (the grid is 32-bit)
     const KeyTablePlan t = key_table_plan(ctx, num_keys);
     H2R_ON_DEVICE(ctx->params.device);
-    hipLaunchKernelGGL(key_expand_kernel, dim3((unsigned)((digits + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const u32 *>(table), t.raw_stride, (u32)num_keys, key_idx, batch, ctx->K, static_cast<u32 *>(n_out));
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_key_expand(static_cast<const u32 *>(table), t.raw_stride, (u32)num_keys, key_idx, batch, ctx->K, static_cast<u32 *>(n_out),
+                              static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -1042,23 +1059,6 @@ struct h2r_arena {
 };
 
 namespace {
-// The address ranges of regions that were unmapped.  They are RETIRED, not given back with hipMemAddressFree: a range that is freed and
-// then reserved and mapped again -- by the look's next candidate, by the next arena -- was seen to keep its old translation on the device
-// for a while.  Records written into the new region then went to the old, released chunks, and the region read back as the zero fill or the
-// look had left it: 33 of 40 small arenas created and closed in turn lost records of a call that way, 0 of 40 with the ranges retired
-// (5 of 40 when the physical chunks were kept and the range reused).  An unmapped reservation costs address space only; if a reservation
-// fails, the retired ranges are given back and it is tried once more.
-struct RetiredRanges {
-    std::mutex mu;
-    std::vector<std::pair<void *, size_t>> ranges;
-    void add(void *va, size_t bytes) { std::lock_guard<std::mutex> lk(mu); ranges.emplace_back(va, bytes); }
-    void give_back() {
-        std::lock_guard<std::mutex> lk(mu);
-        for (auto &r : ranges) (void)hipMemAddressFree(r.first, r.second);
-        ranges.clear();
-    }
-};
-RetiredRanges &retired_ranges() { static RetiredRanges r; return r; }
 hipError_t arena_reserve(void **va, size_t bytes) {
     hipError_t e = hipMemAddressReserve(va, bytes, 0, nullptr, 0);
     if (e != hipSuccess) {
@@ -1075,28 +1075,6 @@ void arena_free_region(h2r_arena::Region &r) {
     for (auto h : r.handles) (void)hipMemRelease(h);
     if (r.va) retired_ranges().add(r.va, r.mapped);   // (not hipMemAddressFree: see RetiredRanges)
     r.va = nullptr; r.handles.clear(); r.n_mapped = 0;
-}
-// a streaming fill in the product kernels' store pattern (16 bytes per lane, non-temporal, whole 4 KB runs per workgroup step,
-// XCD-contiguous blocks): what h2r_image_arena_create times on a candidate region
-__global__ __launch_bounds__(256) void arena_fill_kernel(u8 *p, u64 bytes) {
-    const u64 per_block = 64ull << 10;
-    const u64 b = xcd_contiguous_block(blockIdx.x, gridDim.x);
-    u8 *q = p + b * per_block;
-    const u64 n = bytes - b * per_block < per_block ? bytes - b * per_block : per_block;
-    for (u64 o = (u64)threadIdx.x * 16; o + 16 <= n; o += 4096) st16(q + o, 0x0123456789abcdefull ^ o, b);
-}
-// h2r_arena_restore_constants: the constant planes of every record slot of a region, from the constant record (4 bytes per thread and step;
-// every plane starts on a 16-byte boundary of the record and is a whole number of words)
-struct ArenaConstPlanes { u64 off[7]; u32 bytes[7]; };
-__global__ __launch_bounds__(256) void arena_restore_kernel(u8 *base, u64 elem_stride, u64 off_records, u64 record_stride, u32 T, u64 n_records,
-                                                            const u8 *cr, ArenaConstPlanes pl) {
-    for (u64 k = blockIdx.x; k < n_records; k += gridDim.x) {
-        const u64 elem = k / T, t = k - elem * T;
-        u8 *rec = base + elem * elem_stride + off_records + t * record_stride;
-        for (int p = 0; p < 7; ++p)
-            for (u32 o = threadIdx.x * 4; o < pl.bytes[p]; o += 256 * 4)
-                *reinterpret_cast<u32 *>(rec + pl.off[p] + o) = *reinterpret_cast<const u32 *>(cr + pl.off[p] + o);
-    }
 }
 using ArenaMeasure = std::function<int32_t(void *va, hipStream_t st, hipEvent_t ea, hipEvent_t eb, float *ms)>;
 int32_t arena_build(const h2r_ctx *ctx, u64 region_bytes, uint32_t regions, uint32_t candidates, uint64_t max_look_bytes, hipStream_t st,
@@ -1323,9 +1301,8 @@ int32_t h2r_arena_restore_constants(h2r_arena *a, uint32_t region, h2r_stream_t 
     for (int k = 0; k < 7; ++k) { pl.off[k] = a->const_off[k]; pl.bytes[k] = a->const_bytes[k]; }
     const u64 n_records = a->batch * a->records_per_elem;   // < 2^32 (h2r_arena_create_ex)
     const unsigned grid = (unsigned)std::min<u64>(n_records, 1u << 16);
-    hipLaunchKernelGGL(arena_restore_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<u8 *>(a->kept[region].va),
-                       a->elem_stride, a->first_record_off, a->record_stride, a->records_per_elem, n_records, a->const_rec, pl);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_arena_restore(grid, static_cast<u8 *>(a->kept[region].va), a->elem_stride, a->first_record_off, a->record_stride, a->records_per_elem,
+                                 n_records, a->const_rec, pl, static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -1340,11 +1317,9 @@ int32_t h2r_image_arena_create(const h2r_ctx *ctx, uint64_t region_bytes, uint32
     if (!regions || candidates < regions || region_bytes < (1ull << 20) || (region_bytes >> 16) >= (1ull << 31)) return H2R_E_SHAPE;
     H2R_ON_DEVICE(ctx->params.device);
     const ArenaMeasure measure = [&](void *va, hipStream_t s2, hipEvent_t ea, hipEvent_t eb, float *ms_out) -> int32_t {
-        const unsigned blocks = (unsigned)((region_bytes + (64ull << 10) - 1) >> 16);
         float sum = 0.f;
         for (int rep = 0; rep < 3; ++rep) {
-            hipExtLaunchKernelGGL(arena_fill_kernel, dim3(blocks), dim3(256), 0, s2, ea, eb, 0, static_cast<u8 *>(va), region_bytes);
-            if (!hip_ok(hipGetLastError(), "arena_fill_kernel") || !hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
+            if (!hip_ok(launch_arena_fill(static_cast<u8 *>(va), region_bytes, s2, ea, eb), "arena_fill_kernel") || !hip_ok(hipStreamSynchronize(s2), "hipStreamSynchronize")) return H2R_E_HIP;
             float ms = 0.f;
             if (!hip_ok(hipEventElapsedTime(&ms, ea, eb), "hipEventElapsedTime")) return H2R_E_HIP;
             if (rep) sum += ms;
@@ -1378,13 +1353,6 @@ void h2r_arena_destroy(h2r_arena *a) try {
 } H2R_CATCH_VOID
 
 // ---- the pow path and the pipeline that overlaps its calls: helpers first, then the exports ---------------------------------
-namespace {
-__global__ void queue_probe_kernel(unsigned long long ticks, unsigned long long *stamp) {   // one wave that holds its queue for `ticks` of the 100 MHz wall clock
-    const unsigned long long t0 = wall_clock64();
-    while (wall_clock64() - t0 < ticks) __builtin_amdgcn_s_sleep(8);
-    if (stamp && threadIdx.x == 0) { stamp[0] = t0; stamp[1] = wall_clock64(); }   // when it ran, on the device's own clock
-}
-}  // namespace
 extern "C++" {
 namespace {
 // Which calls are issued as one-launch steps: the shape both roles of step_kernel are built for (RSA-2048: 64-bit limbs,
@@ -1457,8 +1425,8 @@ bool pipeline_three_queues(h2r_pipeline *p, hipStream_t st, bool force = false) 
     if (hipHostMalloc(reinterpret_cast<void **>(&stamps), 6 * sizeof(unsigned long long), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); stamps = nullptr; }
     for (int rep = 0; rep < 4; ++rep) {                           // (the first round also loads the kernel; the best of the other three counts)
         const auto t0 = std::chrono::steady_clock::now();
-        for (int k = 0; k < 3; ++k) hipLaunchKernelGGL(queue_probe_kernel, dim3(1), dim3(64), 0, ss[k], spin_ticks, stamps ? stamps + 2 * k : nullptr);
-        bool ok = hipGetLastError() == hipSuccess;
+        bool ok = true;
+        for (int k = 0; k < 3; ++k) ok = (launch_queue_probe(spin_ticks, stamps ? stamps + 2 * k : nullptr, ss[k]) == hipSuccess) && ok;
         for (hipStream_t s : ss) ok = (hipStreamSynchronize(s) == hipSuccess) && ok;
         if (!ok) { (void)hipGetLastError(); if (stamps) (void)hipHostFree(stamps); return false; }
         const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -1634,13 +1602,10 @@ AuxArgs verify_aux_args(const h2r_ctx *ctx, const void *sig, const void *n, cons
 }
 
 int32_t launch_verify_aux(const h2r_ctx *ctx, const AuxArgs &aa, hipStream_t st) {
-    ProfScope ps(H2R_KERNEL_AUX, st, true);   // dispatch-stamped events: no marker packets on the caller's stream
     const AuxGeom ag(ctx->L, 64);
-    const unsigned lds = (unsigned)(ag.in_field_sz() + ag.em_sz());
-    if (aa.key_idx) hipExtLaunchKernelGGL((aux_kernel<64, true>), dim3((unsigned)aa.batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    else hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)aa.batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
+    const u32 lds = (u32)(ag.in_field_sz() + ag.em_sz());
+    // (dispatch-stamped events: no marker packets on the caller's stream)
+    return stage_launch(H2R_KERNEL_AUX, st, [&](hipEvent_t a, hipEvent_t b) { return launch_aux_shape(64, lds, aa, st, a, b); });
 }
 
 // The assert_in_field(x, n) witness alone (src/chip.rs:106), one element every h2r_fresh_op_layout(IS_IN_FIELD) stride.
@@ -1662,14 +1627,7 @@ int32_t launch_in_field(const h2r_ctx *ctx, const void *x, const void *n, uint64
     const int32_t rc = in_field_args(ctx, x, n, batch, flags, in_field_trace, &aa, &lds);
     if (rc) return rc;
     H2R_ON_DEVICE(ctx->params.device);
-    ProfScope ps(H2R_KERNEL_AUX, st, true);
-    if (aa.key_idx) {
-        if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64, true>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-        else hipExtLaunchKernelGGL((aux_kernel<32, true>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    } else if (ctx->layout.limb_width == 64) hipExtLaunchKernelGGL((aux_kernel<64>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    else hipExtLaunchKernelGGL((aux_kernel<32>), dim3((unsigned)batch), dim3(64), lds, st, ps.a, ps.b, 0, aa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
+    return stage_launch(H2R_KERNEL_AUX, st, [&](hipEvent_t a, hipEvent_t b) { return launch_aux_shape(ctx->layout.limb_width, lds, aa, st, a, b); });
 }
 
 // The SHA-256 / hashed-message step: the checks of its buffers (hm_stride == 0: HM_REGION) and its kernel's arguments.
@@ -1684,10 +1642,7 @@ int32_t sha_args(const uint8_t *msgs, const uint64_t *msg_off, uint64_t fixed_le
     return H2R_OK;
 }
 int32_t launch_sha(const Sha256Args &sa, hipStream_t st) {
-    ProfScope ps(H2R_KERNEL_SHA256, st, true);
-    hipExtLaunchKernelGGL(sha256_kernel, dim3((unsigned)((sa.batch + 63) / 64)), dim3(64), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, sa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
+    return stage_launch(H2R_KERNEL_SHA256, st, [&](hipEvent_t a, hipEvent_t b) { return launch_sha256(sa, st, a, b); });
 }
 
 // What rides along with the chains and records of a pipelined call (all nullable).
@@ -2360,9 +2315,7 @@ int32_t h2r_fresh_op_batch(const h2r_ctx *ctx, uint32_t op, const void *a, const
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfScope ps(H2R_KERNEL_AUX, st);
-    if (ctx->layout.limb_width == 64) hipLaunchKernelGGL((fresh_kernel<64>), dim3((unsigned)batch), dim3(64), 0, st, fa);
-    else hipLaunchKernelGGL((fresh_kernel<32>), dim3((unsigned)batch), dim3(64), 0, st, fa);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_fresh_shape(ctx->layout.limb_width, fa, st));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -2395,9 +2348,7 @@ int32_t h2r_range_decompose_batch(const h2r_ctx *ctx, const void *values, uint32
     H2R_ON_DEVICE(ctx->params.device);
     u64 blocks = (count + 255) / 256;
     if (blocks > 2048) blocks = 2048;
-    const u32 shmem = (da.comp_len + 256) * sizeof(u32);
-    hipLaunchKernelGGL(decompose_kernel, dim3((unsigned)blocks), dim3(256), shmem, static_cast<hipStream_t>(stream), da);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_decompose(da, (u32)blocks, static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -2430,9 +2381,7 @@ int32_t h2r_trace_lookup_hist(const h2r_ctx *ctx, const void *trace, uint64_t fi
     fill_hist_args(ctx, trace, first_record_off, elem_stride, num_elems, records_per_elem, hist_out, ha);
     H2R_ON_DEVICE(ctx->params.device);
     ProfScope ps(H2R_KERNEL_HIST, static_cast<hipStream_t>(stream));
-    hipLaunchKernelGGL(hist_kernel, dim3((unsigned)num_elems), dim3(256), ctx->hist_len * sizeof(u32),
-                       static_cast<hipStream_t>(stream), ha);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_hist(ha, static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -2471,15 +2420,8 @@ int32_t h2r_trace_lookup_permutation_hist(const h2r_ctx *ctx, const void *trace,
     const u64 same_bytes = perm_same_bytes(ctx->hist_len);   // match masks: per wave, group and table row
     const u64 staged_bytes = stage_bytes + ((2ull * n_cells + 15) & ~15ull) + same_bytes;
     // staged form: 16-bit cell ids in LDS (two workgroups per CU still fit next to the 10 KB of static tables)
-    if (n_cells < 65536 && staged_bytes <= 68 * 1024) {
-        if (staged_bytes > 48 * 1024) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&perm_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)staged_bytes);
-            (void)hipGetLastError();
-        }
-        hipLaunchKernelGGL(perm_kernel<true>, dim3((unsigned)num_elems), dim3(256), (unsigned)staged_bytes, static_cast<hipStream_t>(stream), pa);
-    } else
-        hipLaunchKernelGGL(perm_kernel<false>, dim3((unsigned)num_elems), dim3(256), (unsigned)(stage_bytes + same_bytes), static_cast<hipStream_t>(stream), pa);
-    HIP_TRY(hipGetLastError());
+    const bool staged = n_cells < 65536 && staged_bytes <= 68 * 1024;
+    HIP_TRY(launch_perm(staged, (u32)(staged ? staged_bytes : stage_bytes + same_bytes), pa, static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -2577,8 +2519,7 @@ int32_t h2r_lookup_hist_records(const h2r_ctx *ctx, const h2r_lookup_config *cfg
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfScope ps(H2R_KERNEL_HIST, st);
-    hipLaunchKernelGGL(lookup_hist_records_kernel, dim3((unsigned)num_elems), dim3(256), LOOKUP_ARGS * cfg->n_rows * sizeof(u32), st, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lookup_hist_records(a, st));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -2603,8 +2544,7 @@ int32_t lookup_hist_values_impl(const h2r_ctx *ctx, const h2r_lookup_config *cfg
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfScope ps(H2R_KERNEL_HIST, st);
-    hipLaunchKernelGGL(lookup_hist_values_kernel, dim3((unsigned)num_elems), dim3(256), LOOKUP_ARGS * cfg->n_rows * sizeof(u32), st, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lookup_hist_values(a, st));
     return H2R_OK;
 }
 }  // namespace
@@ -2675,8 +2615,7 @@ int32_t lookup_hist_fresh_impl(const h2r_ctx *ctx, const h2r_lookup_config *cfg,
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     ProfScope ps(H2R_KERNEL_HIST, st);
-    hipLaunchKernelGGL(lookup_hist_fresh_kernel, dim3((unsigned)num_elems), dim3(64), LOOKUP_ARGS * cfg->n_rows * sizeof(u32), st, a);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lookup_hist_fresh(a, st));
     return H2R_OK;
 }
 }  // namespace
@@ -2728,8 +2667,7 @@ int32_t h2r_lookup_permuted_columns(const h2r_ctx *ctx, const h2r_lookup_config 
     for (u32 i = 0; i < cfg->n_lens; ++i) { sa.tag[i] = cfg->tag[i]; sa.row_off[i] = cfg->row_off[i]; sa.bit_len[i] = cfg->bit_len[i]; }
     sa.f = ctx->fc; sa.ws = ws; sa.status = status;
     sa.mont = (ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 1u : 0u;   // theta in, A' / S' out: the ctx's representation
-    hipLaunchKernelGGL(lookup_setup_kernel, dim3((unsigned)(num_elems * LOOKUP_ARGS)), dim3(256), lookup_setup_lds_bytes(cfg->n_rows), st, sa);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_lookup_setup(sa, st));
     LookupFillArgs fa;
     std::memset(&fa, 0, sizeof fa);
     fa.ws = ws; fa.num_elems = num_elems; fa.usable_rows = usable_rows; fa.n_rows = cfg->n_rows; fa.arg_mask = arg_mask & 31u;
@@ -2743,12 +2681,7 @@ int32_t h2r_lookup_permuted_columns(const h2r_ctx *ctx, const h2r_lookup_config 
     fa.round_robin = (arg_mask >> 16) & 1u;
 #endif
     fa.a_perm = static_cast<u8 *>(a_perm_out); fa.s_perm = static_cast<u8 *>(s_perm_out); fa.out_elem_stride = out_elem_stride;
-    const unsigned chunks = (usable_rows + fa.rows_per_block - 1) / fa.rows_per_block;
-    const unsigned lds = (unsigned)lookup_slot_bytes(cfg->n_rows);
-    ProfScope ps(H2R_KERNEL_LOOKUP, st, true);
-    hipExtLaunchKernelGGL(lookup_fill_kernel, dim3(chunks, LOOKUP_ARGS, (unsigned)num_elems), dim3(256), lds, st, ps.a, ps.on ? ps.b : nullptr, 0, fa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
+    return stage_launch(H2R_KERNEL_LOOKUP, st, [&](hipEvent_t a, hipEvent_t b) { return launch_lookup_fill(fa, st, a, b); });
 } H2R_CATCH_STATUS
 
 int32_t h2r_field_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t a[4], const uint64_t b[4], uint64_t out[4]) try {
@@ -2965,12 +2898,7 @@ int32_t launch_emit(const h2r_ctx *ctx, EmitArgs &ea, u32 flags, hipStream_t st)
     if (blocks == 0) return H2R_OK;
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
-    ProfScope ps(H2R_KERNEL_EMIT, st, true);
-    const unsigned lds = EMIT_SEG_CAP + 64;
-    if (lo.limb_width == 64) hipExtLaunchKernelGGL((emit_kernel<64>), dim3((unsigned)blocks), dim3(256), lds, st, ps.a, ps.on ? ps.b : nullptr, 0, ea);
-    else hipExtLaunchKernelGGL((emit_kernel<32>), dim3((unsigned)blocks), dim3(256), lds, st, ps.a, ps.on ? ps.b : nullptr, 0, ea);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
+    return stage_launch(H2R_KERNEL_EMIT, st, [&](hipEvent_t a, hipEvent_t b) { return launch_emit_shape(lo.limb_width, ea, (u32)blocks, st, a, b); });
 }
 }  // namespace
 
@@ -3039,11 +2967,7 @@ int32_t launch_advice(const h2r_ctx *ctx, AdviceArgs &aa, hipStream_t st) {
     aa.mk = ctx->mk_dev;
     if (aa.n_items == 0) return H2R_OK;
     if (aa.n_items >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-    ProfScope ps(H2R_KERNEL_EMIT, st, true);
-    if (lo.limb_width == 64) hipExtLaunchKernelGGL((advice_kernel<64>), dim3((unsigned)aa.n_items), dim3(256), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, aa);
-    else hipExtLaunchKernelGGL((advice_kernel<32>), dim3((unsigned)aa.n_items), dim3(256), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, aa);
-    HIP_TRY(hipGetLastError());
-    return H2R_OK;
+    return stage_launch(H2R_KERNEL_EMIT, st, [&](hipEvent_t a, hipEvent_t b) { return launch_advice_shape(lo.limb_width, aa, st, a, b); });
 }
 // The same image written directly from the operands (cells_kernel, h2r_cells.hpp): one wave per mul_mod, no record read.
 int32_t launch_cells(const h2r_ctx *ctx, CellsArgs &ca, hipStream_t st) {
@@ -3131,9 +3055,7 @@ int32_t pow_emit_advice(const h2r_ctx *ctx, const h2r_pow_layout *pl, const void
         const u64 per_elem = (u64)va.e_num_limbs * var_to_bits_rows(va.exp_limb_bits) + (u64)va.nbits * va.L;
         const u64 blocks = (batch * per_elem + 255) / 256;
         if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-        if (ctx->layout.limb_width == 64) hipLaunchKernelGGL((var_rows_kernel<64>), dim3((unsigned)blocks), dim3(256), 0, st, va);
-        else hipLaunchKernelGGL((var_rows_kernel<32>), dim3((unsigned)blocks), dim3(256), 0, st, va);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_var_rows_shape(ctx->layout.limb_width, va, (u32)blocks, st));
         dst = dst.at_row((u64)va.e_num_limbs * var_to_bits_rows(va.exp_limb_bits));
         sel_rows = ctx->L;
     }
@@ -3341,29 +3263,13 @@ int32_t launch_row_prog(const h2r_ctx *ctx, const h2r_ctx::RowProg *rp, RowProgA
     const u64 blocks = ra.batch * ((ra.rows + sr - 1) / sr);
     if (blocks == 0) return H2R_OK;
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-    ProfScope ps(H2R_KERNEL_EMIT, st, true);
-    auto go = [&](auto lw_c, auto sr_c) {
-        constexpr int LW = decltype(lw_c)::value; constexpr u32 SR = decltype(sr_c)::value;
-        hipExtLaunchKernelGGL((rowprog_kernel<LW, SR>), dim3((unsigned)blocks), dim3(SR), 0, st, ps.a, ps.on ? ps.b : nullptr, 0, ra);
-    };
-    using I64 = std::integral_constant<int, 64>; using I32 = std::integral_constant<int, 32>;
-    const bool w64 = ctx->layout.limb_width == 64;
-    if (sr == 64) { if (w64) go(I64{}, std::integral_constant<u32, 64>{}); else go(I32{}, std::integral_constant<u32, 64>{}); }
-    else if (sr == 128) { if (w64) go(I64{}, std::integral_constant<u32, 128>{}); else go(I32{}, std::integral_constant<u32, 128>{}); }
-    else { if (w64) go(I64{}, std::integral_constant<u32, 256>{}); else go(I32{}, std::integral_constant<u32, 256>{}); }
-    HIP_TRY(hipGetLastError());
+    const u32 w = ctx->layout.limb_width;
+    if (const int32_t rc = stage_launch(H2R_KERNEL_EMIT, st, [&](hipEvent_t a, hipEvent_t b) { return launch_rowprog_shape(w, sr, ra, (u32)blocks, st, a, b); })) return rc;
     if (ra.n_inv) {   // is_zero's inverse witnesses, packed into full waves (rowprog_inv_kernel)
         const u32 nt = sr == 64 ? 64u : 256u;   // (one-wave workgroups with the one-wave stage)
         const u64 ib = (ra.batch * ra.n_inv + nt - 1) / nt;
         if (ib >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-        if (nt == 64) {
-            if (w64) hipLaunchKernelGGL((rowprog_inv_kernel<64, 64>), dim3((unsigned)ib), dim3(64), 0, st, ra);
-            else hipLaunchKernelGGL((rowprog_inv_kernel<32, 64>), dim3((unsigned)ib), dim3(64), 0, st, ra);
-        } else {
-            if (w64) hipLaunchKernelGGL((rowprog_inv_kernel<64>), dim3((unsigned)ib), dim3(256), 0, st, ra);
-            else hipLaunchKernelGGL((rowprog_inv_kernel<32>), dim3((unsigned)ib), dim3(256), 0, st, ra);
-        }
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_rowprog_inv_shape(w, nt, ra, (u32)ib, st));
     }
     return H2R_OK;
 }
@@ -3635,8 +3541,7 @@ int32_t h2r_advice_apply_layout(const h2r_ctx *ctx, const h2r_advice_layout *lay
     std::memcpy(la.perm, layout->column_of, sizeof la.perm);
     const u64 blocks = (rows * batch + 255) / 256;
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-    hipLaunchKernelGGL(advice_layout_kernel, dim3((unsigned)blocks), dim3(256), 0, static_cast<hipStream_t>(stream), la);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_advice_layout(la, (u32)blocks, static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -3986,13 +3891,11 @@ int32_t h2r_advice_check(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const
     std::memcpy(ca.perm, layout->column_of, sizeof ca.perm);
     u64 blocks = (rows * batch + 255) / 256;
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-    hipLaunchKernelGGL(advice_check_rows_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ca);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_advice_check_rows(ca, (u32)blocks, st));
     if (n_copies) {
         blocks = (n_copies * batch + 255) / 256;
         if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-        hipLaunchKernelGGL(advice_check_copies_kernel, dim3((unsigned)blocks), dim3(256), 0, st, ca);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(launch_advice_check_copies(ca, (u32)blocks, st));
     }
     return H2R_OK;
 } H2R_CATCH_STATUS
@@ -4018,8 +3921,7 @@ int32_t h2r_lookup_hist_advice(const h2r_ctx *ctx, const h2r_lookup_config *cfg,
     for (u32 i = 0; i < cfg->n_lens; ++i) { ha.bit_len[i] = cfg->bit_len[i]; ha.row_off[i] = cfg->row_off[i]; }
     const u64 blocks = batch * ((rows + HIST_ROWS_PER_WG - 1) / HIST_ROWS_PER_WG);
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-    hipLaunchKernelGGL(advice_hist_kernel, dim3((unsigned)blocks), dim3(256), 5u * cfg->n_rows * sizeof(u32), static_cast<hipStream_t>(stream), ha);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_advice_hist(ha, (u32)blocks, static_cast<hipStream_t>(stream)));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -5030,9 +4932,7 @@ int32_t launch_check(const h2r_ctx *ctx, CheckArgs &ca, const uint8_t *status, u
     if (first_bad_out) HIP_TRY(hipMemsetAsync(first_bad_out, 0, n_elems * sizeof(uint32_t), st));
     if (ca.n_items == 0) return H2R_OK;
     if (ca.n_items >= (1ull << 31)) return H2R_E_UNSUPPORTED;
-    if (lo.limb_width == 64) hipLaunchKernelGGL((check_kernel<64>), dim3((unsigned)ca.n_items), dim3(256), 0, st, ca);
-    else hipLaunchKernelGGL((check_kernel<32>), dim3((unsigned)ca.n_items), dim3(256), 0, st, ca);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_check_shape(lo.limb_width, ca, st));
     return H2R_OK;
 }
 }  // namespace
@@ -5087,9 +4987,7 @@ int32_t h2r_pow_trace_check(const h2r_ctx *ctx, const h2r_pow_layout *pl, const 
     la.status = status; la.trace = ca.trace; la.elem_stride = ca.elem_stride;
     la.off_e_bits = pl->off_e_bits; la.off_selected = pl->off_selected; la.selected_stride = pl->selected_stride; la.off_result = pl->off_result;
     la.bad = bad_out; la.first_bad = first_bad_out;
-    if (lo.limb_width == 64) hipLaunchKernelGGL((link_kernel<64>), dim3((unsigned)batch), dim3(64), 0, st, la);
-    else hipLaunchKernelGGL((link_kernel<32>), dim3((unsigned)batch), dim3(64), 0, st, la);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_link_shape(lo.limb_width, la, batch, st));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -5207,10 +5105,8 @@ int32_t h2r_refresh_batch_ex(const h2r_ctx *ctx, const uint64_t *muled, uint64_t
     if (stage > 60 * 1024) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (stage > 40 * 1024) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&refresh_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage); (void)hipGetLastError(); }
     ProfScope ps(H2R_KERNEL_AUX, st);
-    hipLaunchKernelGGL(refresh_kernel, dim3((unsigned)batch), dim3(256), stage, st, ra);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_refresh(ra, stage, st));
     return H2R_OK;
 } H2R_CATCH_STATUS
 
@@ -5237,11 +5133,12 @@ int32_t h2r_mul_batch_ex(const h2r_ctx *ctx, const void *a, uint32_t d0, const v
     const u64 lb = ctx->layout.limb_bytes, one = batch * ctx->L * lb;
     u8 *pad = nullptr;
     HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&pad), 2 * one, st));
+    bool padded = true;
     for (int k = 0; k < 2; ++k) {
         PadArgs pa{static_cast<const u8 *>(k ? b : a), pad + k * one, batch, k ? d1 : d0, ctx->L, (u32)lb};
-        hipLaunchKernelGGL(pad_limbs_kernel, dim3((unsigned)std::min<u64>(2048, (batch * ctx->L + 255) / 256)), dim3(256), 0, st, pa);
+        padded = (launch_pad_limbs(pa, st) == hipSuccess) && padded;
     }
-    const int32_t rc = hipGetLastError() == hipSuccess ? h2r_mul_batch(ctx, pad, pad + one, batch, trace, muled_out, stream) : H2R_E_HIP;
+    const int32_t rc = padded ? h2r_mul_batch(ctx, pad, pad + one, batch, trace, muled_out, stream) : H2R_E_HIP;
     (void)hipFreeAsync(pad, st);
     return rc;
 } H2R_CATCH_STATUS
@@ -5303,10 +5200,8 @@ int32_t h2r_is_equal_muled_batch_ex(const h2r_ctx *ctx, const uint64_t *muled_a,
     if (stage > 60 * 1024) return H2R_E_UNSUPPORTED;
     H2R_ON_DEVICE(ctx->params.device);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (stage > 36 * 1024) { (void)hipFuncSetAttribute(reinterpret_cast<const void *>(&is_equal_muled_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)stage); (void)hipGetLastError(); }
     ProfScope ps(H2R_KERNEL_AUX, st);
-    hipLaunchKernelGGL(is_equal_muled_kernel, dim3((unsigned)batch), dim3(256), stage, st, ea);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(launch_is_equal_muled(ea, stage, st));
     return H2R_OK;
 } H2R_CATCH_STATUS
 

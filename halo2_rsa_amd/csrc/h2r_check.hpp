@@ -46,6 +46,7 @@ __device__ __forceinline__ void achk_fail(const AdviceCheckArgs &a, u64 elem, u6
     atomicCAS(a.first + elem, 0ull, (unsigned long long)((row << 8) | code));
 }
 
+#ifdef H2R_TU_ADVICE   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_advice.hip)
 __global__ __launch_bounds__(256) void advice_check_rows_kernel(AdviceCheckArgs a) {
     const u64 gid = (u64)blockIdx.x * 256 + threadIdx.x;
     const u64 elem = gid / a.rows;
@@ -88,7 +89,9 @@ __global__ __launch_bounds__(256) void advice_check_rows_kernel(AdviceCheckArgs 
     if (ck.nz & (1u << 7)) sum = fe_add(sum, fe_mont_mul(ck.s[7], m[5], a.f), a.f.p);
     if (!fe_is_zero(sum)) achk_fail(a, elem, r, ACHK_GATE);
 }
+#endif
 
+#ifdef H2R_TU_ADVICE   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_advice.hip)
 __global__ __launch_bounds__(256) void advice_check_copies_kernel(AdviceCheckArgs a) {
     const u64 gid = (u64)blockIdx.x * 256 + threadIdx.x;
     const u64 elem = gid / a.n_copies;
@@ -111,6 +114,7 @@ __global__ __launch_bounds__(256) void advice_check_copies_kernel(AdviceCheckArg
     }
     if (!ok) achk_fail(a, elem, cp.row, ACHK_COPY);
 }
+#endif
 
 // ---- the lookup multiplicities of an advice image: what h2r_lookup_permuted_columns needs of a witness that has no records ----
 // For every row whose kind enables the composition lookup, cells a..d each add one to their (tag, value) table row in arguments 0..3;
@@ -125,6 +129,7 @@ struct AdviceHistArgs {
     u32 bit_len[8], row_off[8];
 };
 constexpr u32 HIST_ROWS_PER_WG = 16384;
+#ifdef H2R_TU_ADVICE   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_advice.hip)
 __global__ __launch_bounds__(256) void advice_hist_kernel(AdviceHistArgs a) {
     extern __shared__ u32 hist_lds[];                        // [5][n_rows]
     const u32 chunks = (u32)((a.rows + HIST_ROWS_PER_WG - 1) / HIST_ROWS_PER_WG);
@@ -174,5 +179,6 @@ __global__ __launch_bounds__(256) void advice_hist_kernel(AdviceHistArgs a) {
     u32 *out = a.hist + elem * 5ull * a.n_rows;
     for (u32 k = threadIdx.x; k < 5 * a.n_rows; k += 256) if (hist_lds[k]) atomicAdd(out + k, hist_lds[k]);
 }
+#endif
 
 }  // namespace h2r

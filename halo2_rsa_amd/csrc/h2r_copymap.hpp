@@ -113,6 +113,7 @@ inline bool layout_perm_valid(const u8 (&col)[5], const h2r_fixed_row &f, bool i
 struct LayoutArgs { const u8 *kinds; u64 rows; AdviceDst dst; u64 batch; const u8 *status; u8 perm[256][5]; };
 
 // one thread per row: the row's five cells move to the columns the layout gives its kind (in place: a thread owns its row)
+#ifdef H2R_TU_ADVICE   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_advice.hip)
 __global__ __launch_bounds__(256) void advice_layout_kernel(LayoutArgs a) {
     const u64 gid = (u64)blockIdx.x * 256 + threadIdx.x;
     const u64 elem = gid / a.rows;
@@ -127,5 +128,6 @@ __global__ __launch_bounds__(256) void advice_layout_kernel(LayoutArgs a) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) { uint4 *c = reinterpret_cast<uint4 *>(row + (u64)pm[k] * a.dst.col_pitch); c[0] = v[2 * k]; c[1] = v[2 * k + 1]; }
 }
+#endif
 
 }  // namespace h2r

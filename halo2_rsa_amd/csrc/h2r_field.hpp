@@ -20,7 +20,13 @@ struct FieldConsts {
     uint64_t n0inv;     // -p^{-1} mod 2^64
 };
 
+// Forced inlining is the device pass's: an outlined helper there puts a kernel's argument struct in scratch.  On the host pass the same
+// force folds every formula of a twin (curve additions, scalar multiplications, fe_inv) into one function that takes a minute to compile.
+#if defined(__HIP_DEVICE_COMPILE__)
 #define H2R_FD __host__ __device__ __forceinline__
+#else
+#define H2R_FD __host__ __device__ inline
+#endif
 
 H2R_FD bool fe_is_zero(const Fe &a) { return (a.v[0] | a.v[1] | a.v[2] | a.v[3]) == 0; }
 H2R_FD bool fe_eq(const Fe &a, const Fe &b) { return a.v[0] == b.v[0] && a.v[1] == b.v[1] && a.v[2] == b.v[2] && a.v[3] == b.v[3]; }

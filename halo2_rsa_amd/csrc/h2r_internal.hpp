@@ -1,7 +1,7 @@
 // Internal to libh2r.so: what the library's translation units share.
 //
-// The library is compiled as several translation units so that a forced build stays under a minute (the device
-// compile of the template kernel families is what a build costs; each family is instantiated in exactly one unit):
+// The library is compiled as several translation units that build side by side (the device compile of the template
+// kernel families is what a build costs; each family is defined, instantiated and launched in exactly one unit):
 //   h2r_tu_trace.hip   trace_kernel<LW, L>         (one record per mul_mod; every supported shape)
 //   h2r_tu_chain.hip   recip / key_table / chain / chain_dual / chain_wave kernels (the dependent mul_mod chain per element)
 //   h2r_tu_step.hip    step_kernel<K, NW, LW, L>   (records of call k + chains of call k+1 in one launch)
@@ -16,7 +16,14 @@
 //   h2r_tu_curve_ntt.hip   the Lagrange-basis commitment key: the transform over the curve's points (h2r_curve_ntt.hpp, h2r_curve.hpp)
 //   h2r_tu_transcript.hip   the Fiat-Shamir transcript: one round of a batch of BLAKE2b states per launch (h2r_transcript.hpp)
 //   h2r_tu_random.hip  the prover's blinding values: a counter-based generator over the transcript's BLAKE2b (h2r_random.hpp)
-//   h2r_api.hip        the C ABI, the ctx, the pipelines, and every small kernel
+//   h2r_tu_witness.hip   the witness kernels outside the mul_mod records: assert_in_field / encoded message (aux), the Fresh ops, SHA-256, the
+//                      in-place audit (check, link), range decompose, key expand, mul / refresh / is_equal_muled (h2r_muled.hpp), and the
+//                      arena's fill / restore kernels and the queue probe
+//   h2r_tu_advice.hip  the advice image from records and programs: advice / emit / var_rows / rowprog kernels, the layout permutation, the
+//                      MockProver's row / copy checks and the image's lookup histogram (h2r_rowprog.hpp, h2r_varrows.hpp, h2r_copymap.hpp, h2r_check.hpp)
+//   h2r_tu_lookup.hip  the lookup argument's multiplicities and permuted columns: hist / perm kernels over the records, the per-argument
+//                      histograms, the A' / S' set-up and fill (h2r_lookup.hpp)
+//   h2r_api.hip        the C ABI, the ctx, the pipelines and the host twins: host code only, no kernel is defined or launched there
 // The launchers below take plain values, never the ctx: `struct h2r_ctx` stays private to h2r_api.hip.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -153,5 +160,55 @@ hipError_t launch_transcript(const TranscriptArgs &a, u32 num_blocks, hipStream_
 // [a.elem0, a.elem0 + num_elems).
 struct RandomArgs;
 hipError_t launch_random(const RandomArgs &a, u32 num_tiles, u32 num_cols, u32 num_elems, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_witness.hip (argument structs: h2r_kernels.hpp, h2r_muled.hpp).  w = the limb width (64 | 32).  The aux kernel is the keyed build when
+// aa.key_idx is set; `lds` / `stage` = the dynamic LDS request.
+struct RefreshArgs;
+struct EqMuledArgs;
+struct PadArgs;
+struct ArenaConstPlanes { u64 off[7]; u32 bytes[7]; };   // the constant planes of a record: offsets in the record, bytes (whole words)
+hipError_t launch_aux_shape(u32 w, u32 lds, const AuxArgs &aa, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_fresh_shape(u32 w, const FreshArgs &fa, hipStream_t st);
+hipError_t launch_sha256(const Sha256Args &sa, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_check_shape(u32 w, const CheckArgs &ca, hipStream_t st);
+hipError_t launch_link_shape(u32 w, const LinkArgs &la, u64 batch, hipStream_t st);
+hipError_t launch_decompose(const DecompArgs &da, u32 blocks, hipStream_t st);
+hipError_t launch_key_expand(const u32 *raw, u32 raw_stride, u32 num_keys, const u32 *key_idx, u64 batch, u32 kreal, u32 *n_out, hipStream_t st);
+hipError_t launch_refresh(const RefreshArgs &ra, u32 stage, hipStream_t st);
+hipError_t launch_is_equal_muled(const EqMuledArgs &ea, u32 stage, hipStream_t st);
+hipError_t launch_pad_limbs(const PadArgs &pa, hipStream_t st);
+hipError_t launch_arena_fill(u8 *p, u64 bytes, hipStream_t st, hipEvent_t ea, hipEvent_t eb);   // one workgroup per 64 KB
+hipError_t launch_arena_restore(u32 blocks, u8 *base, u64 elem_stride, u64 off_records, u64 record_stride, u32 T, u64 n_records, const u8 *cr,
+                                const ArenaConstPlanes &pl, hipStream_t st);
+hipError_t launch_queue_probe(unsigned long long ticks, unsigned long long *stamp, hipStream_t st);
+// h2r_tu_advice.hip (argument structs: h2r_kernels.hpp, h2r_varrows.hpp, h2r_rowprog.hpp, h2r_copymap.hpp, h2r_check.hpp).  sr = rows (= threads)
+// of a row-program workgroup (64 | 128 | 256), nt = threads of an inverse-witness workgroup (64 | 256); `blocks` = the grid.
+struct VarRowsArgs;
+struct RowProgArgs;
+struct LayoutArgs;
+struct AdviceCheckArgs;
+struct AdviceHistArgs;
+hipError_t launch_advice_shape(u32 w, const AdviceArgs &aa, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_emit_shape(u32 w, const EmitArgs &a, u32 blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_var_rows_shape(u32 w, const VarRowsArgs &va, u32 blocks, hipStream_t st);
+hipError_t launch_rowprog_shape(u32 w, u32 sr, const RowProgArgs &ra, u32 blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_rowprog_inv_shape(u32 w, u32 nt, const RowProgArgs &ra, u32 blocks, hipStream_t st);
+hipError_t launch_advice_layout(const LayoutArgs &la, u32 blocks, hipStream_t st);
+hipError_t launch_advice_check_rows(const AdviceCheckArgs &ca, u32 blocks, hipStream_t st);
+hipError_t launch_advice_check_copies(const AdviceCheckArgs &ca, u32 blocks, hipStream_t st);
+hipError_t launch_advice_hist(const AdviceHistArgs &ha, u32 blocks, hipStream_t st);
+// h2r_tu_lookup.hip (argument structs: h2r_kernels.hpp, h2r_lookup.hpp).  One workgroup per element (hist, perm, the three histograms), per
+// element and argument (set-up), per chunk of a.rows_per_block rows, argument and element (fill).  perm: `staged` = 16-bit cell ids in LDS.
+struct LookupHistArgs;
+struct LookupValuesArgs;
+struct LookupFreshArgs;
+struct LookupSetupArgs;
+struct LookupFillArgs;
+hipError_t launch_hist(const HistArgs &ha, hipStream_t st);
+hipError_t launch_perm(bool staged, u32 lds, const PermArgs &pa, hipStream_t st);
+hipError_t launch_lookup_hist_records(const LookupHistArgs &a, hipStream_t st);
+hipError_t launch_lookup_hist_values(const LookupValuesArgs &a, hipStream_t st);
+hipError_t launch_lookup_hist_fresh(const LookupFreshArgs &a, hipStream_t st);
+hipError_t launch_lookup_setup(const LookupSetupArgs &a, hipStream_t st);
+hipError_t launch_lookup_fill(const LookupFillArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 
 }  // namespace h2r

@@ -1133,7 +1133,7 @@ __global__ __launch_bounds__(64 * NW) void key_table_kernel(const u32 *n_keys, u
     }
 }
 // h2r_key_table_expand: n_out[e] = the raw digits of key key_idx[e] (the sentinel's zeros for an index out of range); one thread per digit
-#ifdef H2R_TU_API   // a plain (non-template) kernel: defined in the one translation unit that launches it
+#ifdef H2R_TU_WITNESS   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_witness.hip)
 __global__ void key_expand_kernel(const u32 *raw, u32 raw_stride, u32 num_keys, const u32 *key_idx, u64 batch, u32 kreal, u32 *n_out) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= batch * kreal) return;
@@ -2127,7 +2127,7 @@ struct HistArgs {
     u32 *hist;  // [elem][hist_len]
 };
 
-#ifdef H2R_TU_API   // a plain (non-template) kernel: defined in the one translation unit that launches it
+#ifdef H2R_TU_LOOKUP   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_lookup.hip)
 __global__ __launch_bounds__(256) void hist_kernel(HistArgs a) {
     extern __shared__ u32 h[];
     const u64 elem = blockIdx.x;
@@ -3229,7 +3229,7 @@ struct DecompArgs {
     const u8 *values; u32 value_bytes; u64 count; u32 bit_len, sub_bits, nsub, has_ov;
     u8 *sub_out; u32 sub_stride; u32 *hist; u32 comp_len;
 };
-#ifdef H2R_TU_API   // a plain (non-template) kernel: defined in the one translation unit that launches it
+#ifdef H2R_TU_WITNESS   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_witness.hip)
 __global__ __launch_bounds__(256) void decompose_kernel(DecompArgs a) {
     extern __shared__ u32 h[];
     const u32 hl = a.hist ? a.comp_len + (a.has_ov ? (1u << (a.bit_len % a.sub_bits)) : 0) : 0;

@@ -55,6 +55,7 @@ struct LookupHistArgs {
     u32 *hist;          // [elem][5][n_rows], ADDED to
     const u8 *status;   // nullable: elements with a nonzero status are skipped
 };
+#ifdef H2R_TU_LOOKUP   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_lookup.hip)
 __global__ __launch_bounds__(256) void lookup_hist_records_kernel(LookupHistArgs a) {
     extern __shared__ u32 lh[];
     const u32 tid = threadIdx.x, n = LOOKUP_ARGS * a.n_rows;
@@ -79,6 +80,7 @@ __global__ __launch_bounds__(256) void lookup_hist_records_kernel(LookupHistArgs
     u32 *out = a.hist + elem * n;
     for (u32 k = tid; k < n; k += 256) if (lh[k]) out[k] += lh[k];
 }
+#endif
 
 struct LookupValuesArgs {
     const u8 *values; u32 value_bytes; u64 values_per_elem, num_elems;
@@ -86,6 +88,7 @@ struct LookupValuesArgs {
     const u8 *status;                   // nullable: elements with a nonzero status are skipped
     RangeShape shape; u32 n_rows; u32 *hist;
 };
+#ifdef H2R_TU_LOOKUP   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_lookup.hip)
 __global__ __launch_bounds__(256) void lookup_hist_values_kernel(LookupValuesArgs a) {
     extern __shared__ u32 lh[];
     const u32 tid = threadIdx.x, n = LOOKUP_ARGS * a.n_rows;
@@ -104,6 +107,7 @@ __global__ __launch_bounds__(256) void lookup_hist_values_kernel(LookupValuesArg
     u32 *out = a.hist + elem * n;
     for (u32 k = tid; k < n; k += 256) if (lh[k]) out[k] += lh[k];
 }
+#endif
 
 // The range assigns inside a Fresh-op witness (assert_in_field's add / sub_unchecked steps: every one a
 // RangeChip::assign(limb, w/8, w), big_integer/chip.rs:279-282, 1307-1308): runs of entries {limb, 8 sub-limb bytes} at a stride
@@ -112,6 +116,7 @@ struct LookupFreshArgs {
     u32 n_runs; u32 run_off[16], run_n[16], run_stride[16]; u32 sub_off;   // sub-limb bytes at entry + sub_off
     RangeShape limb; u32 n_rows; u32 *hist; const u8 *status;
 };
+#ifdef H2R_TU_LOOKUP   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_lookup.hip)
 __global__ __launch_bounds__(64) void lookup_hist_fresh_kernel(LookupFreshArgs a) {
     extern __shared__ u32 lh[];
     const u32 tid = threadIdx.x, n = LOOKUP_ARGS * a.n_rows;
@@ -130,6 +135,7 @@ __global__ __launch_bounds__(64) void lookup_hist_fresh_kernel(LookupFreshArgs a
     u32 *out = a.hist + elem * n;
     for (u32 k = tid; k < n; k += 64) if (lh[k]) out[k] += lh[k];
 }
+#endif
 
 // ---- tables of one (element, argument) in the workspace ---------------------------------------------------------------
 // [0, 32 G)  val      sorted distinct compressed values (Fe)
@@ -170,6 +176,7 @@ __device__ __forceinline__ void block_scan_1024(u32 *x, u32 n, u32 *part /* 256 
 // LDS of the set-up kernel for a table of n rows (sized by the table, not by LOOKUP_MAX_ROWS: 19 KB instead of 54.5 KB for RSA-2048's 339 rows --
 // next to a cells kernel that holds most of a CU's LDS a 54.5 KB workgroup waited for room, 0.9 ms per 1,024 circuits in the records-free flow)
 __host__ __device__ inline u32 lookup_setup_lds_bytes(u32 n) { return n * 32u + LOOKUP_MAX_LENS * 32u + 5u * n * 4u + 256u * 4u + 16u; }
+#ifdef H2R_TU_LOOKUP   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_lookup.hip)
 __global__ __launch_bounds__(256) void lookup_setup_kernel(LookupSetupArgs a) {
     extern __shared__ uint4 ls_dyn[];
     const u32 tid = threadIdx.x, n = a.n_rows;
@@ -271,6 +278,7 @@ __global__ __launch_bounds__(256) void lookup_setup_kernel(LookupSetupArgs a) {
     for (u32 g = tid; g < G; g += 256) { a_start[g + 1] = gm[g]; a_rank[g] = g ? gr[g - 1] : 0u; l_start[g + 1] = gs[g]; }
     if (tid == 0) { a_start[0] = 0; l_start[0] = 0; gcount[0] = G; gcount[1] = gr[G - 1]; }
 }
+#endif
 
 struct LookupFillArgs {
     const u8 *ws; u64 num_elems; u32 usable_rows, n_rows, arg_mask, rows_per_block, round_robin;
@@ -283,6 +291,7 @@ __device__ __forceinline__ u32 upper_group(const u32 *start, u32 G, u32 x) {
     while (lo < hi) { const u32 mid = (lo + hi + 1) >> 1; if (start[mid] <= x) lo = mid; else hi = mid - 1; }
     return lo;
 }
+#ifdef H2R_TU_LOOKUP   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_lookup.hip)
 __global__ __launch_bounds__(256) void lookup_fill_kernel(LookupFillArgs a) {
     extern __shared__ uint4 lf_dyn[];
     const u32 tid = threadIdx.x, lane = tid & 63, n = a.n_rows;
@@ -341,5 +350,6 @@ __global__ __launch_bounds__(256) void lookup_fill_kernel(LookupFillArgs a) {
         }
     }
 }
+#endif
 
 }  // namespace h2r

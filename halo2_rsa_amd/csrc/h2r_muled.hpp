@@ -48,6 +48,7 @@ struct RefreshArgs {
     u32 LB, WB, CB, stream_bytes;
 };
 
+#ifdef H2R_TU_WITNESS   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_witness.hip)
 __global__ __launch_bounds__(256) void refresh_kernel(RefreshArgs a) {
     __shared__ u64 v0[MULED_MAX], v1[MULED_MAX]; __shared__ u32 v2[MULED_MAX];
     extern __shared__ uint4 refresh_stage[];
@@ -138,6 +139,7 @@ __global__ __launch_bounds__(256) void refresh_kernel(RefreshArgs a) {
     u8 *dst = a.trace + elem * a.elem_stride;
     for (u32 k = tid; k < (a.stream_bytes + 15) / 16; k += 256) { const uint4 x = refresh_stage[k]; pst16(dst + 16ull * k, ((u64)x.y << 32) | x.x, ((u64)x.w << 32) | x.z); }
 }
+#endif
 
 struct EqMuledArgs {
     const u64 *ma, *mb; u64 muled_stride;   // [elem][muled_stride] x 4 u64
@@ -151,6 +153,7 @@ struct EqMuledArgs {
     u8 *eq_out;                              // [elem] (nullable)
 };
 
+#ifdef H2R_TU_WITNESS   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_witness.hip)
 __global__ __launch_bounds__(256) void is_equal_muled_kernel(EqMuledArgs a) {
     __shared__ u64 c0[MULED_MAX], c1[MULED_MAX];   // carry[i] (carry into column i), < 2^(carry_bits)
     __shared__ u64 x0[MULED_MAX], x1[MULED_MAX];   // accumulated_extra before column i
@@ -241,9 +244,11 @@ __global__ __launch_bounds__(256) void is_equal_muled_kernel(EqMuledArgs a) {
     u8 *dst = a.trace + elem * a.elem_stride;
     for (u32 k = tid; k < (a.stream_bytes + 15) / 16; k += 256) { const uint4 x = eq_stage[k]; pst16(dst + 16ull * k, ((u64)x.y << 32) | x.x, ((u64)x.w << 32) | x.z); }
 }
+#endif
 
 // zero-padded copy of [batch][d] limbs into [batch][L] (mul with operands shorter than the ctx's num_limbs)
 struct PadArgs { const u8 *src; u8 *dst; u64 batch; u32 d, L, LB; };
+#ifdef H2R_TU_WITNESS   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_witness.hip)
 __global__ __launch_bounds__(256) void pad_limbs_kernel(PadArgs a) {
     const u64 n = a.batch * a.L;
     for (u64 idx = (u64)blockIdx.x * 256 + threadIdx.x; idx < n; idx += (u64)gridDim.x * 256) {
@@ -252,5 +257,6 @@ __global__ __launch_bounds__(256) void pad_limbs_kernel(PadArgs a) {
         else reinterpret_cast<u32 *>(a.dst)[idx] = k < a.d ? reinterpret_cast<const u32 *>(a.src)[e * a.d + k] : 0;
     }
 }
+#endif
 
 }  // namespace h2r

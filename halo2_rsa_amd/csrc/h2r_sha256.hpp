@@ -92,7 +92,7 @@ __device__ __forceinline__ void sha256_outputs(const Sha256Args &a, u64 e, const
     }
 }
 
-#ifdef H2R_TU_API   // a plain (non-template) kernel: defined in the one translation unit that launches it
+#ifdef H2R_TU_WITNESS   // a plain (non-template) kernel: defined in the one translation unit that launches it (h2r_tu_witness.hip)
 __global__ __launch_bounds__(64) void sha256_kernel(Sha256Args a) {
     const u64 e = (u64)blockIdx.x * 64 + threadIdx.x;
     if (e >= a.batch) return;
@@ -135,6 +135,7 @@ __global__ __launch_bounds__(64) void sha256_kernel(Sha256Args a) {
 // passes of sixteen unrolled rounds -- the schedule window stays in registers with static indices, the round constants come from
 // constant memory -- about 45 VGPRs.  The role is one latency-bound wave per 64 messages next to five busy workgroups per CU: it
 // raises its wave priority, because the chain role of the same launch may wait for its limbs (Sha256Args::done).
+#ifdef H2R_TU_STEP   // the role and its constant table: defined in the units that instantiate step_kernel (h2r_step_launch.hpp)
 __constant__ u32 SHA256_K[64] = {
 #define X(v) v##u,
     H2R_SHA_K(X)
@@ -195,5 +196,6 @@ __device__ void sha256_role(const Sha256Args &a, u32 blk, u32 *) {
         __hip_atomic_fetch_add(a.done, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
+#endif  // H2R_TU_STEP
 
 }  // namespace h2r

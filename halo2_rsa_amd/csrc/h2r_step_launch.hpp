@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 
+#define H2R_TU_STEP   // the units that include this header instantiate step_kernel: they define its SHA-256 role (h2r_sha256.hpp)
 #include "h2r_internal.hpp"
 #include "h2r_sha256.hpp"
 
