@@ -192,6 +192,42 @@ class H2RRandomColumn(ctypes.Structure):
     _fields_ = [("base", ctypes.c_void_p), ("elem_stride", ctypes.c_uint64), ("tag", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+H2R_VERIFY_MAX_SECTIONS, H2R_VERIFY_MAX_PLAN, H2R_VERIFY_MAX_TERMS = 16, 64, 4096
+VERIFY_GROUPS = ("advice", "fixed", "random", "sigma", "perm_z", "lookup_z", "lookup_a_perm", "lookup_s_perm", "h")   # H2R_VERIFY_G_*
+
+
+class H2RProofSection(ctypes.Structure):
+    _fields_ = [("kind", ctypes.c_uint32), ("count", ctypes.c_uint32)]
+
+
+class H2RProofDecodeConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_sections", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
+
+
+class H2RVerifyPlanEntry(ctypes.Structure):
+    _fields_ = [("group", ctypes.c_uint8), ("index", ctypes.c_uint8), ("mask", ctypes.c_uint8), ("reserved", ctypes.c_uint8)]
+
+
+class H2RVerifyScalarsConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("log_n", ctypes.c_uint32), ("blinding_factors", ctypes.c_uint32), ("num_fixed", ctypes.c_uint32),
+                ("num_columns", ctypes.c_uint32), ("chunk_len", ctypes.c_uint32), ("lookup_mask", ctypes.c_uint32),
+                ("num_eval_plan", ctypes.c_uint32), ("num_open_plan", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("omega", ctypes.c_uint64 * 4), ("delta", ctypes.c_uint64 * 4), ("gate_fixed", ctypes.c_uint8 * 9),
+                ("column_src", ctypes.c_uint8 * H2R_PERM_MAX_COLUMNS), ("lookup_advice", ctypes.c_uint8 * H2R_LOOKUP_ARGS),
+                ("lookup_tag", ctypes.c_uint8 * H2R_LOOKUP_ARGS), ("lookup_enable", ctypes.c_uint8 * H2R_LOOKUP_ARGS),
+                ("table_tag", ctypes.c_uint8), ("table_value", ctypes.c_uint8),
+                ("eval_plan", H2RVerifyPlanEntry * H2R_VERIFY_MAX_PLAN), ("open_plan", H2RVerifyPlanEntry * H2R_VERIFY_MAX_PLAN)]
+
+
+class H2RVerifyChallenges(ctypes.Structure):
+    NAMES = ("theta", "beta", "gamma", "y", "x", "v", "u")
+    _fields_ = [(nm, ctypes.c_void_p) for nm in NAMES]
+
+
+class H2RMsmTermsConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_terms", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -245,6 +281,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_curve_ntt_workspace_bytes", "h2r_curve_ntt",
            "h2r_transcript_state_bytes", "h2r_transcript_round", "h2r_transcript_eval",
            "h2r_random_columns", "h2r_random_eval",
+           "h2r_proof_decode", "h2r_verify_bases", "h2r_verify_scalars", "h2r_msm_terms", "h2r_verify_eval",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -261,6 +298,7 @@ KERNEL_MSM_BUCKET, KERNEL_MSM_FOLD = 23, 24
 KERNEL_CURVE_NTT_TWIDDLE, KERNEL_CURVE_NTT_LOAD, KERNEL_CURVE_NTT_STAGE, KERNEL_CURVE_NTT_STORE = 25, 26, 27, 28
 KERNEL_TRANSCRIPT = 29
 KERNEL_RANDOM = 30
+KERNEL_PROOF_DECODE, KERNEL_VERIFY_SCALARS, KERNEL_MSM_TERMS = 31, 32, 33
 FIELD_MUL, FIELD_TO_MONTGOMERY, FIELD_FROM_MONTGOMERY = 2, 6, 7   # h2r_field_eval's operations a * b, a * R and a * R^-1 mod p (include/h2r.h)
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
@@ -493,6 +531,13 @@ def lib():
     L.h2r_transcript_eval.argtypes = [vp, u32, vp, ctypes.c_char_p, u64, pu64]
     L.h2r_random_columns.argtypes = [vp, ctypes.POINTER(H2RRandomConfig), ctypes.POINTER(H2RRandomColumn), u64, vp]
     L.h2r_random_eval.argtypes = [vp, ctypes.c_char_p, u64, u32, u64, pu64]
+    pvs = ctypes.POINTER(H2RVerifyScalarsConfig)
+    L.h2r_proof_decode.argtypes = [vp, ctypes.POINTER(H2RProofDecodeConfig), ctypes.POINTER(H2RProofSection), vp, u64, u64, vp, u64, vp, u64, vp, vp]
+    L.h2r_verify_bases.argtypes = [pvs, pu32]
+    L.h2r_verify_bases.restype = u32
+    L.h2r_verify_scalars.argtypes = [vp, pvs, vp, u64, ctypes.POINTER(H2RVerifyChallenges), u64, vp, u64, vp, vp, vp]
+    L.h2r_msm_terms.argtypes = [vp, ctypes.POINTER(H2RMsmTermsConfig), vp, u64, vp, u64, u64, vp, vp, vp]
+    L.h2r_verify_eval.argtypes = [vp, u32, pvs, ctypes.c_char_p, u64, vp, u64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.h2r_dist_destroy.argtypes = [vp]

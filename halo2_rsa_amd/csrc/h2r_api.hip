@@ -32,6 +32,7 @@
 #include "h2r_curve_ntt.hpp"
 #include "h2r_transcript.hpp"
 #include "h2r_random.hpp"
+#include "h2r_verify.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4360,7 +4361,9 @@ namespace {
 static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_OPEN_SCAN == H2R_KERNEL_OPEN_TILES + 2 &&
               H2R_KERNEL_MSM_BUCKET == H2R_KERNEL_FOLD + 1 && H2R_KERNEL_MSM_FOLD == H2R_KERNEL_MSM_BUCKET + 1 &&
               H2R_KERNEL_CURVE_NTT_TWIDDLE == H2R_KERNEL_MSM_FOLD + 1 && H2R_KERNEL_CURVE_NTT_STORE == H2R_KERNEL_CURVE_NTT_TWIDDLE + 3 &&
-              H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_RANDOM == H2R_KERNEL_TRANSCRIPT + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_RANDOM + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_RANDOM == H2R_KERNEL_TRANSCRIPT + 1 && H2R_KERNEL_PROOF_DECODE == H2R_KERNEL_RANDOM + 1 &&
+              H2R_KERNEL_VERIFY_SCALARS == H2R_KERNEL_PROOF_DECODE + 1 && H2R_KERNEL_MSM_TERMS == H2R_KERNEL_VERIFY_SCALARS + 1 &&
+              H2R_KERNEL_COUNT == H2R_KERNEL_MSM_TERMS + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -4878,6 +4881,306 @@ int32_t h2r_random_eval(const h2r_ctx *ctx, const uint8_t seed[32], uint64_t cir
     random_seed_words(seed, sw);
     const Fe x = rnd_element(sw, circuit, tag, row, TrBlock{block, 1}, transcript_consts(ctx, *cv));
     for (int k = 0; k < 4; ++k) out[k] = x.v[k];
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the verifier up to the pairing: decoder, the accumulators' scalars, the sum of terms (h2r_verify.hpp, h2r_tu_verify.hip) --------------
+namespace {
+static_assert(H2R_VERIFY_MAX_SECTIONS == VF_MAX_SECTIONS && H2R_VERIFY_MAX_PLAN == VF_MAX_PLAN && H2R_VERIFY_MAX_TERMS == VF_MAX_TERMS &&
+              H2R_VERIFY_G_H == VF_G_H && H2R_VERIFY_G_LOOKUP_S_PERM == VF_G_LOOKUP_S && H2R_TRANSCRIPT_POINT == VF_POINT && H2R_TRANSCRIPT_SCALAR == VF_SCALAR &&
+              H2R_PERM_MAX_COLUMNS == QUOT_PERM_MAX_COLUMNS && H2R_LOOKUP_ARGS == QUOT_LOOKUP_ARGS, "h2r.h and the kernels' argument structs");
+// (q + 1) / 4 of the coordinate field (q = 3 mod 4: the square root is one power)
+void sqrt_exponent(const FieldConsts &fq, u64 (&e)[4]) {
+    u64 t[4], cy = 1;
+    for (int k = 0; k < 4; ++k) { t[k] = fq.p[k] + cy; cy = t[k] < cy ? 1 : 0; }
+    for (int k = 0; k < 4; ++k) e[k] = (t[k] >> 2) | (k < 3 ? t[k + 1] << 62 : 0);
+}
+// the sections of a decode call into the kernel's tables: 0, or the refusal; np / ns = the points and the scalars of a proof
+int32_t decode_sections(const h2r_proof_decode_config *cfg, const h2r_proof_section *sections, DecodeArgs &da, u32 &np, u32 &ns) {
+    if (cfg->num_sections == 0 || cfg->num_sections > VF_MAX_SECTIONS || cfg->reserved) return H2R_E_SHAPE;
+    u64 items = 0;
+    np = ns = 0;
+    for (u32 s = 0; s < cfg->num_sections; ++s) {
+        const h2r_proof_section &sec = sections[s];
+        if ((sec.kind != VF_POINT && sec.kind != VF_SCALAR) || sec.count == 0 || sec.count >= VF_MAX_ITEMS) return H2R_E_SHAPE;
+        items += sec.count;
+        if (items >= VF_MAX_ITEMS) return H2R_E_SHAPE;
+        da.sec_kind[s] = (u8)sec.kind; da.sec_end[s] = (u32)items;
+        u32 &n = sec.kind == VF_POINT ? np : ns;
+        da.sec_out[s] = n; n += sec.count;
+    }
+    da.num_sections = cfg->num_sections; da.num_items = (u32)items;
+    return H2R_OK;
+}
+// A configuration into the kernel's arguments (everything but the buffers): 0, or the refusal.  ctx == nullptr: the parts that need no
+// field (h2r_verify_bases).
+int32_t verify_scalars_args(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, VerifyScalarsArgs &a, u32 &num_evals) {
+    if (cfg->struct_size != sizeof(h2r_verify_scalars_config)) return H2R_E_UNSUPPORTED;
+    const u32 F = cfg->num_fixed, m = cfg->num_columns;
+    if (cfg->reserved || cfg->log_n == 0 || cfg->log_n > QUOT_MAX_LOG || cfg->blinding_factors > VF_MAX_BF || F > QUOT_MAX_FIXED || m == 0 ||
+        m > QUOT_PERM_MAX_COLUMNS || cfg->chunk_len == 0 || (cfg->lookup_mask >> QUOT_LOOKUP_ARGS)) return H2R_E_SHAPE;
+    if ((u64)cfg->blinding_factors + 2 > (1ull << cfg->log_n)) return H2R_E_SHAPE;       // u = n - bf - 1 >= 1
+    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i) if (cfg->gate_fixed[i] >= F) return H2R_E_SHAPE;
+    for (u32 c = 0; c < m; ++c) if (cfg->column_src[c] >= 5) return H2R_E_SHAPE;
+    u32 A = 0;
+    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k) {
+        if (!((cfg->lookup_mask >> k) & 1u)) continue;
+        ++A;
+        if (cfg->lookup_advice[k] >= 5 || cfg->lookup_tag[k] >= F || cfg->lookup_enable[k] >= F) return H2R_E_SHAPE;
+    }
+    if (A && (cfg->table_tag >= F || cfg->table_value >= F)) return H2R_E_SHAPE;
+    if (cfg->num_eval_plan == 0 || cfg->num_eval_plan > VF_MAX_PLAN || cfg->num_open_plan == 0 || cfg->num_open_plan > VF_MAX_PLAN) return H2R_E_SHAPE;
+    const u32 chunk = std::min<u32>(cfg->chunk_len, m), S = (m + chunk - 1) / chunk;
+    a.log_n = cfg->log_n; a.bf = cfg->blinding_factors; a.m = m; a.chunk_len = chunk; a.n_sets = S; a.lookup_mask = cfg->lookup_mask;
+    std::memcpy(a.gate_fixed, cfg->gate_fixed, sizeof a.gate_fixed); std::memcpy(a.src, cfg->column_src, sizeof a.src);
+    std::memcpy(a.lookup_advice, cfg->lookup_advice, sizeof a.lookup_advice); std::memcpy(a.lookup_tag, cfg->lookup_tag, sizeof a.lookup_tag);
+    std::memcpy(a.lookup_enable, cfg->lookup_enable, sizeof a.lookup_enable);
+    a.table_tag = cfg->table_tag; a.table_value = cfg->table_value;
+    // how many columns a group has, and the point sets the expression reads of each
+    auto columns = [&](u32 g) -> u32 {
+        return g == VF_G_ADVICE ? 5u : g == VF_G_FIXED ? F : g == VF_G_RANDOM ? 1u : g == VF_G_SIGMA ? m : g == VF_G_PERM_Z ? S : g == VF_G_H ? 1u : QUOT_LOOKUP_ARGS;
+    };
+    auto exists = [&](u32 g, u32 i) {
+        if (g >= VF_GROUPS || i >= columns(g)) return false;
+        return !(g == VF_G_LOOKUP_Z || g == VF_G_LOOKUP_A || g == VF_G_LOOKUP_S) || ((cfg->lookup_mask >> i) & 1u);
+    };
+    u8 need[VF_GROUPS][VF_MAX_INDEX] = {};
+    for (u32 c = 0; c < 5; ++c) need[VF_G_ADVICE][c] = c == 4 ? 3 : 1;
+    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i) need[VF_G_FIXED][cfg->gate_fixed[i]] = 1;
+    for (u32 c = 0; c < m; ++c) need[VF_G_SIGMA][c] = 1;
+    for (u32 s = 0; s < S; ++s) need[VF_G_PERM_Z][s] = s + 1 < S ? 7 : 3;
+    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k) {
+        if (!((cfg->lookup_mask >> k) & 1u)) continue;
+        need[VF_G_LOOKUP_Z][k] = 3; need[VF_G_LOOKUP_A][k] = 9; need[VF_G_LOOKUP_S][k] = 1;
+        need[VF_G_FIXED][cfg->lookup_tag[k]] = need[VF_G_FIXED][cfg->lookup_enable[k]] = need[VF_G_FIXED][cfg->table_tag] = need[VF_G_FIXED][cfg->table_value] = 1;
+    }
+    u32 q = 0;
+    for (u32 j = 0; j < cfg->num_eval_plan; ++j) {
+        const h2r_verify_plan_entry &e = cfg->eval_plan[j];
+        if (e.group == VF_G_H || !exists(e.group, e.index) || e.mask == 0 || e.mask > 15 || e.reserved || a.ev_mask[e.group][e.index]) return H2R_E_SHAPE;
+        a.ev_mask[e.group][e.index] = e.mask; a.ev_first[e.group][e.index] = (unsigned short)q;
+        q += (u32)__builtin_popcount(e.mask);
+    }
+    for (u32 g = 0; g < VF_GROUPS; ++g)
+        for (u32 i = 0; i < VF_MAX_INDEX; ++i) if ((a.ev_mask[g][i] & need[g][i]) != need[g][i]) return H2R_E_SHAPE;
+    num_evals = q;
+    // the base order
+    u32 pos = 5, rank = 0;
+    for (u32 c = 0; c < 5; ++c) a.base_pos[VF_G_ADVICE][c] = (unsigned short)c;
+    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k)
+        if ((cfg->lookup_mask >> k) & 1u) {
+            a.base_pos[VF_G_LOOKUP_A][k] = (unsigned short)(pos + 2 * rank); a.base_pos[VF_G_LOOKUP_S][k] = (unsigned short)(pos + 2 * rank + 1);
+            a.base_pos[VF_G_LOOKUP_Z][k] = (unsigned short)(pos + 2 * A + S + rank);
+            ++rank;
+        }
+    pos += 2 * A;
+    for (u32 s = 0; s < S; ++s) a.base_pos[VF_G_PERM_Z][s] = (unsigned short)(pos + s);
+    pos += S + A;
+    a.base_pos[VF_G_RANDOM][0] = (unsigned short)pos; a.base_pos[VF_G_H][0] = (unsigned short)(pos + 1);
+    a.w_pos = pos + 1 + VF_H_PIECES;
+    pos = a.w_pos + VF_POINT_SETS;
+    for (u32 i = 0; i < F; ++i) a.base_pos[VF_G_FIXED][i] = (unsigned short)(pos + i);
+    for (u32 c = 0; c < m; ++c) a.base_pos[VF_G_SIGMA][c] = (unsigned short)(pos + F + c);
+    a.g_pos = pos + F + m; a.num_bases = a.g_pos + 1;
+    bool seen[VF_GROUPS][VF_MAX_INDEX] = {};
+    for (u32 j = 0; j < cfg->num_open_plan; ++j) {
+        const h2r_verify_plan_entry &e = cfg->open_plan[j];
+        if (!exists(e.group, e.index) || e.mask == 0 || e.mask > 15 || e.reserved || seen[e.group][e.index]) return H2R_E_SHAPE;
+        if (e.group == VF_G_H ? e.mask != 1 : (e.mask & ~a.ev_mask[e.group][e.index]) != 0) return H2R_E_SHAPE;
+        seen[e.group][e.index] = true;
+        a.open[j] = VfPlanEntry{e.group, e.index, e.mask, 0};
+    }
+    a.num_open = cfg->num_open_plan;
+    if (!ctx) return H2R_OK;
+    const FieldConsts &f = ctx->fc;
+    if (ge_p(cfg->omega, f.p) || ge_p(cfg->delta, f.p)) return H2R_E_SHAPE;
+    const Fe omega = cfg_to_mont(ctx, cfg->omega);
+    if (!is_primitive_root(omega, cfg->log_n, f)) return H2R_E_SHAPE;
+    auto inv = [&](const Fe &x) { return fe_to_mont(fe_inv(fe_from_mont(x, f), f), f); };
+    const Fe wi = inv(omega);
+    a.zmul[VF_P_CUR] = fe_one(f); a.zmul[VF_P_NEXT] = omega; a.zmul[VF_P_PREV] = wi;
+    a.zmul[VF_P_LAST] = wi;
+    for (u32 i = 0; i < cfg->blinding_factors; ++i) a.zmul[VF_P_LAST] = fe_mont_mul(a.zmul[VF_P_LAST], wi, f);
+    {   // n = 2^log_n by doublings of 1
+        Fe n = fe_one(f);
+        for (u32 l = 0; l < cfg->log_n; ++l) n = fe_add(n, n, f.p);
+        a.ninv = inv(n);
+    }
+    fe_power_table(a.dpow, QUOT_PERM_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), f);
+    a.f = f; a.mont = ctx_mont(ctx) ? 1u : 0u;
+    return H2R_OK;
+}
+}  // namespace
+
+int32_t h2r_proof_decode(const h2r_ctx *ctx, const h2r_proof_decode_config *cfg, const h2r_proof_section *sections, const void *proof,
+                         uint64_t proof_stride, uint64_t batch, void *points, uint64_t points_stride, void *scalars, uint64_t scalars_stride,
+                         uint8_t *status, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !sections || !proof) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_proof_decode_config)) return H2R_E_UNSUPPORTED;
+    DecodeArgs da;
+    std::memset(static_cast<void *>(&da), 0, sizeof da);
+    u32 np = 0, ns = 0;
+    if (cfg->num_sections && cfg->num_sections <= VF_MAX_SECTIONS)   // (a section of a kind needs that kind's output: before the shape)
+        for (u32 s = 0; s < cfg->num_sections; ++s)
+            if ((sections[s].kind == VF_POINT && !points) || (sections[s].kind == VF_SCALAR && !scalars)) return H2R_E_NULL;
+    if (const int32_t rc = decode_sections(cfg, sections, da, np, ns)) return rc;
+    const u64 p_bytes = 32ull * da.num_items, pt_bytes = 64ull * np, sc_bytes = 32ull * ns;
+    if (misaligned(proof, proof_stride) || (np && misaligned(points, points_stride)) || (ns && misaligned(scalars, scalars_stride))) return H2R_E_SHAPE;
+    if ((proof_stride ? proof_stride < p_bytes : batch > 1) || (np && points_stride < pt_bytes) || (ns && scalars_stride < sc_bytes)) return H2R_E_SHAPE;
+    if (batch) {
+        struct Range { const void *p; u128 n; };
+        const Range in{proof, (u128)(batch - 1) * proof_stride + p_bytes};
+        const Range outs[3] = {{np ? points : nullptr, (u128)(batch - 1) * points_stride + pt_bytes}, {ns ? scalars : nullptr, (u128)(batch - 1) * scalars_stride + sc_bytes},
+                               {status, (u128)batch}};
+        for (u32 x = 0; x < 3; ++x) {
+            if (!outs[x].p) continue;
+            if (overlaps(outs[x].p, outs[x].n, in.p, in.n)) return H2R_E_SHAPE;
+            for (u32 y = x + 1; y < 3; ++y)
+                if (outs[y].p && overlaps(outs[x].p, outs[x].n, outs[y].p, outs[y].n)) return H2R_E_SHAPE;
+        }
+    }
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    da.proof = static_cast<const u8 *>(proof); da.proof_stride = proof_stride;
+    da.points = static_cast<u8 *>(points); da.points_stride = points_stride; da.scalars = static_cast<u8 *>(scalars); da.scalars_stride = scalars_stride;
+    da.status = status; da.batch = batch;
+    sqrt_exponent(cv->fq, da.sqrt_exp);
+    da.b3 = cv->b3;
+    da.c = transcript_consts(ctx, *cv);
+    const u64 blocks = (batch + VF_LANES - 1) / VF_LANES, per = slice_items(da.num_items, blocks);   // (workgroups of 64 counted as of 256; the items are grid.y)
+    if (!per) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    for (da.pass = 0; da.pass < 2; ++da.pass)
+        if (const int32_t rc = for_each_slice(blocks, per, [&](u64 b0, u64 nb) {
+                da.block0 = (u32)b0;
+                return stage_launch(H2R_KERNEL_PROOF_DECODE, st, [&](hipEvent_t a, hipEvent_t b) { return launch_proof_decode(da, (u32)nb, st, a, b); });
+            })) return rc;
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+uint32_t h2r_verify_bases(const h2r_verify_scalars_config *cfg, uint32_t *num_evals) try {
+    if (!cfg) return 0;
+    VerifyScalarsArgs a;
+    std::memset(static_cast<void *>(&a), 0, sizeof a);
+    u32 q = 0;
+    if (verify_scalars_args(nullptr, cfg, a, q) != H2R_OK) return 0;
+    if (num_evals) *num_evals = q;
+    return a.num_bases;
+} H2R_CATCH_ZERO
+
+int32_t h2r_verify_scalars(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, const void *evals, uint64_t evals_stride,
+                           const h2r_verify_challenges *challenges, uint64_t batch, void *right, uint64_t right_stride, void *left,
+                           uint8_t *status, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !evals || !challenges || !right || !left) return H2R_E_NULL;
+    const uint64_t *ch[7] = {challenges->theta, challenges->beta, challenges->gamma, challenges->y, challenges->x, challenges->v, challenges->u};
+    for (const uint64_t *c : ch) if (!c) return H2R_E_NULL;
+    if (!curve_of_field(ctx->params.field)) return H2R_E_UNSUPPORTED;
+    VerifyScalarsArgs va;
+    std::memset(static_cast<void *>(&va), 0, sizeof va);
+    u32 num_evals = 0;
+    if (const int32_t rc = verify_scalars_args(ctx, cfg, va, num_evals)) return rc;
+    const u64 e_bytes = 32ull * num_evals, r_bytes = 32ull * va.num_bases;
+    if (misaligned(evals, evals_stride) || misaligned(right, right_stride) || misaligned(left)) return H2R_E_SHAPE;
+    for (const uint64_t *c : ch) if (misaligned(c)) return H2R_E_SHAPE;
+    if ((evals_stride ? evals_stride < e_bytes : batch > 1) || right_stride < r_bytes) return H2R_E_SHAPE;
+    if (batch) {
+        struct Range { const void *p; u128 n; };
+        const Range outs[3] = {{right, (u128)(batch - 1) * right_stride + r_bytes}, {left, (u128)batch * 128}, {status, (u128)batch}};
+        for (u32 x = 0; x < 3; ++x) {
+            if (!outs[x].p) continue;
+            if (overlaps(outs[x].p, outs[x].n, evals, (u128)(batch - 1) * evals_stride + e_bytes)) return H2R_E_SHAPE;
+            for (const uint64_t *c : ch) if (overlaps(outs[x].p, outs[x].n, c, (u128)batch * 32)) return H2R_E_SHAPE;
+            for (u32 y = x + 1; y < 3; ++y)
+                if (outs[y].p && overlaps(outs[x].p, outs[x].n, outs[y].p, outs[y].n)) return H2R_E_SHAPE;
+        }
+    }
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    va.evals = static_cast<const u8 *>(evals); va.evals_stride = evals_stride;
+    for (int k = 0; k < 7; ++k) va.ch[k] = ch[k];
+    va.right = static_cast<u8 *>(right); va.right_stride = right_stride; va.left = static_cast<u8 *>(left); va.status = status; va.batch = batch;
+    const u64 blocks = (batch + VF_LANES - 1) / VF_LANES;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return for_each_slice(blocks, slice_items(1, blocks), [&](u64 b0, u64 nb) {
+        va.block0 = (u32)b0;
+        return stage_launch(H2R_KERNEL_VERIFY_SCALARS, st, [&](hipEvent_t a, hipEvent_t b) { return launch_verify_scalars(va, (u32)nb, st, a, b); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_msm_terms(const h2r_ctx *ctx, const h2r_msm_terms_config *cfg, const void *scalars, uint64_t scalars_elem_stride, const void *bases,
+                      uint64_t bases_elem_stride, uint64_t batch, void *out, uint8_t *status, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !scalars || !bases || !out) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_msm_terms_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->num_terms == 0 || cfg->num_terms > VF_MAX_TERMS || cfg->reserved) return H2R_E_SHAPE;
+    const u64 s_bytes = 32ull * cfg->num_terms, b_bytes = 64ull * cfg->num_terms;
+    if (misaligned(scalars, scalars_elem_stride) || misaligned(bases, bases_elem_stride) || misaligned(out)) return H2R_E_SHAPE;
+    if ((scalars_elem_stride && scalars_elem_stride < s_bytes) || (bases_elem_stride && bases_elem_stride < b_bytes)) return H2R_E_SHAPE;
+    if (batch) {
+        const u128 o_bytes = (u128)batch * 64;
+        if (overlaps(out, o_bytes, scalars, (u128)(batch - 1) * scalars_elem_stride + s_bytes) ||
+            overlaps(out, o_bytes, bases, (u128)(batch - 1) * bases_elem_stride + b_bytes) || (status && overlaps(out, o_bytes, status, (u128)batch))) return H2R_E_SHAPE;
+    }
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    if (batch > 0xffffffffull) return H2R_E_UNSUPPORTED;
+    MsmTermsArgs ma;
+    std::memset(static_cast<void *>(&ma), 0, sizeof ma);
+    ma.scalars = static_cast<const u8 *>(scalars); ma.s_elem_stride = scalars_elem_stride;
+    ma.bases = static_cast<const u8 *>(bases); ma.b_elem_stride = bases_elem_stride;
+    ma.out = static_cast<u8 *>(out); ma.status = status; ma.T = cfg->num_terms; ma.mont = ctx_mont(ctx) ? 1u : 0u;
+    ma.fr = ctx->fc; ma.cv = *cv;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return for_each_slice(batch, slice_items(1, batch), [&](u64 e0, u64 ne) {
+        ma.elem0 = (u32)e0;
+        return stage_launch(H2R_KERNEL_MSM_TERMS, st, [&](hipEvent_t a, hipEvent_t b) { return launch_msm_terms(ma, (u32)ne, st, a, b); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_verify_eval(const h2r_ctx *ctx, uint32_t op, const h2r_verify_scalars_config *cfg, const uint8_t *in, uint64_t in_len, uint8_t *out,
+                        uint64_t out_len) try {
+    if (!ctx || !in || !out || (op == 1 && !cfg)) return H2R_E_NULL;
+    if (op > 2) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    const u32 mont = ctx_mont(ctx) ? 1u : 0u;
+    if (op == 0) {          // one item: both passes of the kernel
+        if (in_len != 33 || (in[0] != VF_POINT && in[0] != VF_SCALAR) || out_len != (in[0] == VF_POINT ? 64u : 32u)) return H2R_E_SHAPE;
+        const TrConsts c = transcript_consts(ctx, *cv);
+        const Fe raw = vf_ld(in + 1);
+        if (const u32 bad = vf_item_range(in[0], raw, c)) return (int32_t)bad;
+        if (in[0] == VF_SCALAR) { vf_st(out, vf_decode_scalar(raw, c)); return H2R_OK; }
+        u64 e[4];
+        sqrt_exponent(cv->fq, e);
+        Fe x, y;
+        if (const u32 bad = vf_decode_point(raw, e, cv->b3, c, x, y)) return (int32_t)bad;
+        vf_st(out, x); vf_st(out + 32, y);
+    } else if (op == 1) {   // the scalars of one circuit
+        VerifyScalarsArgs va;
+        std::memset(static_cast<void *>(&va), 0, sizeof va);
+        u32 num_evals = 0;
+        if (const int32_t rc = verify_scalars_args(ctx, cfg, va, num_evals)) return rc;
+        if (in_len != 32ull * (7 + num_evals) || out_len != 32ull * (va.num_bases + VF_POINT_SETS)) return H2R_E_SHAPE;
+        u64 ch[7][4];
+        std::memcpy(ch, in, sizeof ch);
+        for (int k = 0; k < 7; ++k) va.ch[k] = ch[k];
+        va.batch = 1;
+        Fe tmp[VF_MAX_INV];
+        std::vector<u8> right(32ull * va.num_bases), left(128);   // (a status leaves `out` untouched, as the kernel leaves its rows)
+        if (const u32 bad = vf_scalars(va, 0, in + 224, right.data(), left.data(), VfStore{tmp, 1})) return (int32_t)bad;
+        std::memcpy(out, right.data(), right.size()); std::memcpy(out + right.size(), left.data(), 128);
+    } else {                // sum s_t P_t as a lane forms it, then the workgroup's additions
+        if (in_len == 0 || in_len % 96 || in_len / 96 > VF_MAX_TERMS || out_len != 64) return H2R_E_SHAPE;
+        PtProj acc = pt_identity(*cv);
+        for (u64 t = 0; t < in_len / 96; ++t) acc = pt_add(acc, vf_term(in + t * 96, in + t * 96 + 32, mont, ctx->fc, *cv), *cv);
+        vf_store_sum(out, acc, mont, *cv);
+    }
     return H2R_OK;
 } H2R_CATCH_STATUS
 

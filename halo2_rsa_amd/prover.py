@@ -1,5 +1,5 @@
 """The prover stages on the device: halo2's lookup and permutation arguments, the evaluation domain (transforms, quotient, openings) and
-the commitment key, the Fiat-Shamir transcript that joins them, the generator of the blinding values, and create_proof, which runs them in halo2's order.  None of them has a counterpart in the reference's `big_integer`
+the commitment key, the Fiat-Shamir transcript that joins them, the generator of the blinding values, create_proof, which runs them in halo2's order, and verify_proof, the verifier up to the pairing.  None of them has a counterpart in the reference's `big_integer`
 module; `big_integer` re-exports the five classes.
 All arithmetic happens in libh2r.so; every method marshals its arguments with `_marshal` and makes the call.
 A chip is whatever has `_ctx`, `_stream()`, `device` and `montgomery` (big_integer.BigIntChip)."""
@@ -623,14 +623,8 @@ class ProvingKey:
             wl = dom._field(_lib.FIELD_MUL, wl, wi)
         rep = (lambda v: dom._field(_lib.FIELD_TO_MONTGOMERY, v)) if mont else (lambda v: v)
         self.derive = [(0, dom.omega, 0), (0, rep(wl), 0), (0, rep(wi), 0), (0, dom.one, dom.k)]
-        # the evaluations in transcript order and the GWC query list: (group, index, point mask); point sets x, omega x, omega^-(bf+1) x, omega^-1 x
         S, A = self.pa.sets, self.lookup_args
-        adv = [("advice", c, 3 if c == 4 else 1) for c in range(5)]
-        fx, sg = [("fixed", i, 1) for i in range(fixed.shape[0])], [("sigma", c, 1) for c in range(sigma.shape[0])]
-        pz = [("perm_z", s, 3 | (4 if s < S - 1 else 0)) for s in range(S)]
-        lk = [q for a in A for q in (("lookup_z", a, 3), ("lookup_a_perm", a, 9), ("lookup_s_perm", a, 1))]
-        self.eval_plan = adv + fx + [("random", 0, 1)] + sg + pz + lk
-        self.open_plan = adv + pz + lk + fx + sg + [("h", 0, 1), ("random", 0, 1)]
+        self.eval_plan, self.open_plan = _plans(fixed.shape[0], sigma.shape[0], S, A)
         self.num_evals = sum(bin(m).count("1") for _, _, m in self.eval_plan)
         self.proof_bytes = 32 * (5 + 2 * len(A) + S + len(A) + 1 + self.h_pieces + self.num_evals + 4)
 
@@ -723,3 +717,197 @@ def create_proof(key: ProvingKey, image: torch.Tensor, batch: int, seed: Optiona
         tr.write_points(key.ck.commit(split(W), status=st), status=st)
         proof[g0:g0 + B] = tr.proof()
     return proof, status
+
+
+# ---- the verifier up to the pairing -----------------------------------------------------------------------------------
+TAG_COMBINE = 6 * 256                      # the generator's tag of combine's rho: kind 6, one row per circuit
+
+
+def _plans(num_fixed: int, num_sigma: int, sets: int, lookup_args):
+    """(eval_plan, open_plan): the evaluations in transcript order and the GWC query list, as (group, index, point mask); the point sets
+    are x, omega x, omega^-(bf+1) x, omega^-1 x."""
+    adv = [("advice", c, 3 if c == 4 else 1) for c in range(5)]
+    fx, sg = [("fixed", i, 1) for i in range(num_fixed)], [("sigma", c, 1) for c in range(num_sigma)]
+    pz = [("perm_z", s, 3 | (4 if s < sets - 1 else 0)) for s in range(sets)]
+    lk = [q for a in lookup_args for q in (("lookup_z", a, 3), ("lookup_a_perm", a, 9), ("lookup_s_perm", a, 1))]
+    return adv + fx + [("random", 0, 1)] + sg + pz + lk, adv + pz + lk + fx + sg + [("h", 0, 1), ("random", 0, 1)]
+
+
+def _points_tensor(t, count: int, dev) -> torch.Tensor:
+    """uint8 [count, 64] on `dev` of points given as int64 [..., count, 2, 4] / [2, 4] or uint8 [..., count, 64] / [64]."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in (torch.int64, torch.uint8) or t.numel() * t.element_size() != 64 * count:
+        check(_lib.H2R_E_SHAPE, "VerifyingKey")
+    return t.to(dev).contiguous().view(torch.uint8).reshape(count, 64)
+
+
+class VerifyingKey:
+    """What verify_proof needs of one circuit shape, held on the device: the constraint system's configuration and
+    the two plans (h2r_verify_scalars' config), the proof's section list, the commitments of the fixed and sigma columns followed by G --
+    the key's tail of the base order --, and the caller's vk_repr.  Constructible from commitments alone: a verifier holds no columns.
+    dom: the EvaluationDomain (k, omega); fixed_commitments / sigma_commitments: F and m affine points (int64 [F, 2, 4] or uint8 [F, 64],
+    a leading batch dimension of 1 is taken as it comes from CommitKey.commit); g: the commit key's first base; delta, vk_repr: integers
+    in the chip's representation.  ProvingKey.verifying_key() builds one from a proving key."""
+
+    def __init__(self, chip, dom: EvaluationDomain, fixed_commitments: torch.Tensor, sigma_commitments: torch.Tensor, g: torch.Tensor, blinding_factors: int,
+                 delta: int, gate_fixed: Sequence[int], column_src: Sequence[int], chunk_len: int, lookup_advice: Sequence[int], lookup_tag: Sequence[int],
+                 lookup_enable: Sequence[int], table_tag: int, table_value: int, vk_repr: int, lookup_mask: int = 31, h_pieces: int = 4):
+        dev = "cuda:%d" % chip.device
+        F, m = int(fixed_commitments.numel() * fixed_commitments.element_size() // 64), len(column_src)
+        if (h_pieces != 4 or len(gate_fixed) != 9 or not 0 < m <= _lib.H2R_PERM_MAX_COLUMNS or chunk_len < 1 or
+                any(len(x) != _lib.H2R_LOOKUP_ARGS for x in (lookup_advice, lookup_tag, lookup_enable))):
+            check(_lib.H2R_E_SHAPE, "VerifyingKey")
+        self.chip, self.dom, self.h_pieces = chip, dom, 4
+        self.lookup_args = [a for a in range(LookupArgument.ARGS) if (lookup_mask >> a) & 1]
+        chunk = min(int(chunk_len), m)
+        S, A = (m + chunk - 1) // chunk, len(self.lookup_args)
+        self.eval_plan, self.open_plan = _plans(F, m, S, self.lookup_args)
+        self.cfg = cfg = _lib.H2RVerifyScalarsConfig(struct_size=ctypes.sizeof(_lib.H2RVerifyScalarsConfig), log_n=dom.k, blinding_factors=blinding_factors,
+                                                     num_fixed=F, num_columns=m, chunk_len=chunk_len, lookup_mask=lookup_mask,
+                                                     num_eval_plan=len(self.eval_plan), num_open_plan=len(self.open_plan), reserved=0)
+        if max(len(self.eval_plan), len(self.open_plan)) > _lib.H2R_VERIFY_MAX_PLAN:
+            check(_lib.H2R_E_SHAPE, "VerifyingKey")
+        set_words(cfg.omega, dom.omega)
+        set_words(cfg.delta, delta)
+        for i, v in enumerate(gate_fixed):
+            cfg.gate_fixed[i] = int(v)
+        for c, s in enumerate(column_src):
+            cfg.column_src[c] = int(s)
+        for k in range(_lib.H2R_LOOKUP_ARGS):
+            cfg.lookup_advice[k], cfg.lookup_tag[k], cfg.lookup_enable[k] = int(lookup_advice[k]), int(lookup_tag[k]), int(lookup_enable[k])
+        cfg.table_tag, cfg.table_value = int(table_tag), int(table_value)
+        for table, plan in ((cfg.eval_plan, self.eval_plan), (cfg.open_plan, self.open_plan)):
+            for entry, (group, index, mask) in zip(table, plan):
+                entry.group, entry.index, entry.mask, entry.reserved = _lib.VERIFY_GROUPS.index(group), index, mask, 0
+        num_evals = ctypes.c_uint32(0)
+        self.num_bases = int(lib().h2r_verify_bases(ctypes.byref(cfg), ctypes.byref(num_evals)))
+        if self.num_bases == 0:
+            check(_lib.H2R_E_SHAPE, "h2r_verify_bases")
+        self.num_evals = int(num_evals.value)
+        # the proof's sections, in order: (name, kind, count)
+        self.sections = [("advice", Transcript.POINT, 5), ("lookup_perm", Transcript.POINT, 2 * A), ("perm_z", Transcript.POINT, S),
+                         ("lookup_z", Transcript.POINT, A), ("random", Transcript.POINT, 1), ("h", Transcript.POINT, self.h_pieces),
+                         ("evals", Transcript.SCALAR, self.num_evals), ("w", Transcript.POINT, 4)]
+        self.sections = [s for s in self.sections if s[2]]
+        self.num_points = sum(c for _, kind, c in self.sections if kind == Transcript.POINT)
+        self.proof_bytes = 32 * (self.num_points + self.num_evals)
+        self.w_pos = self.num_points - 4
+        assert self.num_bases == self.num_points + F + m + 1
+        self.key_bases = torch.cat([_points_tensor(fixed_commitments, F, dev), _points_tensor(sigma_commitments, m, dev), _points_tensor(g, 1, dev)])
+        self.vk = challenges([vk_repr], dev)
+
+
+def _verifying_key(self: ProvingKey) -> VerifyingKey:
+    """The verifying half of this key: the commitments of the fixed and sigma columns, formed once with the Lagrange key."""
+    fixed = self.lk.commit([self.fixed_lag[i] for i in range(self.fixed_lag.shape[0])])
+    sigma = self.lk.commit([self.sigma_lag[c] for c in range(self.sigma_lag.shape[0])])
+    return VerifyingKey(self.chip, self.dom, fixed, sigma, self.ck.bases[0],self.blinding_factors, self.delta, self.gate_fixed, self.column_src, self.chunk_len,
+                        self.lookup["lookup_advice"], self.lookup["lookup_tag"], self.lookup["lookup_enable"], self.lookup["table_tag"],
+                        self.lookup["table_value"], from_words(self.vk[0].tolist()), lookup_mask=self.lookup["lookup_mask"], h_pieces=self.h_pieces)
+
+
+ProvingKey.verifying_key = _verifying_key
+
+
+def msm_terms(chip, scalars: torch.Tensor, bases: torch.Tensor, num_terms: int, batch: int, scalars_stride: int, bases_stride: int, out: torch.Tensor,
+              status: Optional[torch.Tensor] = None, scalars_off: int = 0, bases_off: int = 0) -> torch.Tensor:
+    """out[e] = sum_{t < num_terms} s[e][t] * P[e][t] (h2r_msm_terms): uint8 [batch, 64] affine, (0, 0) for the identity.  Term t of circuit e:
+    32 bytes at scalars + scalars_off + e * scalars_stride + 32 t, 64 bytes at bases + bases_off + e * bases_stride + 64 t (a stride of 0:
+    one copy the batch shares); both in the chip's representation, any 256-bit scalar."""
+    if (not 0 < num_terms <= _lib.H2R_VERIFY_MAX_TERMS or scalars.numel() * scalars.element_size() < scalars_off + (batch - 1) * scalars_stride + 32 * num_terms or
+            bases.numel() * bases.element_size() < bases_off + (batch - 1) * bases_stride + 64 * num_terms or out.numel() * out.element_size() != 64 * batch):
+        check(_lib.H2R_E_SHAPE, "msm_terms")      # (no assert: a short buffer must never reach the kernel)
+    assert scalars.is_contiguous() and bases.is_contiguous() and out.is_contiguous()
+    cfg = _lib.H2RMsmTermsConfig(struct_size=ctypes.sizeof(_lib.H2RMsmTermsConfig), num_terms=num_terms, reserved=0)
+    check(lib().h2r_msm_terms(chip._ctx, ctypes.byref(cfg), scalars.data_ptr() + scalars_off, scalars_stride, bases.data_ptr() + bases_off, bases_stride,
+                              batch, out.data_ptr(), ptr(status), chip._stream()), "h2r_msm_terms")
+    return out
+
+
+def verify_proof(vk: VerifyingKey, proofs: torch.Tensor, instances: Optional[torch.Tensor] = None, out=None):
+    """(left, right, status): halo2's verify_proof (KZG, GWC) up to the pairing, for `batch` independent one-circuit proofs (DESIGN.md
+    section 2n), with no host synchronisation.  proofs: uint8 [batch, vk.proof_bytes] on the device; instances: int64 [batch, I, 4],
+    absorbed as common scalars.  left / right: uint8 [batch, 64], the affine accumulators L and R in the chip's representation: circuit e
+    is ACCEPTED iff e(left[e], [tau]G2) = e(right[e], G2) -- the pairing is the caller's, once per batch over combine()'s fold.  status
+    uint8 [batch]: H2R_E_SHAPE for a scalar >= r, an abscissa >= q or an instance that is not canonical, H2R_E_ASSERTION for an abscissa of
+    no point or x^n = 1; a flagged circuit's left / right are left as they were (zeros when the call allocates).  out: (left, right,
+    status) to write into; a status byte that is nonzero on entry skips the circuit; the call never clears it."""
+    chip = vk.chip
+    if proofs.dtype != torch.uint8 or proofs.dim() != 2 or proofs.shape[1] != vk.proof_bytes or proofs.shape[0] < 1 or not proofs.is_cuda:
+        check(_lib.H2R_E_SHAPE, "verify_proof")
+    assert proofs.is_contiguous()
+    batch, dev, NB, NE = int(proofs.shape[0]), proofs.device, vk.num_bases, vk.num_evals
+    left, right, status = outputs(out, dev, (torch.zeros, torch.uint8, (batch, 64)), (torch.zeros, torch.uint8, (batch, 64)), status=batch)
+    # 1. decode: the proof's points at the head of every circuit's bases, the key's commitments and G behind them
+    bases = torch.empty((batch, NB, 64), dtype=torch.uint8, device=dev)
+    bases[:, vk.num_points:] = vk.key_bases
+    evals = torch.empty((batch, NE, 32), dtype=torch.uint8, device=dev)
+    sec = (_lib.H2RProofSection * len(vk.sections))()
+    for d, (_, kind, count) in zip(sec, vk.sections):
+        d.kind, d.count = _lib.H2R_TRANSCRIPT_POINT if kind == Transcript.POINT else _lib.H2R_TRANSCRIPT_SCALAR, count
+    dcfg = _lib.H2RProofDecodeConfig(struct_size=ctypes.sizeof(_lib.H2RProofDecodeConfig), num_sections=len(vk.sections), reserved=0)
+    check(lib().h2r_proof_decode(chip._ctx, ctypes.byref(dcfg), sec, proofs.data_ptr(), proofs.stride(0), batch, bases.data_ptr(), NB * 64,
+                                 evals.data_ptr(), NE * 32, status.data_ptr(), chip._stream()), "h2r_proof_decode")
+    # 2. the prover's rounds as common rounds, one more after the four W
+    at, off = {}, 0
+    for name, kind, count in vk.sections:
+        if kind == Transcript.POINT:
+            at[name] = (bases[:, off:off + count], Transcript.POINT)
+            off += count
+    tr = Transcript(chip, batch, 0)
+    tr.round([(vk.vk, tr.SCALAR)] + ([(instances, tr.SCALAR)] if instances is not None and instances.shape[1] else []), common=True, status=status)
+
+    def draw(names, squeeze):
+        return tr.round([at[nm] for nm in names if nm in at], squeeze, common=True, status=status)[0]
+
+    theta, bg = draw(["advice"], 1)[:, 0], draw(["lookup_perm"], 2)
+    y, x = draw(["perm_z", "lookup_z", "random"], 1)[:, 0], draw(["h"], 1)[:, 0]
+    v = tr.round([(evals, tr.SCALAR)], 1, common=True, status=status)[0][:, 0]
+    u = draw(["w"], 1)[:, 0]
+    # 3. the scalars of R (one per base) and of L (u^p over the four W)
+    ch = _lib.H2RVerifyChallenges()
+    held = [challenges(c, dev, batch) for c in (theta, bg[:, 0], bg[:, 1], y, x, v, u)]
+    for name, c in zip(ch.NAMES, held):
+        setattr(ch, name, c.data_ptr())
+    rs = torch.empty((batch, NB, 32), dtype=torch.uint8, device=dev)
+    ls = torch.empty((batch, 4, 32), dtype=torch.uint8, device=dev)
+    check(lib().h2r_verify_scalars(chip._ctx, ctypes.byref(vk.cfg), evals.data_ptr(), NE * 32, ctypes.byref(ch), batch, rs.data_ptr(), NB * 32,
+                                   ls.data_ptr(), status.data_ptr(), chip._stream()), "h2r_verify_scalars")
+    # 4. R over all the bases, L over the four W where they lie among them
+    msm_terms(chip, rs, bases, NB, batch, NB * 32, NB * 64, right, status)
+    msm_terms(chip, ls, bases, 4, batch, 128, NB * 64, left, status, bases_off=vk.w_pos * 64)
+    hold(vk, "verify_proof", proofs, instances, bases, evals, held, rs, ls, tr, left, right, status)
+    return left, right, status
+
+
+def combine(left: torch.Tensor, right: torch.Tensor, status: torch.Tensor, seed: bytes, chip):
+    """(L*, R*), uint8 [64] each: the batch folded into ONE pair, L* = sum_e rho_e left[e] and R* = sum_e rho_e right[e], so that the
+    caller's one pairing check e(L*, [tau]G2) = e(R*, G2) accepts every circuit whose status is 0 TOGETHER (a circuit with a nonzero
+    status gets rho_e = 0 on the device and its points are not read: it is dropped, and stays rejected by its status).  rho_e is the
+    generator's element (seed, circuit e, TAG_COMBINE, row 0) (h2r_random_columns).  `seed` (32 bytes) MUST BE UNKNOWN TO WHOEVER MADE THE
+    PROOFS -- draw it after the proofs exist: one who knows rho can make two bad proofs whose errors cancel in the fold.  A batch above
+    4,096 is summed in chunks of 4,096, and the chunks' sums once more."""
+    batch, dev = int(left.shape[0]), left.device
+    if len(seed) != 32 or batch < 1 or tuple(left.shape) != (batch, 64) or tuple(right.shape) != (batch, 64) or tuple(status.shape) != (batch,):
+        check(_lib.H2R_E_SHAPE, "combine")
+    rho = torch.zeros((batch, 1, 32), dtype=torch.uint8, device=dev)
+    random_columns(chip, [rho], [TAG_COMBINE], (0, 1), seed)
+    flagged = (status != 0)
+    rho = torch.where(flagged[:, None, None], torch.zeros_like(rho), rho).reshape(batch, 32).contiguous()
+    CH = _lib.H2R_VERIFY_MAX_TERMS
+    chunks = (batch + CH - 1) // CH
+    res = []
+    for pts in (left, right):
+        pts = torch.where(flagged[:, None], torch.zeros_like(pts), pts).contiguous()
+        part = torch.zeros((chunks, 64), dtype=torch.uint8, device=dev)
+        for c in range(chunks):
+            n = min(CH, batch - c * CH)
+            msm_terms(chip, rho, pts, n, 1, 0, 0, part[c], scalars_off=c * CH * 32, bases_off=c * CH * 64)
+        if chunks > 1:
+            wa, wb, one = ((ctypes.c_uint64 * 4)(*words(v)) for v in (1, 0, 1))       # 1 in the chip's representation
+            if chip.montgomery:
+                check(lib().h2r_field_eval(chip._ctx, _lib.FIELD_TO_MONTGOMERY, wa, wb, one), "h2r_field_eval")
+            ones = torch.frombuffer(bytearray(from_words(one).to_bytes(32, "little") * chunks), dtype=torch.uint8).to(dev)
+            part = msm_terms(chip, ones, part, chunks, 1, 0, 0, torch.zeros((1, 64), dtype=torch.uint8, device=dev))
+        res.append(part.reshape(64))
+    hold(chip, "combine", rho, res)
+    return res[0], res[1]

@@ -1214,6 +1214,86 @@ typedef struct h2r_random_config {
 typedef struct h2r_random_column { void *base; uint64_t elem_stride; uint32_t tag, reserved; } h2r_random_column;
 int32_t h2r_random_columns(const h2r_ctx *ctx, const h2r_random_config *cfg, const h2r_random_column *cols, uint64_t batch, h2r_stream_t stream);
 int32_t h2r_random_eval(const h2r_ctx *ctx, const uint8_t seed[32], uint64_t circuit, uint32_t tag, uint64_t row, uint64_t out[4]);
+/* ---- the verifier up to the pairing: proof bytes in, the two pairing accumulators out ------------
+ * THIRD-PARTY behaviour (halo2 plonk::verify_proof with poly::kzg::multiopen::VerifierGWC over Blake2bRead, not in the reference tree),
+ * restated in DESIGN.md section 2n; parity is pinned against a Python restatement (tests/verify_proof_ref.py), NOT against upstream.  A
+ * batch is `batch` independent one-circuit proofs (section 2m).  A proof is accepted iff e(L, [tau]G2) = e(R, G2) with
+ *     L = sum_p u^p W_p        R = sum_p u^p (z_p W_p + sum_i v^i C_{p,i} - [sum_i v^i e_{p,i}] G)
+ * over the point sets p = 0..3 at z_p = x, omega x, omega^-(blinding_factors + 1) x, omega^-1 x, u the challenge drawn after the four W.
+ * G2 and the pairing are NOT here: the caller runs that one check (per batch, after folding: prover.combine).  Only a ctx whose field
+ * has a curve; everything in the ctx's representation; every call enqueues on `stream` and never synchronises; no workgroup waits for
+ * another, no atomics.  status (nullable, [batch]) is never cleared: a circuit whose byte is nonzero on entry is skipped and nothing of
+ * it is written.
+ * h2r_proof_decode: the proof's 32-byte items -> points[e][k] (64 bytes: x then y) and scalars[e][k] (32 bytes), k counting the items of
+ *    that kind in proof order -- ready to be named by h2r_transcript_round items and by the calls below.  sections: a host array of
+ *    (kind, count), H2R_TRANSCRIPT_POINT or H2R_TRANSCRIPT_SCALAR, in proof order.  One lane per (circuit, item).  A point is x with bit 255
+ *    cleared, y = (x^3 + b)^((q+1)/4) where y^2 = x^3 + b, of the parity bit 255 names.  Status: H2R_E_SHAPE for a scalar >= r or an
+ *    abscissa >= q, H2R_E_ASSERTION for an abscissa of no point; H2R_E_SHAPE WINS where both occur in one proof (two launches: ranges
+ *    first).  A circuit flagged BY the call has some of its items written.
+ * h2r_verify_scalars: the verifier's field side, one lane per circuit.  evals[e]: the decoded evaluations in the eval plan's order
+ *    (entry by entry, a column's point sets ascending); the seven challenges [batch][4].  right[e][num_bases][4]: the scalars of R in the
+ *    BASE ORDER -- the proof's points in proof order (5 advice; A' and S' interleaved per selected lookup argument; the S permutation Z;
+ *    the lookup Z; the random polynomial; the 4 pieces of h; W_0..W_3), then the key's num_fixed fixed and num_columns sigma commitments,
+ *    then G: num_bases = h2r_verify_bases(cfg) -- and left[e][4][4] = u^p, the scalars of L over W_0..W_3.  A commitment's scalar sums
+ *    u^p v^i over its queries in the open plan (i counts set p's queries from 0), piece j of h gets its query's times x^(n j), W_p gets
+ *    u^p z_p, G minus the sum of u^p v^i e_{p,i}; the evaluation of h is (the constraint expression at x -- h2r_quotient_columns' terms in
+ *    their order, on evaluations -- folded with y) / (x^n - 1), l0 / l_last / l_active at x in closed form.  Status: H2R_E_SHAPE for a
+ *    challenge >= r, H2R_E_ASSERTION for x^n = 1; nothing is written then.
+ *    cfg: the constraint system as h2r_quotient_config names it (no extra columns), omega of the 2^log_n domain, and the two plans as
+ *    (group, index, mask) entries: group H2R_VERIFY_G_*, index the column (a lookup's: the argument), bit p of mask = point set p.  The
+ *    eval plan holds every evaluation the expression reads (advice 0..4 at set 0, advice 4 also at 1; the fixed columns it names and
+ *    every sigma at 0; a permutation Z at 0 and 1, all but the last also at 2; a lookup's Z at 0 and 1, A' at 0 and 3, S' at 0); an
+ *    open plan entry is an eval plan column at point sets it is evaluated at, or (H2R_VERIFY_G_H, 0): the folded h at set 0.
+ * h2r_msm_terms: out[e] = sum_{t < num_terms} scalars[e][t] * bases[e][t], 64 bytes affine, (0, 0) for the identity; scalars of 32 and
+ *    bases of 64 bytes at base + e * elem_stride, elem_stride = 0 for one copy the batch shares.  Any 256-bit scalar (a Montgomery ctx:
+ *    the integer w * R^-1 mod r), (0, 0) bases are the identity, bases are not validated.  One workgroup per circuit; a lane multiplies
+ *    with fixed 2-bit windows and the complete formulas, so its work does not depend on the scalars.
+ * h2r_verify_eval (host only; works on a host-only ctx) runs the very functions the kernels inline: op 0 = decode one item: in = a kind
+ *    byte and 32 bytes, out = 64 or 32 bytes, the return value the item's status; op 1 = the scalars of one circuit: in = the seven
+ *    challenges (theta, beta, gamma, y, x, v, u) then the evaluations, 32 bytes each, out = right then left, the return value the status;
+ *    op 2 = sum s_t P_t: in = records of a scalar (32) and a base (64), out = 64 bytes.  cfg is read by op 1 only.
+ *  - H2R_E_NULL for a NULL required pointer (status is optional; points / scalars exactly when a section of that kind exists);
+ *    H2R_E_UNSUPPORTED for another struct_size, a field without a curve, a host-only ctx (that one after every other check);
+ *    H2R_E_SHAPE for a nonzero `reserved`, no section or more than 16, a section's kind or a zero count, more than 65,535 items,
+ *    num_terms = 0 or > 4096, a configuration out of range (log_n 1..24, blinding_factors <= 13 and < 2^log_n - 1, num_fixed <= 16,
+ *    num_columns 1..8, chunk_len >= 1, column_src >= 5, an index >= num_fixed, lookup fields as h2r_quotient_columns, omega or delta >= p,
+ *    omega not a primitive 2^log_n-th root, a plan that is empty, longer than 64, repeats a column, names a column that does not exist
+ *    or misses an evaluation), a pointer or stride that is not 16-byte aligned, a nonzero stride smaller than what it holds (a zero
+ *    stride of an output with batch > 1), another in_len / out_len, an output overlapping an input, another output or status.
+ *    batch = 0 returns H2R_OK with no launch. */
+#define H2R_VERIFY_MAX_SECTIONS 16
+#define H2R_VERIFY_MAX_PLAN     64
+#define H2R_VERIFY_MAX_TERMS    4096u
+enum { H2R_VERIFY_G_ADVICE = 0, H2R_VERIFY_G_FIXED = 1, H2R_VERIFY_G_RANDOM = 2, H2R_VERIFY_G_SIGMA = 3, H2R_VERIFY_G_PERM_Z = 4,
+       H2R_VERIFY_G_LOOKUP_Z = 5, H2R_VERIFY_G_LOOKUP_A_PERM = 6, H2R_VERIFY_G_LOOKUP_S_PERM = 7, H2R_VERIFY_G_H = 8 };
+typedef struct h2r_proof_section { uint32_t kind, count; } h2r_proof_section;
+typedef struct h2r_proof_decode_config { uint32_t struct_size, num_sections; uint64_t reserved; } h2r_proof_decode_config;
+typedef struct h2r_verify_plan_entry { uint8_t group, index, mask, reserved; } h2r_verify_plan_entry;
+typedef struct h2r_verify_scalars_config {
+    uint32_t struct_size;              /* sizeof; anything else: H2R_E_UNSUPPORTED */
+    uint32_t log_n, blinding_factors, num_fixed;
+    uint32_t num_columns, chunk_len, lookup_mask;   /* as in h2r_quotient_config */
+    uint32_t num_eval_plan, num_open_plan, reserved;
+    uint64_t omega[4], delta[4];       /* the ctx's representation */
+    uint8_t  gate_fixed[9];
+    uint8_t  column_src[H2R_PERM_MAX_COLUMNS];
+    uint8_t  lookup_advice[H2R_LOOKUP_ARGS], lookup_tag[H2R_LOOKUP_ARGS], lookup_enable[H2R_LOOKUP_ARGS];
+    uint8_t  table_tag, table_value;
+    h2r_verify_plan_entry eval_plan[H2R_VERIFY_MAX_PLAN], open_plan[H2R_VERIFY_MAX_PLAN];
+} h2r_verify_scalars_config;
+typedef struct h2r_verify_challenges { const uint64_t *theta, *beta, *gamma, *y, *x, *v, *u; } h2r_verify_challenges;   /* [batch][4] each, on the device */
+typedef struct h2r_msm_terms_config { uint32_t struct_size, num_terms; uint64_t reserved; } h2r_msm_terms_config;
+int32_t h2r_proof_decode(const h2r_ctx *ctx, const h2r_proof_decode_config *cfg, const h2r_proof_section *sections, const void *proof,
+                         uint64_t proof_stride, uint64_t batch, void *points, uint64_t points_stride, void *scalars, uint64_t scalars_stride,
+                         uint8_t *status, h2r_stream_t stream);
+uint32_t h2r_verify_bases(const h2r_verify_scalars_config *cfg, uint32_t *num_evals);   /* host: num_bases (0: a refused configuration) */
+int32_t h2r_verify_scalars(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, const void *evals, uint64_t evals_stride,
+                           const h2r_verify_challenges *challenges, uint64_t batch, void *right, uint64_t right_stride, void *left,
+                           uint8_t *status, h2r_stream_t stream);
+int32_t h2r_msm_terms(const h2r_ctx *ctx, const h2r_msm_terms_config *cfg, const void *scalars, uint64_t scalars_elem_stride, const void *bases,
+                      uint64_t bases_elem_stride, uint64_t batch, void *out, uint8_t *status, h2r_stream_t stream);
+int32_t h2r_verify_eval(const h2r_ctx *ctx, uint32_t op, const h2r_verify_scalars_config *cfg, const uint8_t *in, uint64_t in_len, uint8_t *out,
+                        uint64_t out_len);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1517,7 +1597,9 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_CURVE_NTT_STORE = 28 /* h2r_curve_ntt's launches: the twiddle table, affine -> projective, the stages, projective -> affine */,
        H2R_KERNEL_TRANSCRIPT = 29 /* transcript_kernel: one round of the Fiat-Shamir transcript */,
        H2R_KERNEL_RANDOM = 30 /* random_kernel: the prover's blinding values */,
-       H2R_KERNEL_COUNT = 31 };
+       H2R_KERNEL_PROOF_DECODE = 31 /* proof_decode_kernel: two launches per call */, H2R_KERNEL_VERIFY_SCALARS = 32 /* verify_scalars_kernel */,
+       H2R_KERNEL_MSM_TERMS = 33 /* msm_terms_kernel */,
+       H2R_KERNEL_COUNT = 34 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
