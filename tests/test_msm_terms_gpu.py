@@ -1,7 +1,7 @@
 """h2r_msm_terms on the device (prover.msm_terms) byte for byte against the plain model (tests/msm_ref.py), bn254_fr
 (bn256 G1) in both representations: out[e] = sum_t s[e][t] P[e][t] over bases that differ per circuit.  Every base has a known discrete
-logarithm (P_i = [A0 + i D]G), so a sum's expectation is ONE scalar multiplication; T runs over the lane stride's wrap (256) and ragged last
-rounds, the scalars and the bases come per circuit or shared, and the output lies between sentinel-filled guards."""
+logarithm (P_i = [A0 + i D]G), so a sum's expectation is ONE scalar multiplication; T runs over the lane stride's wrap (256), ragged last
+rounds and the call's maximum of 4,096 terms, the scalars and the bases come per circuit or shared, and the output lies between sentinel-filled guards."""
 import os
 import random
 import sys
@@ -18,7 +18,7 @@ REPRS, IDS = [False, True], ["canonical", "montgomery"]
 SENTINEL, GUARD = 0xAB, 2
 A0, D = 0x1234567890abcdef1122334455667788, 0x0fedcba987654321ffeeddccbbaa9988
 R = M.R_ORDER
-TS = [1, 2, 63, 64, 65, 255, 256, 257, 600]
+TS = [1, 2, 63, 64, 65, 255, 256, 257, 600, 4096]                               # 4096: the call's maximum, 16 terms per lane
 CACHE = {}
 
 

@@ -2,8 +2,10 @@
 The k = 9 `mul_mod-64x4-bn254` image of tests/test_create_proof_gpu.py as three circuits, a key over [tau^i]G, proofs from create_proof, both
 representations: the accumulators of the accepting batch are byte-equal to the model's on those bytes and satisfy [tau] L = R; one flipped
 bit per proof section in circuit 1 leaves circuits 0 and 2 as they were and makes circuit 1 what the model says (a status, or [tau] L != R);
-a scalar = r, an abscissa = q, an abscissa of no point; a status set on entry; combine; no host access; and the k = 10 recorded circuits of
-tests/test_prover_chain_gpu.py with one changed image cell, judged where the proofs lie.  The model's answers are made once per proof."""
+a scalar = r, an abscissa = q, an abscissa of no point; a status set on entry; combine, also over 4,097 synthetic accumulators (two chunks
+and the sum of the chunks' sums); the three proofs tiled to 65 circuits, a batch across a workgroup of 64, with circuits 63 and 64 changed;
+no host access; and the k = 10 recorded circuits of tests/test_prover_chain_gpu.py with one changed image cell, judged where the proofs
+lie.  The model's answers are made once per proof."""
 import os
 import sys
 
@@ -29,6 +31,8 @@ B = CP.B
 REPRS, IDS = [False, True], ["canonical", "montgomery"]
 SENTINEL = 0xAB
 COMBINE_SEED = bytes(range(60, 92))
+A0, D = 0x2468ace013579bdf0f1e2d3c4b5a6978, 0x13579bdf2468ace08796a5b4c3d2e1f0     # the structured accumulators P_i = [A0 + i D]G
+CHUNK = 4096                                                                     # combine sums a batch in chunks of H2R_VERIFY_MAX_TERMS
 CACHE = {}
 
 
@@ -51,7 +55,7 @@ def model_vk():
 
 
 def model(proof, e):
-    """(status, L, R) of the model on one proof's bytes with circuit e's instances, made once per (bytes, e)."""
+    """(status, L, R) of the model on one proof's bytes with the instances of the key's circuit e, made once per (bytes, e)."""
     if (proof, e) not in CACHE:
         CACHE[(proof, e)] = V.accumulate(model_vk(), proof, INSTANCES[e])
     return CACHE[(proof, e)]
@@ -59,19 +63,20 @@ def model(proof, e):
 
 def run(H, vk, proofs, inst, status_in=None):
     """verify_proof into sentinel-filled outputs -> (left bytes [B][64], right bytes, status list)."""
-    left, right = (torch.full((B, 64), SENTINEL, dtype=torch.uint8, device="cuda") for _ in range(2))
-    status = torch.tensor(status_in or [0] * B, dtype=torch.uint8, device="cuda")
+    batch = int(proofs.shape[0])
+    left, right = (torch.full((batch, 64), SENTINEL, dtype=torch.uint8, device="cuda") for _ in range(2))
+    status = torch.tensor(status_in or [0] * batch, dtype=torch.uint8, device="cuda")
     out = H.prover.verify_proof(vk, proofs, inst, out=(left, right, status))
     torch.cuda.synchronize()
     assert out[0] is left and out[1] is right and out[2] is status
     return [bytes(r) for r in left.cpu().numpy()], [bytes(r) for r in right.cpu().numpy()], status.cpu().tolist()
 
 
-def same_as_model(got, e, proof, montgomery):
+def same_as_model(got, e, proof, montgomery, instances_of=None):
     """Circuit e's (left, right, status) against the model: byte-equal accumulators, or the model's status and untouched outputs.  Returns
-    whether the circuit is accepted."""
+    whether the circuit is accepted.  instances_of: the key's circuit whose instances e carries (e itself where the batch is the key's)."""
     left, right, status = got
-    st, L, Rp = model(proof, e)
+    st, L, Rp = model(proof, e if instances_of is None else instances_of)
     assert status[e] == st, (e, status[e], st)
     if st:
         assert left[e] == right[e] == bytes([SENTINEL]) * 64, "a flagged circuit's accumulators stay as they were"
@@ -175,6 +180,60 @@ def test_combine(H, montgomery):
     assert fold(proofs)                                          # three good circuits: accepted together
     assert not fold(mixed)                                       # the bad circuit unflagged: the one pair rejects
     assert fold(mixed, flag=1)                                   # flagged and dropped: the rest is accepted
+    # two chunks, 4,096 circuits and 1, and the sum of the two sums; then the second chunk's only circuit unflagged, so that its rho and its
+    # points count
+    fold_of_structured_points(H, vk.chip, montgomery, CHUNK + 1, (1234, CHUNK))
+    fold_of_structured_points(H, vk.chip, montgomery, CHUNK + 1, (CHUNK - 1,))
+
+
+def fold_of_structured_points(H, chip, montgomery, batch, flagged):
+    """combine on synthetic accumulators with known logarithms, left[e] = P_e and right[e] = P_(batch + e): the fold is ONE scalar
+    multiplication, L* = [sum rho_e log_e]G.  A flagged circuit's rows hold sentinel bytes, which are no point: they must not count."""
+    if "structured" not in CACHE:
+        CACHE["structured"] = M.structured_bases(2 * (CHUNK + 1), A0, D)
+    pts = CACHE["structured"]
+    assert 2 * batch <= len(pts) and batch > CHUNK and all(e < batch for e in flagged)
+    assert {e // CHUNK for e in flagged} == set(range((batch + CHUNK - 1) // CHUNK)) or len(flagged) == 1
+    sides = []
+    for first in (0, batch):
+        raw = bytearray(M.point_bytes(pts[first:first + batch], montgomery))
+        for e in flagged:
+            raw[64 * e:64 * e + 64] = bytes([SENTINEL]) * 64
+        sides.append(torch.frombuffer(raw, dtype=torch.uint8).reshape(batch, 64).cuda())
+    st = [E_ASSERTION if e in flagged else 0 for e in range(batch)]
+    status = torch.tensor(st, dtype=torch.uint8, device="cuda")
+    before = [t.clone() for t in sides]
+    Ls, Rs = H.prover.combine(sides[0], sides[1], status, COMBINE_SEED, chip)
+    torch.cuda.synchronize()
+    rhos = [0 if s else V.rho(COMBINE_SEED, e) for e, s in enumerate(st)]
+    assert len(set(rhos)) == batch - len(flagged) + 1
+    for got, first, name in ((Ls, 0, "L*"), (Rs, batch, "R*")):
+        want = M.mul_g(sum(rho * (A0 + (first + e) * D) for e, rho in enumerate(rhos)) % R)
+        assert bytes(got.cpu().numpy()) == M.point_bytes([want], montgomery), "%s of %d circuits, flagged %r" % (name, batch, flagged)
+    assert all(torch.equal(a, b) for a, b in zip(sides, before)) and status.cpu().tolist() == st, "combine writes none of its operands"
+
+
+@pytest.mark.parametrize("montgomery", REPRS, ids=IDS)
+def test_a_batch_across_a_workgroup_boundary(H, montgomery):
+    """The three proofs tiled to 65 circuits -- circuit e holds proof e mod 3 under the instances of e mod 3 --, one evaluation bit flipped in
+    circuits 63 (the first workgroup's last lane) and 64 (the second workgroup's only one)."""
+    vk, proofs, inst = setup(H, montgomery)
+    host = [bytes(p) for p in proofs.cpu().numpy()]
+    batch = 65
+    off = sections(CP.model9()[0].cfg)["evals"][0] + 5
+    tiled, tiled_inst = proofs.repeat(22, 1)[:batch].contiguous(), inst.repeat(22, 1, 1)[:batch].contiguous()
+    want = [host[e % B] for e in range(batch)]
+    for e in (63, 64):
+        bad = bytearray(want[e])
+        bad[off] ^= 1
+        want[e] = bytes(bad)
+        tiled = with_bytes(tiled, e, 0, want[e])
+    got = run(H, vk, tiled, tiled_inst)
+    assert [bytes(p) for p in tiled.cpu().numpy()] == want
+    for e in range(batch):
+        accepted = same_as_model(got, e, want[e], montgomery, instances_of=e % B)
+        assert accepted == (e not in (63, 64)), "circuit %d is %s" % (e, "accepted" if accepted else "rejected")
+    assert got[2] == [0] * batch, "a flipped evaluation bit is a rejection without a status"
 
 
 def test_no_host_access(H):

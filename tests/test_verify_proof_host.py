@@ -18,6 +18,7 @@ from halo2_rsa_amd import _lib
 from halo2_rsa_amd._lib import lib
 from test_create_proof_model import INSTANCES, TAU, case   # noqa: F401  (case: the module's fixture, the model proof made once here)
 from test_transcript_host import host_ctx
+from verify_cases import verify_config
 
 Q, R = T.Q, T.R
 NULL, SHAPE, UNSUP, ASSERTION = _lib.H2R_E_NULL, _lib.H2R_E_SHAPE, _lib.H2R_E_UNSUPPORTED, _lib.H2R_E_ASSERTION
@@ -30,24 +31,6 @@ def ctx(request):
     c = host_ctx(request.param)
     yield c, request.param
     lib().h2r_ctx_destroy(c)
-
-
-def verify_config(cfg, montgomery):
-    """h2r_verify_scalars' configuration of a model configuration: the model's own plans, entry by entry."""
-    plans = C.eval_plan(cfg), C.open_plan(cfg)
-    out = _lib.H2RVerifyScalarsConfig(struct_size=ctypes.sizeof(_lib.H2RVerifyScalarsConfig), log_n=cfg.k, blinding_factors=cfg.blinding_factors,
-                                      num_fixed=cfg.num_fixed, num_columns=cfg.m, chunk_len=cfg.chunk_len, lookup_mask=cfg.lookup_mask,
-                                      num_eval_plan=len(plans[0]), num_open_plan=len(plans[1]), reserved=0)
-    out.omega[:] = M.words(T.to_repr(cfg.omega(R), R, montgomery))
-    out.delta[:] = M.words(T.to_repr(cfg.delta, R, montgomery))
-    out.gate_fixed[:] = cfg.gate_fixed
-    out.column_src[:cfg.m] = cfg.column_src
-    out.lookup_advice[:], out.lookup_tag[:], out.lookup_enable[:] = cfg.lookup_advice, cfg.lookup_tag, cfg.lookup_enable
-    out.table_tag, out.table_value = cfg.table_tag, cfg.table_value
-    for table, plan in zip((out.eval_plan, out.open_plan), plans):
-        for entry, (g, i, m) in zip(table, plan):
-            entry.group, entry.index, entry.mask = _lib.VERIFY_GROUPS.index(g), i, m
-    return out
 
 
 def copy_config(c):
