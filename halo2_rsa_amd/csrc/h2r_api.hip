@@ -4052,13 +4052,14 @@ int32_t h2r_lookup_product_columns(const h2r_ctx *ctx, const h2r_lookup_config *
 namespace {
 static_assert(H2R_PERM_MAX_COLUMNS == PERM_MAX_COLUMNS, "h2r.h and the kernels' argument struct");
 // what h2r_permutation_sets answers 0 for: the parts of a configuration that need no ctx (delta and omega are compared with the ctx's p)
-bool perm_cfg_valid(const h2r_permutation_config *cfg) {
+// (once = false: a source may be named by several columns -- the verifier's configuration, which only reads evaluations)
+bool perm_cfg_valid(const h2r_permutation_config *cfg, bool once = true) {
     if (cfg->struct_size != sizeof(h2r_permutation_config)) return false;
     if (cfg->num_columns == 0 || cfg->num_columns > H2R_PERM_MAX_COLUMNS || cfg->chunk_len == 0 || cfg->n_extra > H2R_PERM_MAX_EXTRA) return false;
     u32 seen = 0;
     for (u32 c = 0; c < cfg->num_columns; ++c) {
         const u32 src = cfg->column_src[c];
-        if (src >= 5 + cfg->n_extra || ((seen >> src) & 1u)) return false;
+        if (src >= 5 + cfg->n_extra || (once && ((seen >> src) & 1u))) return false;
         seen |= 1u << src;
     }
     return true;
@@ -4234,39 +4235,50 @@ namespace {
 static_assert(H2R_KERNEL_OPEN_TILES == H2R_KERNEL_QUOTIENT + 1, "h2r.h: the launch classes");
 static_assert(H2R_QUOTIENT_MAX_FIXED == QUOT_MAX_FIXED && H2R_LOOKUP_ARGS == QUOT_LOOKUP_ARGS && H2R_PERM_MAX_COLUMNS == QUOT_PERM_MAX_COLUMNS &&
               sizeof(((h2r_quotient_config *)nullptr)->gate_fixed) == QUOT_GATE_FIXED, "h2r.h and the kernel's argument struct");
-h2r_permutation_config quotient_perm_cfg(const h2r_quotient_config *cfg) {
+extern "C++" {
+// The constraint system of a quotient or a verifier configuration (the two name these fields alike) into the shape constraint_fold takes
+// (h2r_constraints.hpp): 0, or H2R_E_SHAPE.  n_extra: the prover's extra permutation sources, every source named once; nullptr for the
+// verifier, which has none and may name an advice column twice.  ctx == nullptr: the parts that need no field (everything but delta).
+template <class Cfg> int32_t constraint_shape(const h2r_ctx *ctx, const Cfg *cfg, const u32 *n_extra, ConstraintShape &cs) {
+    const u32 F = cfg->num_fixed;
+    if (F > QUOT_MAX_FIXED || (cfg->lookup_mask >> QUOT_LOOKUP_ARGS)) return H2R_E_SHAPE;
+    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i)
+        if (cfg->gate_fixed[i] >= F) return H2R_E_SHAPE;
+    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k)
+        if (((cfg->lookup_mask >> k) & 1u) && (cfg->lookup_advice[k] >= 5 || cfg->lookup_tag[k] >= F || cfg->lookup_enable[k] >= F)) return H2R_E_SHAPE;
+    if (cfg->lookup_mask && (cfg->table_tag >= F || cfg->table_value >= F)) return H2R_E_SHAPE;
     h2r_permutation_config pc;
     std::memset(&pc, 0, sizeof pc);
     pc.struct_size = sizeof pc;
-    pc.num_columns = cfg->num_columns; pc.chunk_len = cfg->chunk_len; pc.n_extra = cfg->n_extra;
+    pc.num_columns = cfg->num_columns; pc.chunk_len = cfg->chunk_len; pc.n_extra = n_extra ? *n_extra : 0;
     std::memcpy(pc.column_src, cfg->column_src, sizeof pc.column_src);
-    return pc;
+    if (!perm_cfg_valid(&pc, n_extra != nullptr)) return H2R_E_SHAPE;
+    cs.m = cfg->num_columns; cs.chunk_len = std::min<u32>(cfg->chunk_len, cfg->num_columns); cs.n_sets = perm_sets(&pc); cs.lookup_mask = cfg->lookup_mask;
+    std::memcpy(cs.gate_fixed, cfg->gate_fixed, sizeof cs.gate_fixed); std::memcpy(cs.src, cfg->column_src, sizeof cs.src);
+    std::memcpy(cs.lookup_advice, cfg->lookup_advice, sizeof cs.lookup_advice); std::memcpy(cs.lookup_tag, cfg->lookup_tag, sizeof cs.lookup_tag);
+    std::memcpy(cs.lookup_enable, cfg->lookup_enable, sizeof cs.lookup_enable);
+    cs.table_tag = cfg->table_tag; cs.table_value = cfg->table_value;
+    if (!ctx) return H2R_OK;
+    if (ge_p(cfg->delta, ctx->fc.p)) return H2R_E_SHAPE;
+    fe_power_table(cs.dpow, QUOT_PERM_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), ctx->fc);
+    return H2R_OK;
 }
-// what h2r_quotient_sets answers 0 for: the parts of a configuration that need no ctx (omega_ext, zeta and delta are compared with the ctx's p)
-int32_t quotient_cfg_status(const h2r_quotient_config *cfg) {
+}  // extern "C++"
+// what h2r_quotient_sets answers 0 for (ctx == nullptr: omega_ext, zeta and delta are compared with the ctx's p); fills the shape
+int32_t quotient_cfg_status(const h2r_ctx *ctx, const h2r_quotient_config *cfg, ConstraintShape &cs) {
     if (cfg->struct_size != sizeof(h2r_quotient_config)) return H2R_E_UNSUPPORTED;
     if (cfg->log_n == 0 || cfg->log_ext <= cfg->log_n || cfg->log_ext > QUOT_MAX_LOG || cfg->log_ext - cfg->log_n > QUOT_MAX_SCALE_LOG) return H2R_E_SHAPE;
     if ((u64)cfg->blinding_factors + 2 > (1ull << cfg->log_n)) return H2R_E_SHAPE;   // u = n - blinding_factors - 1 >= 1
-    if (cfg->num_fixed > QUOT_MAX_FIXED) return H2R_E_SHAPE;
-    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i)
-        if (cfg->gate_fixed[i] >= cfg->num_fixed) return H2R_E_SHAPE;
-    if (cfg->lookup_mask >> H2R_LOOKUP_ARGS) return H2R_E_SHAPE;
-    for (u32 k = 0; k < H2R_LOOKUP_ARGS; ++k) {
-        if (!((cfg->lookup_mask >> k) & 1u)) continue;
-        if (cfg->lookup_advice[k] >= 5 || cfg->lookup_tag[k] >= cfg->num_fixed || cfg->lookup_enable[k] >= cfg->num_fixed) return H2R_E_SHAPE;
-    }
-    if (cfg->lookup_mask && (cfg->table_tag >= cfg->num_fixed || cfg->table_value >= cfg->num_fixed)) return H2R_E_SHAPE;
-    const h2r_permutation_config pc = quotient_perm_cfg(cfg);
-    return perm_cfg_valid(&pc) ? H2R_OK : H2R_E_SHAPE;
+    return constraint_shape(ctx, cfg, &cfg->n_extra, cs);
 }
 // lookup column slots in use: the highest selected argument + 1
 u32 quotient_lookup_cols(u32 mask) { u32 nl = 0; while (mask >> nl) ++nl; return nl; }
 }  // namespace
 
 uint32_t h2r_quotient_sets(const h2r_quotient_config *cfg, uint32_t *circuit_columns, uint32_t *key_columns) try {
-    if (!cfg || quotient_cfg_status(cfg) != H2R_OK) return 0;
-    const h2r_permutation_config pc = quotient_perm_cfg(cfg);
-    const u32 S = perm_sets(&pc);
+    ConstraintShape cs;
+    if (!cfg || quotient_cfg_status(nullptr, cfg, cs) != H2R_OK) return 0;
+    const u32 S = cs.n_sets;
     u32 fixed_seen = 0, nk = 0;
     auto use = [&](u32 c) { fixed_seen |= 1u << c; };
     for (u32 i = 0; i < QUOT_GATE_FIXED; ++i) use(cfg->gate_fixed[i]);
@@ -4286,15 +4298,15 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
     if (cfg->struct_size != sizeof(h2r_quotient_config)) return H2R_E_UNSUPPORTED;
     if (cfg->n_extra && cfg->n_extra <= H2R_PERM_MAX_EXTRA && !in->extra.base) return H2R_E_NULL;
     if (cfg->lookup_mask && !(cfg->lookup_mask >> H2R_LOOKUP_ARGS) && (!in->lookup_a_perm.base || !in->lookup_s_perm.base || !in->lookup_z.base)) return H2R_E_NULL;
-    if (const int32_t rc = quotient_cfg_status(cfg)) return rc;
+    QuotientArgs qa;
+    std::memset(static_cast<void *>(&qa), 0, sizeof qa);
+    if (const int32_t rc = quotient_cfg_status(ctx, cfg, qa.cs)) return rc;
     const FieldConsts &f = ctx->fc;
-    if (ge_p(cfg->omega_ext, f.p) || ge_p(cfg->zeta, f.p) || ge_p(cfg->delta, f.p)) return H2R_E_SHAPE;
+    if (ge_p(cfg->omega_ext, f.p) || ge_p(cfg->zeta, f.p)) return H2R_E_SHAPE;
     if (!(cfg->zeta[0] | cfg->zeta[1] | cfg->zeta[2] | cfg->zeta[3])) return H2R_E_SHAPE;
     const bool mont = ctx_mont(ctx);
     const u32 log_n = cfg->log_n, log_ext = cfg->log_ext, scale_log = log_ext - log_n, r = 1u << scale_log;
     const Fe one = fe_one(f), omega = cfg_to_mont(ctx, cfg->omega_ext), zeta = cfg_to_mont(ctx, cfg->zeta);   // Montgomery form from here on
-    QuotientArgs qa;
-    std::memset(static_cast<void *>(&qa), 0, sizeof qa);
     fe_squaring_chain(qa.wpow, QUOT_MAX_LOG, omega, f);
     if (!is_primitive_root(omega, log_ext, f)) return H2R_E_SHAPE;
     {   // X_j^n = zeta^n * (omega_ext^n)^(j mod r): none of them may be 1
@@ -4308,8 +4320,7 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
             zn = fe_mont_mul(zn, wn, f);
         }
     }
-    const h2r_permutation_config pc = quotient_perm_cfg(cfg);
-    const u32 S = perm_sets(&pc), nl = quotient_lookup_cols(cfg->lookup_mask);
+    const u32 S = qa.cs.n_sets, nl = quotient_lookup_cols(cfg->lookup_mask);
     const u64 col = 32ull << log_ext;
     struct Group { const h2r_column_group *g; u32 cols; bool per_circuit; };
     const Group groups[9] = {{&in->advice, 5, true}, {&in->extra, cfg->n_extra, true}, {&in->perm_z, S, true}, {&in->lookup_a_perm, nl, true},
@@ -4338,12 +4349,6 @@ int32_t h2r_quotient_columns(const h2r_ctx *ctx, const h2r_quotient_config *cfg,
     qa.theta = in->theta; qa.beta = in->beta; qa.gamma = in->gamma; qa.y = in->y;
     qa.status = status; qa.h = static_cast<u8 *>(h_out); qa.h_elem_stride = h_elem_stride;
     qa.log_ext = log_ext; qa.scale_log = scale_log; qa.mont = mont ? 1u : 0u; qa.last_rot = cfg->blinding_factors + 1;
-    qa.m = cfg->num_columns; qa.chunk_len = std::min<u32>(cfg->chunk_len, cfg->num_columns); qa.n_sets = S; qa.lookup_mask = cfg->lookup_mask;
-    std::memcpy(qa.gate_fixed, cfg->gate_fixed, sizeof qa.gate_fixed); std::memcpy(qa.src, cfg->column_src, sizeof qa.src);
-    std::memcpy(qa.lookup_advice, cfg->lookup_advice, sizeof qa.lookup_advice); std::memcpy(qa.lookup_tag, cfg->lookup_tag, sizeof qa.lookup_tag);
-    std::memcpy(qa.lookup_enable, cfg->lookup_enable, sizeof qa.lookup_enable);
-    qa.table_tag = cfg->table_tag; qa.table_value = cfg->table_value;
-    fe_power_table(qa.dpow, QUOT_PERM_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), f);
     qa.zeta = zeta; qa.f = f;
     // slices of tiles (a grid's x holds the circuits, at most 65,535)
     const u64 tiles = quotient_tiles(log_ext), tiles_per = slice_items(batch, tiles);
@@ -4912,30 +4917,27 @@ int32_t decode_sections(const h2r_proof_decode_config *cfg, const h2r_proof_sect
     da.num_sections = cfg->num_sections; da.num_items = (u32)items;
     return H2R_OK;
 }
+// constraint_fold's reads as masks, need[group][index] |= 1 << point set: every value is zero and the arithmetic does nothing, so the walk
+// needs no field.  What the expression reads of the evaluations is thus what the fold reads, not a table kept beside it.
+struct VfNeed {
+    u8 (*need)[VF_MAX_INDEX];
+    Fe E(u32 g, u32 i, u32 p) const { need[g][i] |= (u8)(1u << p); return fe_zero(); }
+    Fe l(u32) const { return fe_zero(); }   Fe ident(u32) const { return fe_zero(); }   Fe one() const { return fe_zero(); }
+    Fe theta() const { return fe_zero(); }  Fe beta() const { return fe_zero(); }       Fe gamma() const { return fe_zero(); }  Fe y() const { return fe_zero(); }
+    Fe mul(const Fe &, const Fe &) const { return fe_zero(); }
+    Fe add(const Fe &, const Fe &) const { return fe_zero(); }
+    Fe sub(const Fe &, const Fe &) const { return fe_zero(); }
+};
 // A configuration into the kernel's arguments (everything but the buffers): 0, or the refusal.  ctx == nullptr: the parts that need no
 // field (h2r_verify_bases).
 int32_t verify_scalars_args(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, VerifyScalarsArgs &a, u32 &num_evals) {
     if (cfg->struct_size != sizeof(h2r_verify_scalars_config)) return H2R_E_UNSUPPORTED;
-    const u32 F = cfg->num_fixed, m = cfg->num_columns;
-    if (cfg->reserved || cfg->log_n == 0 || cfg->log_n > QUOT_MAX_LOG || cfg->blinding_factors > VF_MAX_BF || F > QUOT_MAX_FIXED || m == 0 ||
-        m > QUOT_PERM_MAX_COLUMNS || cfg->chunk_len == 0 || (cfg->lookup_mask >> QUOT_LOOKUP_ARGS)) return H2R_E_SHAPE;
+    if (cfg->reserved || cfg->log_n == 0 || cfg->log_n > QUOT_MAX_LOG || cfg->blinding_factors > VF_MAX_BF) return H2R_E_SHAPE;
     if ((u64)cfg->blinding_factors + 2 > (1ull << cfg->log_n)) return H2R_E_SHAPE;       // u = n - bf - 1 >= 1
-    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i) if (cfg->gate_fixed[i] >= F) return H2R_E_SHAPE;
-    for (u32 c = 0; c < m; ++c) if (cfg->column_src[c] >= 5) return H2R_E_SHAPE;
-    u32 A = 0;
-    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k) {
-        if (!((cfg->lookup_mask >> k) & 1u)) continue;
-        ++A;
-        if (cfg->lookup_advice[k] >= 5 || cfg->lookup_tag[k] >= F || cfg->lookup_enable[k] >= F) return H2R_E_SHAPE;
-    }
-    if (A && (cfg->table_tag >= F || cfg->table_value >= F)) return H2R_E_SHAPE;
+    if (const int32_t rc = constraint_shape(ctx, cfg, nullptr, a.cs)) return rc;
     if (cfg->num_eval_plan == 0 || cfg->num_eval_plan > VF_MAX_PLAN || cfg->num_open_plan == 0 || cfg->num_open_plan > VF_MAX_PLAN) return H2R_E_SHAPE;
-    const u32 chunk = std::min<u32>(cfg->chunk_len, m), S = (m + chunk - 1) / chunk;
-    a.log_n = cfg->log_n; a.bf = cfg->blinding_factors; a.m = m; a.chunk_len = chunk; a.n_sets = S; a.lookup_mask = cfg->lookup_mask;
-    std::memcpy(a.gate_fixed, cfg->gate_fixed, sizeof a.gate_fixed); std::memcpy(a.src, cfg->column_src, sizeof a.src);
-    std::memcpy(a.lookup_advice, cfg->lookup_advice, sizeof a.lookup_advice); std::memcpy(a.lookup_tag, cfg->lookup_tag, sizeof a.lookup_tag);
-    std::memcpy(a.lookup_enable, cfg->lookup_enable, sizeof a.lookup_enable);
-    a.table_tag = cfg->table_tag; a.table_value = cfg->table_value;
+    const u32 F = cfg->num_fixed, m = a.cs.m, S = a.cs.n_sets, A = (u32)__builtin_popcount(cfg->lookup_mask);
+    a.log_n = cfg->log_n; a.bf = cfg->blinding_factors;
     // how many columns a group has, and the point sets the expression reads of each
     auto columns = [&](u32 g) -> u32 {
         return g == VF_G_ADVICE ? 5u : g == VF_G_FIXED ? F : g == VF_G_RANDOM ? 1u : g == VF_G_SIGMA ? m : g == VF_G_PERM_Z ? S : g == VF_G_H ? 1u : QUOT_LOOKUP_ARGS;
@@ -4945,15 +4947,7 @@ int32_t verify_scalars_args(const h2r_ctx *ctx, const h2r_verify_scalars_config 
         return !(g == VF_G_LOOKUP_Z || g == VF_G_LOOKUP_A || g == VF_G_LOOKUP_S) || ((cfg->lookup_mask >> i) & 1u);
     };
     u8 need[VF_GROUPS][VF_MAX_INDEX] = {};
-    for (u32 c = 0; c < 5; ++c) need[VF_G_ADVICE][c] = c == 4 ? 3 : 1;
-    for (u32 i = 0; i < QUOT_GATE_FIXED; ++i) need[VF_G_FIXED][cfg->gate_fixed[i]] = 1;
-    for (u32 c = 0; c < m; ++c) need[VF_G_SIGMA][c] = 1;
-    for (u32 s = 0; s < S; ++s) need[VF_G_PERM_Z][s] = s + 1 < S ? 7 : 3;
-    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k) {
-        if (!((cfg->lookup_mask >> k) & 1u)) continue;
-        need[VF_G_LOOKUP_Z][k] = 3; need[VF_G_LOOKUP_A][k] = 9; need[VF_G_LOOKUP_S][k] = 1;
-        need[VF_G_FIXED][cfg->lookup_tag[k]] = need[VF_G_FIXED][cfg->lookup_enable[k]] = need[VF_G_FIXED][cfg->table_tag] = need[VF_G_FIXED][cfg->table_value] = 1;
-    }
+    constraint_fold(a.cs, VfColumns<VfNeed>{{need}});
     u32 q = 0;
     for (u32 j = 0; j < cfg->num_eval_plan; ++j) {
         const h2r_verify_plan_entry &e = cfg->eval_plan[j];
@@ -4993,20 +4987,19 @@ int32_t verify_scalars_args(const h2r_ctx *ctx, const h2r_verify_scalars_config 
     a.num_open = cfg->num_open_plan;
     if (!ctx) return H2R_OK;
     const FieldConsts &f = ctx->fc;
-    if (ge_p(cfg->omega, f.p) || ge_p(cfg->delta, f.p)) return H2R_E_SHAPE;
+    if (ge_p(cfg->omega, f.p)) return H2R_E_SHAPE;
     const Fe omega = cfg_to_mont(ctx, cfg->omega);
     if (!is_primitive_root(omega, cfg->log_n, f)) return H2R_E_SHAPE;
     auto inv = [&](const Fe &x) { return fe_to_mont(fe_inv(fe_from_mont(x, f), f), f); };
     const Fe wi = inv(omega);
-    a.zmul[VF_P_CUR] = fe_one(f); a.zmul[VF_P_NEXT] = omega; a.zmul[VF_P_PREV] = wi;
-    a.zmul[VF_P_LAST] = wi;
-    for (u32 i = 0; i < cfg->blinding_factors; ++i) a.zmul[VF_P_LAST] = fe_mont_mul(a.zmul[VF_P_LAST], wi, f);
+    a.zmul[ROT_CUR] = fe_one(f); a.zmul[ROT_NEXT] = omega; a.zmul[ROT_PREV] = wi;
+    a.zmul[ROT_LAST] = wi;
+    for (u32 i = 0; i < cfg->blinding_factors; ++i) a.zmul[ROT_LAST] = fe_mont_mul(a.zmul[ROT_LAST], wi, f);
     {   // n = 2^log_n by doublings of 1
         Fe n = fe_one(f);
         for (u32 l = 0; l < cfg->log_n; ++l) n = fe_add(n, n, f.p);
         a.ninv = inv(n);
     }
-    fe_power_table(a.dpow, QUOT_PERM_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), f);
     a.f = f; a.mont = ctx_mont(ctx) ? 1u : 0u;
     return H2R_OK;
 }

@@ -13,8 +13,9 @@
 //   verify_scalars_kernel   the verifier's field side, one lane per circuit, 64 circuits per workgroup (the transcript kernel's geometry):
 //                           l0(x), l_last(x), l_active(x) in closed form (the bf + 2 differences x - omega^i and x^n - 1 inverted by
 //                           Montgomery's trick around ONE fe_inv, the prefix products in the lane's LDS column), the constraint expression
-//                           at x -- h2r_quotient.hpp's term sequence in its order, read from evaluations instead of columns -- folded with
-//                           y, the expected h(x), and then one scalar per base of R and the four scalars u^p of L.
+//                           at x folded with y -- constraint_fold (h2r_constraints.hpp: THE definition of the terms and their order, shared
+//                           with the quotient kernel) over a source that reads evaluations instead of columns --, the expected h(x), and
+//                           then one scalar per base of R and the four scalars u^p of L.
 //   msm_terms_kernel        out[e] = sum_{t<T} s[e][t] P[e][t] for bases that differ per circuit: one workgroup of 256 per circuit, lane l
 //                           takes the terms l, l + 256, ... (pt_mul_window2: any 256-bit scalar, a trip count that no scalar changes), the
 //                           workgroup sums over LDS with the complete addition, lane 0 stores the affine sum, (0, 0) for the identity.
@@ -29,8 +30,8 @@
 
 #include <cstring>
 
+#include "h2r_constraints.hpp"
 #include "h2r_curve_ntt.hpp"
-#include "h2r_quotient.hpp"
 #include "h2r_transcript.hpp"
 
 namespace h2r {
@@ -41,13 +42,11 @@ constexpr u32 VF_LANES = 64;                        // circuits of a decode / sc
 constexpr u32 VF_MAX_PLAN = 64;                     // entries of a plan
 constexpr u32 VF_MAX_INDEX = 16;                    // columns of a group
 constexpr u32 VF_MAX_BF = 13, VF_MAX_INV = VF_MAX_BF + 3;   // blinding factors; values inverted together
-constexpr u32 VF_H_PIECES = 4, VF_POINT_SETS = 4;
+constexpr u32 VF_H_PIECES = 4, VF_POINT_SETS = ROTATIONS;   // point set p = x under rotation p (ROT_*: the bits of a plan mask)
 constexpr u32 VF_MAX_TERMS = 4096, VF_TERM_LANES = 256;
 // the groups of a plan entry
 constexpr u32 VF_G_ADVICE = 0, VF_G_FIXED = 1, VF_G_RANDOM = 2, VF_G_SIGMA = 3, VF_G_PERM_Z = 4, VF_G_LOOKUP_Z = 5, VF_G_LOOKUP_A = 6, VF_G_LOOKUP_S = 7,
               VF_G_H = 8, VF_GROUPS = 9;
-// the point set of a rotation
-constexpr u32 VF_P_CUR = 0, VF_P_NEXT = 1, VF_P_LAST = 2, VF_P_PREV = 3;
 
 // 32 bytes of host or device memory <-> an element (device: two 16-byte accesses, as fe_load / fe_store)
 H2R_FD Fe vf_ld(const u8 *p) {
@@ -70,9 +69,7 @@ H2R_FD void vf_st(u8 *p, const Fe &x) {
 H2R_FD Fe vf_pow_shared(const Fe &a, const u64 (&e)[4], const FieldConsts &f) {
     u64 e0 = e[0], e1 = e[1], e2 = e[2], e3 = e[3];
     Fe acc = fe_words(f.one);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+    H2R_ROLLED
     for (int bit = 0; bit < 256; ++bit) {
         acc = fe_mont_mul(acc, acc, f);
         if (e3 >> 63) acc = fe_mont_mul(acc, a, f);
@@ -128,20 +125,46 @@ struct VerifyScalarsArgs {
     u8 *left;                                       // [batch][4][32]
     u8 *status;                                     // nullable, never cleared
     u64 batch;
-    u32 block0, mont, log_n, bf, m, chunk_len, n_sets, lookup_mask, num_open, num_bases, w_pos, g_pos;
-    u8 gate_fixed[QUOT_GATE_FIXED], src[QUOT_PERM_MAX_COLUMNS];
-    u8 lookup_advice[QUOT_LOOKUP_ARGS], lookup_tag[QUOT_LOOKUP_ARGS], lookup_enable[QUOT_LOOKUP_ARGS], table_tag, table_value;
+    u32 block0, mont, log_n, bf, num_open, num_bases, w_pos, g_pos;
+    ConstraintShape cs;
     unsigned short ev_first[VF_GROUPS][VF_MAX_INDEX];   // a column's first evaluation
     u8 ev_mask[VF_GROUPS][VF_MAX_INDEX];                // ... and the point sets it is evaluated at (the eval plan)
     unsigned short base_pos[VF_GROUPS][VF_MAX_INDEX];   // a column's commitment among the bases (group h: its piece 0)
     VfPlanEntry open[VF_MAX_PLAN];
-    Fe dpow[QUOT_PERM_MAX_COLUMNS];                 // delta^c, Montgomery form
     Fe zmul[VF_POINT_SETS];                         // 1, omega, omega^-(bf+1), omega^-1: Montgomery form
     Fe ninv;                                        // 1 / n, Montgomery form
     FieldConsts f;
 };
 
 H2R_FD u32 vf_popc(u32 x) { u32 n = 0; for (; x; x &= x - 1) ++n; return n; }
+
+// constraint_fold's column reads under the verifier's names: E(group, index, point set).  B answers E and the rest of a source.
+template <class B> struct VfColumns : B {
+    H2R_FD Fe adv(u32 c, u32 rot) const { return this->E(VF_G_ADVICE, c, rot); }
+    H2R_FD Fe fix(u32 c) const { return this->E(VF_G_FIXED, c, ROT_CUR); }
+    H2R_FD Fe sigma(u32 c) const { return this->E(VF_G_SIGMA, c, ROT_CUR); }
+    H2R_FD Fe perm_value(u32 src) const { return adv(src, ROT_CUR); }   // (the verifier has no extra columns)
+    H2R_FD Fe perm_z(u32 s, u32 rot) const { return this->E(VF_G_PERM_Z, s, rot); }
+    H2R_FD Fe look_z(u32 k, u32 rot) const { return this->E(VF_G_LOOKUP_Z, k, rot); }
+    H2R_FD Fe a_perm(u32 k, u32 rot) const { return this->E(VF_G_LOOKUP_A, k, rot); }
+    H2R_FD Fe s_perm(u32 k) const { return this->E(VF_G_LOOKUP_S, k, ROT_CUR); }
+};
+// one circuit's evaluations (Montgomery form on the way out), its challenges, l0 / l_last / l_active at x and beta x
+struct VfEvals : ConstraintField {
+    const VerifyScalarsArgs &a; const u8 *ev;
+    const Fe &theta_, &beta_, &gamma_, &y_, &bx; const Fe (&lag)[3];
+    H2R_FD Fe E(u32 g, u32 i, u32 p) const {
+        const u32 at = (u32)a.ev_first[g][i] + vf_popc((u32)a.ev_mask[g][i] & ((1u << p) - 1u));
+        const Fe r = vf_ld(ev + (u64)at * 32);
+        return a.mont ? r : fe_to_mont(r, f);
+    }
+    H2R_FD Fe l(u32 i) const { return lag[i]; }
+    H2R_FD Fe ident(u32 c) const { return mul(a.cs.dpow[c], bx); }
+    H2R_FD const Fe &theta() const { return theta_; }
+    H2R_FD const Fe &beta() const { return beta_; }
+    H2R_FD const Fe &gamma() const { return gamma_; }
+    H2R_FD const Fe &y() const { return y_; }
+};
 
 // The scalars of one circuit.  ev: its evaluations, right / left: its outputs, tmp: VF_MAX_INV elements of the lane's own.  0, H2R_E_SHAPE for
 // a challenge that is not canonical (nothing written), H2R_E_ASSERTION for x^n = 1 (nothing written).
@@ -164,134 +187,52 @@ H2R_FD u32 vf_scalars(const VerifyScalarsArgs &a, u64 e, const u8 *ev, u8 *right
     auto inv = [&](const Fe &p) __attribute__((always_inline)) { return fe_to_mont(fe_inv(fe_from_mont(p, f), f), f); };
     const Fe one = fe_words(f.one);
     Fe xn = x;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+    H2R_ROLLED
     for (u32 l = 0; l < a.log_n; ++l) xn = mul(xn, xn);
     if (fe_eq(xn, one)) return (u32)H2R_E_ASSERTION;
 
     // ---- l0, l_last, l_active and 1 / (x^n - 1): t_0 = x^n - 1, t_1 = x - 1, t_(2+j) = x - omega^(u+j) for j <= bf (u + bf = n - 1) ----
-    Fe l0, l_last, l_active, xn1_inv;
+    Fe lag[3], xn1_inv;                                                // l0, l_last, l_active at x
     {
         const u32 K = a.bf + 3;
         const Fe xn1 = sub(xn, one);
-        Fe pr = xn1, w = a.zmul[VF_P_LAST];                            // omega^u = omega^-(bf+1)
+        Fe pr = xn1, w = a.zmul[ROT_LAST];                            // omega^u = omega^-(bf+1)
         tmp.w[0] = pr;
         pr = mul(pr, sub(x, one)); tmp.w[tmp.stride] = pr;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-        for (u32 j = 2; j < K; ++j) { pr = mul(pr, sub(x, w)); tmp.w[j * tmp.stride] = pr; w = mul(w, a.zmul[VF_P_NEXT]); }
+        H2R_ROLLED
+        for (u32 j = 2; j < K; ++j) { pr = mul(pr, sub(x, w)); tmp.w[j * tmp.stride] = pr; w = mul(w, a.zmul[ROT_NEXT]); }
         Fe all = inv(pr);                                              // every factor is nonzero: x^n != 1
         const Fe zn = mul(xn1, a.ninv);
         Fe blind = fe_zero();
-        w = a.zmul[VF_P_PREV];                                         // omega^(n-1), then down to omega^u
-        l_last = fe_zero();
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+        w = a.zmul[ROT_PREV];                                         // omega^(n-1), then down to omega^u
+        lag[1] = fe_zero();
+        H2R_ROLLED
         for (u32 j = K - 1; j >= 2; --j) {
             const Fe t = sub(x, w), ti = mul(all, tmp.w[(j - 1) * tmp.stride]);
             all = mul(all, t);
             const Fe l = mul(mul(zn, w), ti);
-            if (j == 2) l_last = l; else blind = add(blind, l);
-            w = mul(w, a.zmul[VF_P_PREV]);
+            if (j == 2) lag[1] = l; else blind = add(blind, l);
+            w = mul(w, a.zmul[ROT_PREV]);
         }
-        l0 = mul(zn, mul(all, tmp.w[0]));                              // t_1's inverse
+        lag[0] = mul(zn, mul(all, tmp.w[0]));                              // t_1's inverse
         xn1_inv = mul(all, sub(x, one));                               // t_0's
-        l_active = sub(sub(one, l_last), blind);
+        lag[2] = sub(sub(one, lag[1]), blind);
     }
 
-    auto E = [&](u32 g, u32 i, u32 p) __attribute__((always_inline)) {
-        const u32 at = (u32)a.ev_first[g][i] + vf_popc((u32)a.ev_mask[g][i] & ((1u << p) - 1u));
-        const Fe r = vf_ld(ev + (u64)at * 32);
-        return a.mont ? r : fe_to_mont(r, f);
-    };
-    auto adv = [&](u32 c) __attribute__((always_inline)) { return E(VF_G_ADVICE, c, VF_P_CUR); };
-    auto fix = [&](u32 c) __attribute__((always_inline)) { return E(VF_G_FIXED, c, VF_P_CUR); };
-    // ---- the constraint expression at x, folded with y: h2r_quotient.hpp's terms in its order ----
-    Fe acc = fe_zero();
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-    for (u32 pr = 0; pr < 2; ++pr) {
-        const Fe va = adv(2 * pr), vb = adv(2 * pr + 1);
-        acc = add(acc, add(mul(fix(a.gate_fixed[2 * pr]), va), mul(fix(a.gate_fixed[2 * pr + 1]), vb)));
-        acc = add(acc, mul(fix(a.gate_fixed[5 + pr]), mul(va, vb)));
-    }
-    acc = add(acc, mul(fix(a.gate_fixed[4]), adv(4)));
-    acc = add(acc, mul(fix(a.gate_fixed[7]), E(VF_G_ADVICE, 4, VF_P_NEXT)));
-    acc = add(acc, fix(a.gate_fixed[8]));
-    auto push = [&](const Fe &t) __attribute__((always_inline)) { acc = add(mul(acc, y), t); };
-    {
-        auto Z = [&](u32 s, u32 p) __attribute__((always_inline)) { return E(VF_G_PERM_Z, s, p); };
-        push(mul(l0, sub(one, Z(0, VF_P_CUR))));
-        {
-            const Fe z = Z(a.n_sets - 1, VF_P_CUR);
-            push(mul(l_last, sub(mul(z, z), z)));
-        }
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-        for (u32 s = 1; s < a.n_sets; ++s) push(mul(l0, sub(Z(s, VF_P_CUR), Z(s - 1, VF_P_LAST))));
-        const Fe bx = mul(beta, x);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-        for (u32 s = 0; s < a.n_sets; ++s) {
-            const u32 c0 = s * a.chunk_len, c1 = c0 + a.chunk_len < a.m ? c0 + a.chunk_len : a.m;
-            Fe lft = Z(s, VF_P_NEXT), rgt = Z(s, VF_P_CUR);
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-            for (u32 c = c0; c < c1; ++c) {
-                const Fe vg = add(adv(a.src[c]), gamma);
-                lft = mul(lft, add(vg, mul(beta, E(VF_G_SIGMA, c, VF_P_CUR))));
-                rgt = mul(rgt, add(vg, mul(a.dpow[c], bx)));
-            }
-            push(mul(l_active, sub(lft, rgt)));
-        }
-    }
-    if (a.lookup_mask) {
-        const Fe sg = add(add(mul(theta, fix(a.table_tag)), fix(a.table_value)), gamma);   // S + gamma
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
-        for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k) {
-            if (!((a.lookup_mask >> k) & 1u)) continue;
-            const Fe z = E(VF_G_LOOKUP_Z, k, VF_P_CUR);
-            push(mul(l0, sub(one, z)));
-            push(mul(l_last, sub(mul(z, z), z)));
-            const Fe ap = E(VF_G_LOOKUP_A, k, VF_P_CUR), sp = E(VF_G_LOOKUP_S, k, VF_P_CUR);
-            {
-                const Fe ak = add(mul(theta, fix(a.lookup_tag[k])), mul(fix(a.lookup_enable[k]), adv(a.lookup_advice[k])));
-                const Fe lft = mul(mul(E(VF_G_LOOKUP_Z, k, VF_P_NEXT), add(ap, beta)), add(sp, gamma));
-                const Fe rgt = mul(mul(z, add(ak, beta)), sg);
-                push(mul(l_active, sub(lft, rgt)));
-            }
-            const Fe d = sub(ap, sp);
-            push(mul(l0, d));
-            push(mul(l_active, mul(d, sub(ap, E(VF_G_LOOKUP_A, k, VF_P_PREV)))));
-        }
-    }
-    const Fe eh = mul(acc, xn1_inv);                                   // the expected h(x)
+    const Fe bx = mul(beta, x);
+    const VfColumns<VfEvals> src{{{f}, a, ev, theta, beta, gamma, y, bx, lag}};
+    const Fe eh = mul(constraint_fold(a.cs, src), xn1_inv);            // the expected h(x): the constraint expression at x, folded with y
 
     // ---- the scalars: sums in the ctx's representation, in this circuit's own row ----
     auto repr = [&](const Fe &p) __attribute__((always_inline)) { return a.mont ? p : fe_from_mont(p, f); };
     auto bump = [&](u32 pos, const Fe &c) __attribute__((always_inline)) { u8 *o = right + (u64)pos * 32; vf_st(o, add(vf_ld(o), repr(c))); };
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+    H2R_ROLLED
     for (u32 i = 0; i < a.num_bases; ++i) vf_st(right + (u64)i * 32, fe_zero());
     Fe up = one, gsum = fe_zero();
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+    H2R_ROLLED
     for (u32 p = 0; p < VF_POINT_SETS; ++p) {
         Fe vp = one, esum = fe_zero();
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+        H2R_ROLLED
         for (u32 j = 0; j < a.num_open; ++j) {
             const VfPlanEntry q = a.open[j];
             if (!((q.mask >> p) & 1u)) continue;
@@ -299,12 +240,10 @@ H2R_FD u32 vf_scalars(const VerifyScalarsArgs &a, u64 e, const u8 *ev, u8 *right
             const u32 pos = a.base_pos[q.group][q.index];
             if (q.group == VF_G_H) {
                 val = eh;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll 1
-#endif
+                H2R_ROLLED
                 for (u32 piece = 0; piece < VF_H_PIECES; ++piece) { bump(pos + piece, coeff); coeff = mul(coeff, xn); }
             } else {
-                val = E(q.group, q.index, p);
+                val = src.E(q.group, q.index, p);
                 bump(pos, coeff);
             }
             esum = add(esum, mul(vp, val));

@@ -101,22 +101,42 @@ static int terms(const CurveConsts &cv, u32 mont) {
     return 0;
 }
 
-// The smallest configuration: one fixed column for every selector, one permutation column, no lookups; log_n = 3, one blinding factor.
-static int scalars(u32 mont) {
+// Two configurations of the constraint expression (csrc/h2r_constraints.hpp: constraint_fold, the source over evaluations).  The smallest: one
+// fixed column for every selector, one permutation column, no lookups.  The full one: two fixed columns, three permutation columns in sets
+// of two (a ragged last set, Z_0 read at the last rotation), the lookup arguments 1 and 4 (A' read at the previous rotation).  log_n = 3,
+// one blinding factor; the plans hold exactly what the expression reads, so a read of anything else leaves the exact-size buffers.
+static int scalars(u32 mont, bool full) {
     auto a = std::make_unique<VerifyScalarsArgs>();
     std::memset(static_cast<void *>(a.get()), 0, sizeof *a);
     field_consts_init(kR, &a->f);
     const FieldConsts &f = a->f;
-    a->mont = mont; a->log_n = 3; a->bf = 1; a->m = 1; a->chunk_len = 1; a->n_sets = 1; a->batch = 1;
-    // evaluations: advice 0..3 (1 each), advice 4 (2), fixed 0 (1), sigma 0 (1), perm_z 0 (2) = 10; bases: 5 advice, Z, random, 4 h, 4 W, fixed, sigma, G
-    u32 q = 0;
-    auto col = [&](u32 g, u32 i, u32 mask, u32 pos) { a->ev_first[g][i] = (unsigned short)q; a->ev_mask[g][i] = (u8)mask; a->base_pos[g][i] = (unsigned short)pos; q += vf_popc(mask); };
-    for (u32 c = 0; c < 5; ++c) col(VF_G_ADVICE, c, c == 4 ? 3 : 1, c);
-    col(VF_G_FIXED, 0, 1, 15); col(VF_G_SIGMA, 0, 1, 16); col(VF_G_PERM_Z, 0, 3, 5);
-    a->base_pos[VF_G_RANDOM][0] = 6; a->base_pos[VF_G_H][0] = 7; a->w_pos = 11; a->g_pos = 17; a->num_bases = 18;
-    const VfPlanEntry open[5] = {{VF_G_ADVICE, 4, 3, 0}, {VF_G_PERM_Z, 0, 3, 0}, {VF_G_FIXED, 0, 1, 0}, {VF_G_SIGMA, 0, 1, 0}, {VF_G_H, 0, 1, 0}};
-    for (u32 j = 0; j < 5; ++j) a->open[j] = open[j];
-    a->num_open = 5;
+    const u32 F = full ? 2 : 1, m = full ? 3 : 1, S = full ? 2 : 1, mask = full ? 0x12 : 0, A = vf_popc(mask);
+    a->mont = mont; a->log_n = 3; a->bf = 1; a->batch = 1;
+    ConstraintShape &cs = a->cs;
+    cs.m = m; cs.chunk_len = full ? 2 : 1; cs.n_sets = S; cs.lookup_mask = mask;
+    if (full) {
+        cs.gate_fixed[8] = 1; cs.src[1] = 2; cs.src[2] = 4; cs.table_tag = 1;
+        cs.lookup_advice[1] = 3; cs.lookup_tag[1] = 1; cs.lookup_advice[4] = 0; cs.lookup_enable[4] = 1;
+    }
+    // the base order: 5 advice, A' / S' per argument, the S permutation Z, the A lookup Z, random, 4 h, 4 W, F fixed, m sigma, G
+    const u32 pz = 5 + 2 * A, lz = pz + S, rnd = lz + A, h = rnd + 1, fx = h + 8, sg = fx + F;
+    u32 q = 0, no = 0, rank = 0;
+    auto col = [&](u32 g, u32 i, u32 msk, u32 pos, bool open) {
+        a->ev_first[g][i] = (unsigned short)q; a->ev_mask[g][i] = (u8)msk; a->base_pos[g][i] = (unsigned short)pos; q += vf_popc(msk);
+        if (open) a->open[no++] = VfPlanEntry{(u8)g, (u8)i, (u8)msk, 0};
+    };
+    for (u32 c = 0; c < 5; ++c) col(VF_G_ADVICE, c, c == 4 ? 3 : 1, c, full || c == 4);   // (the smallest: advice 0..3 are evaluated and not opened)
+    for (u32 i = 0; i < F; ++i) col(VF_G_FIXED, i, 1, fx + i, true);
+    for (u32 c = 0; c < m; ++c) col(VF_G_SIGMA, c, 1, sg + c, true);
+    for (u32 s = 0; s < S; ++s) col(VF_G_PERM_Z, s, s + 1 < S ? 7 : 3, pz + s, true);
+    for (u32 k = 0; k < QUOT_LOOKUP_ARGS; ++k) {
+        if (!((mask >> k) & 1u)) continue;
+        col(VF_G_LOOKUP_Z, k, 3, lz + rank, true); col(VF_G_LOOKUP_A, k, 9, 5 + 2 * rank, true); col(VF_G_LOOKUP_S, k, 1, 6 + 2 * rank, true);
+        ++rank;
+    }
+    a->base_pos[VF_G_RANDOM][0] = (unsigned short)rnd; a->base_pos[VF_G_H][0] = (unsigned short)h; a->w_pos = h + 4; a->g_pos = sg + m; a->num_bases = a->g_pos + 1;
+    a->open[no++] = VfPlanEntry{VF_G_H, 0, 1, 0};
+    a->num_open = no;
     // omega of order 8: 7^((r - 1) / 8) by square-and-multiply
     Fe e = fe_sub(fe_words(kR), fe_small(1), f.p), w = fe_words(f.one);
     for (int s = 0; s < 3; ++s) { e.v[0] = (e.v[0] >> 1) | (e.v[1] << 63); e.v[1] = (e.v[1] >> 1) | (e.v[2] << 63); e.v[2] = (e.v[2] >> 1) | (e.v[3] << 63); e.v[3] >>= 1; }
@@ -125,9 +145,10 @@ static int scalars(u32 mont) {
     Fe w4 = fe_mont_mul(fe_mont_mul(w, w, f), fe_mont_mul(w, w, f), f);
     REQUIRE(fe_is_zero(fe_add(w4, fe_words(f.one), f.p)));                     // omega^4 = -1
     auto inv = [&](const Fe &x) { return fe_to_mont(fe_inv(fe_from_mont(x, f), f), f); };
-    a->zmul[VF_P_CUR] = fe_words(f.one); a->zmul[VF_P_NEXT] = w; a->zmul[VF_P_PREV] = inv(w); a->zmul[VF_P_LAST] = fe_mont_mul(a->zmul[VF_P_PREV], a->zmul[VF_P_PREV], f);
+    a->zmul[ROT_CUR] = fe_words(f.one); a->zmul[ROT_NEXT] = w; a->zmul[ROT_PREV] = inv(w); a->zmul[ROT_LAST] = fe_mont_mul(a->zmul[ROT_PREV], a->zmul[ROT_PREV], f);
     a->ninv = inv(fe_to_mont(fe_small(8), f));
-    a->dpow[0] = fe_words(f.one);
+    cs.dpow[0] = fe_words(f.one);
+    for (u32 c = 1; c < m; ++c) cs.dpow[c] = fe_mont_mul(cs.dpow[c - 1], seven, f);   // (delta: any element will do)
     auto repr = [&](u64 v) { const Fe x = fe_small(v); return mont ? fe_to_mont(x, f) : x; };
     auto ch = heap<u64>(7 * 4); auto ev = heap<u8>(32 * q); auto right = heap<u8>(32 * a->num_bases); auto left = heap<u8>(128); auto tmp = heap<Fe>(VF_MAX_INV);
     for (u32 k = 0; k < 7; ++k) { const Fe c = repr(3 + 2 * k); std::memcpy(ch.get() + 4 * k, c.v, 32); a->ch[k] = ch.get() + 4 * k; }
@@ -143,8 +164,9 @@ static int scalars(u32 mont) {
         REQUIRE(fe_eq(mont ? wp : fe_to_mont(wp, f), fe_mont_mul(up, fe_mont_mul(x, a->zmul[p], f), f)));
         up = fe_mont_mul(up, u, f);
     }
-    for (u32 pos : {0u, 1u, 2u, 3u, 6u}) REQUIRE(fe_is_zero(vf_ld(right.get() + 32 * pos)));
-    REQUIRE(!fe_is_zero(vf_ld(right.get() + 32 * a->g_pos)) && !fe_is_zero(vf_ld(right.get() + 32 * 10)));
+    if (!full) for (u32 pos : {0u, 1u, 2u, 3u}) REQUIRE(fe_is_zero(vf_ld(right.get() + 32 * pos)));
+    REQUIRE(fe_is_zero(vf_ld(right.get() + 32 * rnd)));
+    REQUIRE(!fe_is_zero(vf_ld(right.get() + 32 * a->g_pos)) && !fe_is_zero(vf_ld(right.get() + 32 * (h + 3))));
     // x = omega^5: an assertion, nothing written; a challenge = r: a shape
     std::memset(right.get(), 0xEE, 32 * a->num_bases);
     Fe w5 = fe_mont_mul(w4, w, f);
@@ -161,7 +183,7 @@ int main() {
     const CurveConsts *cv = curve_of_field(0);
     if (!cv) return 1;
     for (u32 mont = 0; mont < 2; ++mont)
-        if (decoder(*cv, mont) || terms(*cv, mont) || scalars(mont)) return 1;
+        if (decoder(*cv, mont) || terms(*cv, mont) || scalars(mont, false) || scalars(mont, true)) return 1;
     std::printf("VERIFY_SHARED_OK 2 representations\n");
     return 0;
 }

@@ -85,7 +85,8 @@ def measure(vk, proofs):
         _lib.profile_enable(0)
     print("batch %3d: verify_proof %8.3f ms of stream time, median (min %.3f, max %.3f; %d timed runs after one untimed)"
           % (batch, statistics.median(total), min(total), max(total), REPS))
-    print("    per launch class, ms: " + "; ".join("%s %.3f (%d launches)" % (name, statistics.median(per[name]), launches[name]) for name, _ in CLASSES), flush=True)
+    print("    per launch class, ms: " + "; ".join("%s %.3f (min %.3f, max %.3f; %d launches)" % (name, statistics.median(per[name]), min(per[name]), max(per[name]), launches[name])
+                                               for name, _ in CLASSES), flush=True)
 
 
 if __name__ == "__main__":
