@@ -228,6 +228,10 @@ class H2RMsmTermsConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("num_terms", ctypes.c_uint32), ("reserved", ctypes.c_uint64)]
 
 
+class H2RPairingConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("num_pairs", ctypes.c_uint32), ("negate_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -282,6 +286,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_transcript_state_bytes", "h2r_transcript_round", "h2r_transcript_eval",
            "h2r_random_columns", "h2r_random_eval",
            "h2r_proof_decode", "h2r_verify_bases", "h2r_verify_scalars", "h2r_msm_terms", "h2r_verify_eval",
+           "h2r_pairing_prepare", "h2r_pairing_products", "h2r_pairing_eval",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -299,6 +304,8 @@ KERNEL_CURVE_NTT_TWIDDLE, KERNEL_CURVE_NTT_LOAD, KERNEL_CURVE_NTT_STAGE, KERNEL_
 KERNEL_TRANSCRIPT = 29
 KERNEL_RANDOM = 30
 KERNEL_PROOF_DECODE, KERNEL_VERIFY_SCALARS, KERNEL_MSM_TERMS = 31, 32, 33
+KERNEL_PAIRING = 34
+H2R_PAIRING_STEPS, H2R_PAIRING_TABLE_BYTES, H2R_PAIRING_MAX_PAIRS = 102, 13056, 4
 FIELD_MUL, FIELD_TO_MONTGOMERY, FIELD_FROM_MONTGOMERY = 2, 6, 7   # h2r_field_eval's operations a * b, a * R and a * R^-1 mod p (include/h2r.h)
 H2R_HASHED_MSG_STREAM_BYTES = 288
 H2R_STREAM_FIELD_AB = 1
@@ -538,6 +545,9 @@ def lib():
     L.h2r_verify_scalars.argtypes = [vp, pvs, vp, u64, ctypes.POINTER(H2RVerifyChallenges), u64, vp, u64, vp, vp, vp]
     L.h2r_msm_terms.argtypes = [vp, ctypes.POINTER(H2RMsmTermsConfig), vp, u64, vp, u64, u64, vp, vp, vp]
     L.h2r_verify_eval.argtypes = [vp, u32, pvs, ctypes.c_char_p, u64, vp, u64]
+    L.h2r_pairing_prepare.argtypes = [vp, ctypes.c_char_p, vp]
+    L.h2r_pairing_products.argtypes = [vp, ctypes.POINTER(H2RPairingConfig), vp, vp, u64, u64, vp, vp, vp, vp]
+    L.h2r_pairing_eval.argtypes = [vp, u32, ctypes.c_char_p, u64, vp, u64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.h2r_dist_destroy.argtypes = [vp]

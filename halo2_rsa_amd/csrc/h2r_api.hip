@@ -33,6 +33,7 @@
 #include "h2r_transcript.hpp"
 #include "h2r_random.hpp"
 #include "h2r_verify.hpp"
+#include "h2r_pairing.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4368,7 +4369,7 @@ static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_O
               H2R_KERNEL_CURVE_NTT_TWIDDLE == H2R_KERNEL_MSM_FOLD + 1 && H2R_KERNEL_CURVE_NTT_STORE == H2R_KERNEL_CURVE_NTT_TWIDDLE + 3 &&
               H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_RANDOM == H2R_KERNEL_TRANSCRIPT + 1 && H2R_KERNEL_PROOF_DECODE == H2R_KERNEL_RANDOM + 1 &&
               H2R_KERNEL_VERIFY_SCALARS == H2R_KERNEL_PROOF_DECODE + 1 && H2R_KERNEL_MSM_TERMS == H2R_KERNEL_VERIFY_SCALARS + 1 &&
-              H2R_KERNEL_COUNT == H2R_KERNEL_MSM_TERMS + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_PAIRING == H2R_KERNEL_MSM_TERMS + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_PAIRING + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -5174,6 +5175,105 @@ int32_t h2r_verify_eval(const h2r_ctx *ctx, uint32_t op, const h2r_verify_scalar
         for (u64 t = 0; t < in_len / 96; ++t) acc = pt_add(acc, vf_term(in + t * 96, in + t * 96 + 32, mont, ctx->fc, *cv), *cv);
         vf_store_sum(out, acc, mont, *cv);
     }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- the verifier's verdict: the pairing check (h2r_pairing.hpp) ---------------------------------------------------------------------------
+static_assert(H2R_PAIRING_STEPS == PR_STEPS && H2R_PAIRING_TABLE_BYTES == PR_TABLE_BYTES && H2R_PAIRING_MAX_PAIRS == PR_MAX_PAIRS, "h2r.h and the kernel's constants");
+
+int32_t h2r_pairing_prepare(const h2r_ctx *ctx, const uint8_t *g2, uint8_t *table) try {
+    if (!ctx || !g2 || !table) return H2R_E_NULL;
+    const PairingConsts *pc = pairing_consts_of(ctx->params.field, ctx_mont(ctx));
+    if (!pc) return H2R_E_UNSUPPORTED;
+    std::vector<u8> t(PR_TABLE_BYTES);                      // (a status leaves `table` untouched)
+    if (const u32 bad = pr_prepare(g2, t.data(), *pc)) return (int32_t)bad;
+    std::memcpy(table, t.data(), t.size());
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_pairing_products(const h2r_ctx *ctx, const h2r_pairing_config *cfg, const void *tables, const void *points, uint64_t points_elem_stride,
+                             uint64_t batch, void *gt, uint8_t *accept, uint8_t *status, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !tables || !points) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_pairing_config)) return H2R_E_UNSUPPORTED;
+    if (cfg->num_pairs == 0 || cfg->num_pairs > PR_MAX_PAIRS || (cfg->negate_mask >> cfg->num_pairs) || cfg->reserved) return H2R_E_SHAPE;
+    const u64 p_bytes = 64ull * cfg->num_pairs, t_bytes = (u64)PR_TABLE_BYTES * cfg->num_pairs;
+    if (misaligned(tables) || misaligned(points, points_elem_stride) || (gt && misaligned(gt))) return H2R_E_SHAPE;
+    if (points_elem_stride && points_elem_stride < p_bytes) return H2R_E_SHAPE;
+    if (batch) {
+        struct Range { const void *p; u128 n; };
+        const Range ins[2] = {{tables, (u128)t_bytes}, {points, (u128)(batch - 1) * points_elem_stride + p_bytes}};
+        const Range outs[3] = {{gt, (u128)batch * PR_FQ12_BYTES}, {accept, (u128)batch}, {status, (u128)batch}};
+        for (u32 x = 0; x < 3; ++x) {
+            if (!outs[x].p) continue;
+            for (const Range &in : ins) if (overlaps(outs[x].p, outs[x].n, in.p, in.n)) return H2R_E_SHAPE;
+            for (u32 y = x + 1; y < 3; ++y)
+                if (outs[y].p && overlaps(outs[x].p, outs[x].n, outs[y].p, outs[y].n)) return H2R_E_SHAPE;
+        }
+    }
+    const PairingConsts *pc = pairing_consts_of(ctx->params.field, ctx_mont(ctx));
+    if (!pc) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    if (batch == 0) return H2R_OK;
+    PairingArgs pa;
+    std::memset(static_cast<void *>(&pa), 0, sizeof pa);
+    pa.tables = static_cast<const u8 *>(tables); pa.points = static_cast<const u8 *>(points); pa.points_elem_stride = points_elem_stride;
+    pa.gt = static_cast<u8 *>(gt); pa.accept = accept; pa.status = status; pa.batch = batch;
+    pa.num_pairs = cfg->num_pairs; pa.negate_mask = cfg->negate_mask; pa.c = *pc;
+    const u64 blocks = (batch + PR_TEAMS - 1) / PR_TEAMS;
+    if (blocks > 0xffffffffull) return H2R_E_UNSUPPORTED;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return for_each_slice(blocks, slice_items(1, blocks), [&](u64 b0, u64 nb) {   // (workgroups of 64 counted as of 256)
+        pa.block0 = (u32)b0;
+        return stage_launch(H2R_KERNEL_PAIRING, st, [&](hipEvent_t a, hipEvent_t b) { return launch_pairing(pa, (u32)nb, st, a, b); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_pairing_eval(const h2r_ctx *ctx, uint32_t op, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_len) try {
+    if (!ctx || !in || !out) return H2R_E_NULL;
+    if (op > 5) return H2R_E_SHAPE;
+    const PairingConsts *pc = pairing_consts_of(ctx->params.field, ctx_mont(ctx));
+    if (!pc) return H2R_E_UNSUPPORTED;
+    const PairingConsts &c = *pc;
+    std::vector<Fq2> store(PR_TEAM_FQ2);
+    PrHostTeam t{store.data(), store.data() + PR_SLOTS * 6};
+    auto load = [&](u32 slot, const u8 *p) { for (u32 j = 0; j < 6; ++j) t.s[slot * 6 + j] = pr_ld2(p + 64 * j, c); };
+    auto put = [&](u8 *p) { for (u32 j = 0; j < 6; ++j) pr_st2(p + 64 * j, t.s[j], c); };
+    if (op == 3 || op == 5) {
+        if (in_len < 2) return H2R_E_SHAPE;
+        const u32 J = in[0], mask = in[1];
+        const u64 rec = PR_G1_BYTES + PR_TABLE_BYTES;
+        if (J == 0 || J > PR_MAX_PAIRS || (mask >> J) || in_len != 2 + J * rec || out_len != (op == 3 ? PR_FQ12_BYTES : PR_FQ12_BYTES + 1)) return H2R_E_SHAPE;
+        std::vector<u8> pts(J * PR_G1_BYTES);
+        for (u32 j = 0; j < J; ++j) {
+            std::memcpy(pts.data() + j * PR_G1_BYTES, in + 2 + j * rec, PR_G1_BYTES);
+            if (!pr_in_range(in + 2 + j * rec + PR_G1_BYTES, PR_TABLE_BYTES / 32, c)) return H2R_E_SHAPE;
+        }
+        if (const u32 bad = pr_points_status(pts.data(), J, c)) return (int32_t)bad;
+        pr_set_points(t, pts.data(), J, mask, true, c);
+        pr_miller(t, J, in + 2 + PR_G1_BYTES, rec, c);
+        if (op == 5) { pr_final_exp(t, c); out[0] = pr_is_one(t.s, c.fq) ? 1 : 0; put(out + 1); } else put(out);
+        return H2R_OK;
+    }
+    const u64 want_in = op == 0 ? 2 * PR_FQ12_BYTES : op == 2 ? PR_FQ12_BYTES + 1 : PR_FQ12_BYTES;
+    if (in_len != want_in || out_len != PR_FQ12_BYTES) return H2R_E_SHAPE;
+    const u8 *v = in + (op == 2 ? 1 : 0);
+    if (!pr_in_range(v, (u32)((in_len - (op == 2 ? 1 : 0)) / 32), c)) return H2R_E_SHAPE;
+    load(0, v);
+    if (op == 0) {
+        const bool same = std::memcmp(v, v + PR_FQ12_BYTES, PR_FQ12_BYTES) == 0;   // (one value twice: the square's own formula, as the kernel takes it)
+        load(1, v + PR_FQ12_BYTES);
+        t.each(0, [&](u32 k) { return fq12_product_coeff(t.s, same ? t.s : t.s + 6, k, c.fq); });
+    } else if (op == 1) {
+        bool zero = true;
+        for (u32 j = 0; j < 6; ++j) if (!fq2_is_zero(t.s[j])) zero = false;
+        if (zero) return H2R_E_SHAPE;
+        pr_inverse(t, c);
+    } else if (op == 2) {
+        if (in[0] > 11) return H2R_E_SHAPE;
+        for (u32 i = 0; i < in[0]; ++i) t.each(0, [&](u32 k) { return fq12_frob_coeff(t.s, 1, k, c); });
+    } else pr_final_exp(t, c);
+    put(out);
     return H2R_OK;
 } H2R_CATCH_STATUS
 

@@ -882,7 +882,8 @@ def verify_proof(vk: VerifyingKey, proofs: torch.Tensor, instances: Optional[tor
 def combine(left: torch.Tensor, right: torch.Tensor, status: torch.Tensor, seed: bytes, chip):
     """(L*, R*), uint8 [64] each: the batch folded into ONE pair, L* = sum_e rho_e left[e] and R* = sum_e rho_e right[e], so that the
     caller's one pairing check e(L*, [tau]G2) = e(R*, G2) accepts every circuit whose status is 0 TOGETHER (a circuit with a nonzero
-    status gets rho_e = 0 on the device and its points are not read: it is dropped, and stays rejected by its status).  rho_e is the
+    status gets rho_e = 0 on the device and its points are not read: it is dropped, and stays rejected by its status).  That check runs on
+    the device too: pairing_check(pkey, torch.stack((L*, R*))[None], 0b10) at batch 1.  rho_e is the
     generator's element (seed, circuit e, TAG_COMBINE, row 0) (h2r_random_columns).  `seed` (32 bytes) MUST BE UNKNOWN TO WHOEVER MADE THE
     PROOFS -- draw it after the proofs exist: one who knows rho can make two bad proofs whose errors cancel in the fold.  A batch above
     4,096 is summed in chunks of 4,096, and the chunks' sums once more."""
@@ -911,3 +912,64 @@ def combine(left: torch.Tensor, right: torch.Tensor, status: torch.Tensor, seed:
         res.append(part.reshape(64))
     hold(chip, "combine", rho, res)
     return res[0], res[1]
+
+
+# ---- the verdict: the pairing check ------------------------------------------------------------------------------------
+class PairingKey:
+    """The prepared tables of fixed G2 points, held on the device: h2r_pairing_prepare runs once per point on the host (102 line
+    coefficients, 13,056 bytes per point), no G2 arithmetic runs per proof.  g2_points: up to 4 affine points of 128 bytes each (x.re, x.im,
+    y.re, y.im in the chip's representation) as bytes or tensors.  The KZG verifier's key is PairingKey(chip, [tau_g2, g2]).  The points are
+    key material: they must lie on the twist (checked) and in the subgroup of order r (NOT checked)."""
+
+    def __init__(self, chip, g2_points):
+        pts = [bytes(p.detach().cpu().contiguous().view(torch.uint8).reshape(-1).tolist()) if isinstance(p, torch.Tensor) else bytes(p) for p in g2_points]
+        if not 0 < len(pts) <= _lib.H2R_PAIRING_MAX_PAIRS or any(len(p) != 128 for p in pts):
+            check(_lib.H2R_E_SHAPE, "PairingKey")
+        tabs = bytearray()
+        for p in pts:
+            t = (ctypes.c_uint8 * _lib.H2R_PAIRING_TABLE_BYTES)()
+            check(lib().h2r_pairing_prepare(chip._ctx, p, t), "h2r_pairing_prepare")
+            tabs += bytes(t)
+        self.chip, self.num_pairs = chip, len(pts)
+        self.tables = torch.frombuffer(tabs, dtype=torch.uint8).to("cuda:%d" % chip.device)
+
+
+def pairing_check(pkey: PairingKey, points: torch.Tensor, negate_mask: int = 0, status: Optional[torch.Tensor] = None, out=None):
+    """(accept, gt): for every circuit e the product over j of e(points[e][j], pkey's point j), y of pair j negated where bit j of
+    negate_mask is set (h2r_pairing_products), with no host synchronisation.  points: uint8 [batch, num_pairs, 64] (or int64 [batch,
+    num_pairs, 2, 4]) on the device, affine G1 points in the chip's representation, (0, 0) the identity; the rows of a circuit contiguous,
+    any 16-byte-aligned stride between circuits.  accept uint8 [batch]: 1 iff the circuit's status is 0 after the call and the product is
+    one, written for every circuit.  gt uint8 [batch, 384]: the product's value, left as it was for a flagged circuit (zeros when the call
+    allocates).  status uint8 [batch]: nonzero on entry skips the circuit; H2R_E_SHAPE for a coordinate >= q, H2R_E_ASSERTION for a point
+    off the curve; never cleared.  out: (accept, gt) to write into, either may be None to leave that output out."""
+    chip, J = pkey.chip, pkey.num_pairs
+    if not isinstance(points, torch.Tensor) or not points.is_cuda or points.dtype not in (torch.uint8, torch.int64) or points.dim() < 2:
+        check(_lib.H2R_E_SHAPE, "pairing_check")
+    batch, row = int(points.shape[0]), points[0]
+    if batch < 1 or row.numel() * row.element_size() != 64 * J or not row.is_contiguous():
+        check(_lib.H2R_E_SHAPE, "pairing_check")
+    stride = points.stride(0) * points.element_size() if batch > 1 else 64 * J
+    accept, gt = outputs(out, points.device, (torch.empty, torch.uint8, (batch,)), (torch.zeros, torch.uint8, (batch, 384)))
+    if (accept is not None and (accept.dtype != torch.uint8 or tuple(accept.shape) != (batch,))) or (gt is not None and (gt.dtype != torch.uint8 or tuple(gt.shape) != (batch, 384))):
+        check(_lib.H2R_E_SHAPE, "pairing_check")
+    assert (accept is None or accept.is_contiguous()) and (gt is None or gt.is_contiguous()) and (status is None or status.is_contiguous())
+    cfg = _lib.H2RPairingConfig(struct_size=ctypes.sizeof(_lib.H2RPairingConfig), num_pairs=J, negate_mask=negate_mask, reserved=0)
+    check(lib().h2r_pairing_products(chip._ctx, ctypes.byref(cfg), pkey.tables.data_ptr(), points.data_ptr(), stride, batch, ptr(gt), ptr(accept), ptr(status),
+                                     chip._stream()), "h2r_pairing_products")
+    hold(pkey, "pairing_check", points, status, accept, gt)
+    return accept, gt
+
+
+def verify(vk: VerifyingKey, pkey: PairingKey, proofs: torch.Tensor, instances: Optional[torch.Tensor] = None, out=None):
+    """(accept, status): halo2's verify_proof to its verdict for `batch` independent one-circuit proofs, proof bytes in, no host access in
+    between: verify_proof's accumulators, then e(left[e], [tau]G2) e(-right[e], G2) = 1 per circuit.  pkey: PairingKey(chip, [tau_g2, g2]).
+    accept uint8 [batch]: 1 iff the circuit's status is 0 and the pairing check holds.  status as verify_proof's.  out: (accept, status) to
+    write into; a status byte that is nonzero on entry skips the circuit."""
+    batch, dev = int(proofs.shape[0]), proofs.device
+    if pkey.num_pairs != 2:
+        check(_lib.H2R_E_SHAPE, "verify")
+    accept, status = outputs(out, dev, (torch.empty, torch.uint8, (batch,)), status=batch)
+    acc = (torch.zeros((batch, 64), dtype=torch.uint8, device=dev), torch.zeros((batch, 64), dtype=torch.uint8, device=dev), status)
+    left, right, _ = verify_proof(vk, proofs, instances, out=acc)
+    pairing_check(pkey, torch.stack((left, right), dim=1), 0b10, status, out=(accept, None))
+    return accept, status

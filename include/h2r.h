@@ -1220,7 +1220,8 @@ int32_t h2r_random_eval(const h2r_ctx *ctx, const uint8_t seed[32], uint64_t cir
  * batch is `batch` independent one-circuit proofs (section 2m).  A proof is accepted iff e(L, [tau]G2) = e(R, G2) with
  *     L = sum_p u^p W_p        R = sum_p u^p (z_p W_p + sum_i v^i C_{p,i} - [sum_i v^i e_{p,i}] G)
  * over the point sets p = 0..3 at z_p = x, omega x, omega^-(blinding_factors + 1) x, omega^-1 x, u the challenge drawn after the four W.
- * G2 and the pairing are NOT here: the caller runs that one check (per batch, after folding: prover.combine).  Only a ctx whose field
+ * G2 and the pairing are NOT in these four calls: h2r_pairing_products below gives the verdict (per circuit, or per batch after folding:
+ * prover.combine).  Only a ctx whose field
  * has a curve; everything in the ctx's representation; every call enqueues on `stream` and never synchronises; no workgroup waits for
  * another, no atomics.  status (nullable, [batch]) is never cleared: a circuit whose byte is nonzero on entry is skipped and nothing of
  * it is written.
@@ -1294,6 +1295,43 @@ int32_t h2r_msm_terms(const h2r_ctx *ctx, const h2r_msm_terms_config *cfg, const
                       uint64_t bases_elem_stride, uint64_t batch, void *out, uint8_t *status, h2r_stream_t stream);
 int32_t h2r_verify_eval(const h2r_ctx *ctx, uint32_t op, const h2r_verify_scalars_config *cfg, const uint8_t *in, uint64_t in_len, uint8_t *out,
                         uint64_t out_len);
+/* ---- the verifier's verdict: the bn256 pairing check ---------------------------------------------
+ * DESIGN.md section 2o.  A restatement held to a Python model (tests/pairing_ref.py); byte parity with halo2curves' Gt is not claimed.
+ * u = 4965661367192848881; Fq2 = Fq[i] / (i^2 + 1), xi = 9 + i, Fq12 = Fq2[w] / (w^6 - xi).  An Fq12 value is its six Fq2 coefficients
+ * of w^0..w^5 as c0.re, c0.im, c1.re, ...: 384 bytes.  G2 is the twist E': y^2 = x^3 + 3 / xi; an affine G2 point is 128 bytes: x.re, x.im,
+ * y.re, y.im; a G1 point is 64 bytes, (0, 0) the identity (section 2i).  Everything in the ctx's representation (a Montgomery ctx: x * R
+ * mod q), canonical representatives.  Only a ctx whose field has a curve.
+ * h2r_pairing_prepare (host only; works on a host-only ctx): the table of a FIXED G2 point -- the verifier's [tau]G2 and G2 are key material, no
+ *    G2 arithmetic runs per proof.  T walks from Q over the bits of 6 u + 2 below the top one (64 doublings, an addition of Q after each
+ *    of the 36 set bits), then T += pi(Q) and the line through T and -pi^2(Q): H2R_PAIRING_STEPS = 102 steps of (lambda, c = lambda x_T -
+ *    y_T), 128 bytes each.  The line of a step at P = (x_P, y_P) is y_P + (-lambda x_P) w + c w^3.  H2R_E_SHAPE for a coordinate >= q,
+ *    H2R_E_ASSERTION for the identity or a point off E'.  Membership of the order-r subgroup is NOT checked: key material.
+ * h2r_pairing_products: for every circuit e the product over j < num_pairs of the pairings of points[e][j] (64 bytes at points + e *
+ *    points_elem_stride + 64 j; y negated in the kernel where bit j of negate_mask is set) with the fixed point of tables[j] (device,
+ *    num_pairs tables back to back): f = 1; per bit f <- f^2 prod_j line_j, then the addition lines, then the two Frobenius lines;
+ *    gt[e] = f^((q^12 - 1) / r) exactly.  A (0, 0) operand contributes no lines.  accept[e] (nullable) is written for EVERY circuit: 1 iff
+ *    its status is 0 after the call and gt is one, else 0.  gt (nullable, [batch][384]) of a flagged circuit is left as it was.  A status
+ *    nonzero on entry skips the circuit; status (nullable) is never cleared.  Each operand is validated in the kernel: H2R_E_SHAPE for a
+ *    coordinate >= q, else H2R_E_ASSERTION for a point that is neither (0, 0) nor on the curve (H2R_E_SHAPE wins in a circuit).  The
+ *    verifier's check: num_pairs = 2, tables of [tau]G2 and G2, points (left, right), negate_mask = 2.  A team of eight lanes per circuit,
+ *    eight circuits per workgroup; enqueues on `stream`, never synchronises; no workgroup waits for another, no atomics.
+ * h2r_pairing_eval (host only; works on a host-only ctx) runs the very functions the kernel inlines: op 0 = Fq12 product (in 768, out
+ *    384); 1 = Fq12 inverse (in 384, out 384; H2R_E_SHAPE for zero); 2 = Frobenius^k (in a k byte <= 11 and 384, out 384); 3 = the Miller
+ *    value (in: J, negate_mask, then per pair a 64-byte point and a table; out 384; the return value is the operands' status); 4 = the
+ *    final exponentiation (in 384, out 384); 5 = the whole check (in as op 3; out an accept byte and 384).
+ *  - H2R_E_NULL for a NULL required pointer (gt, accept and status are optional); H2R_E_UNSUPPORTED for another struct_size, a field
+ *    without a curve, a host-only ctx (h2r_pairing_products only, after every other check); H2R_E_SHAPE for num_pairs = 0 or > 4, a bit of
+ *    negate_mask at or above num_pairs, a nonzero `reserved`, a pointer or stride that is not 16-byte aligned, a nonzero stride below 64
+ *    num_pairs, an output overlapping an input, another output or status, another op, in_len or out_len, an Fq12 coordinate >= q.
+ *    batch = 0 returns H2R_OK with no launch. */
+#define H2R_PAIRING_STEPS       102
+#define H2R_PAIRING_TABLE_BYTES 13056
+#define H2R_PAIRING_MAX_PAIRS   4
+typedef struct h2r_pairing_config { uint32_t struct_size, num_pairs, negate_mask, reserved; } h2r_pairing_config;
+int32_t h2r_pairing_prepare(const h2r_ctx *ctx, const uint8_t *g2, uint8_t *table);
+int32_t h2r_pairing_products(const h2r_ctx *ctx, const h2r_pairing_config *cfg, const void *tables, const void *points, uint64_t points_elem_stride,
+                             uint64_t batch, void *gt, uint8_t *accept, uint8_t *status, h2r_stream_t stream);
+int32_t h2r_pairing_eval(const h2r_ctx *ctx, uint32_t op, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_len);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1599,7 +1637,8 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_RANDOM = 30 /* random_kernel: the prover's blinding values */,
        H2R_KERNEL_PROOF_DECODE = 31 /* proof_decode_kernel: two launches per call */, H2R_KERNEL_VERIFY_SCALARS = 32 /* verify_scalars_kernel */,
        H2R_KERNEL_MSM_TERMS = 33 /* msm_terms_kernel */,
-       H2R_KERNEL_COUNT = 34 };
+       H2R_KERNEL_PAIRING = 34 /* pairing_kernel */,
+       H2R_KERNEL_COUNT = 35 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
