@@ -16,6 +16,12 @@ assert len(PLANES) == H2R_PL_COUNT
 H2R_OK, H2R_E_SHAPE, H2R_E_ZERO_MODULUS, H2R_E_NOT_REDUCED, H2R_E_FIELD_TOO_SMALL, H2R_E_HIP, H2R_E_UNSUPPORTED, \
     H2R_E_NULL, H2R_E_NOT_IN_FIELD, H2R_E_ASSERTION = range(10)
 FIELDS = {"bn254_fr": 0, "bn254_fq": 1, "pasta_fp": 2, "pasta_fq": 3}
+# delta per field, canonical: g^(2^S) for p - 1 = 2^S * odd and g the smallest quadratic non-residue -- halo2's generator of the odd-order
+# subgroup, the permutation argument's column shift (tests/permutation_ref.py::domain derives it; tests/test_keygen_host.py compares)
+FIELD_DELTA = {"bn254_fr": 0x0ba49465f79ce3ca21f1ec72be9f9a263f544c14cc40ac6ba1458af683d28e01,
+               "bn254_fq": 0x9,
+               "pasta_fp": 0x0a757d0f0006ab6cbd455b7112a5049df5e4f3f13eee56366a6ccd20dd7b9ba2,
+               "pasta_fq": 0x2237d5442372416606f0a88e7f7949f8e3ac3376541d11408494392472d1683c}
 H2R_F_SHARED_MODULUS = 1
 H2R_F_KEYED_MODULI = 2   # `n` points to a host H2RKeyedModuli: a per-element index into a key table (h2r_key_table_build)
 
@@ -232,6 +238,10 @@ class H2RPairingConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("num_pairs", ctypes.c_uint32), ("negate_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class H2RKeygenSigmaInfo(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("hook_rounds", ctypes.c_uint32), ("touched_cells", ctypes.c_uint32), ("sort_passes", ctypes.c_uint32)]
+
+
 class H2RFixedRow(ctypes.Structure):
     NAMES = ("sa", "sb", "sc", "sd", "se", "s_mul_ab", "s_mul_cd", "se_next", "s_const")
     _fields_ = [(nm, ctypes.c_uint64 * 4) for nm in NAMES] + [("tag_composition", ctypes.c_uint32), ("tag_overflow", ctypes.c_uint32)]
@@ -287,6 +297,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_random_columns", "h2r_random_eval",
            "h2r_proof_decode", "h2r_verify_bases", "h2r_verify_scalars", "h2r_msm_terms", "h2r_verify_eval",
            "h2r_pairing_prepare", "h2r_pairing_products", "h2r_pairing_eval",
+           "h2r_keygen_fixed_workspace_bytes", "h2r_keygen_fixed_columns", "h2r_keygen_sigma_workspace_bytes", "h2r_keygen_sigma_columns", "h2r_keygen_vk_repr",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -305,6 +316,8 @@ KERNEL_TRANSCRIPT = 29
 KERNEL_RANDOM = 30
 KERNEL_PROOF_DECODE, KERNEL_VERIFY_SCALARS, KERNEL_MSM_TERMS = 31, 32, 33
 KERNEL_PAIRING = 34
+KERNEL_KEYGEN_FIXED, KERNEL_KEYGEN_COMPONENTS, KERNEL_KEYGEN_COMPACT, KERNEL_KEYGEN_SORT, KERNEL_KEYGEN_WRITE = 35, 36, 37, 38, 39
+H2R_KEYGEN_NUM_FIXED = 15
 H2R_PAIRING_STEPS, H2R_PAIRING_TABLE_BYTES, H2R_PAIRING_MAX_PAIRS = 102, 13056, 4
 FIELD_MUL, FIELD_TO_MONTGOMERY, FIELD_FROM_MONTGOMERY = 2, 6, 7   # h2r_field_eval's operations a * b, a * R and a * R^-1 mod p (include/h2r.h)
 H2R_HASHED_MSG_STREAM_BYTES = 288
@@ -548,6 +561,13 @@ def lib():
     L.h2r_pairing_prepare.argtypes = [vp, ctypes.c_char_p, vp]
     L.h2r_pairing_products.argtypes = [vp, ctypes.POINTER(H2RPairingConfig), vp, vp, u64, u64, vp, vp, vp, vp]
     L.h2r_pairing_eval.argtypes = [vp, u32, ctypes.c_char_p, u64, vp, u64]
+    L.h2r_keygen_fixed_workspace_bytes.argtypes = [ctypes.POINTER(H2RLookupConfig)]
+    L.h2r_keygen_fixed_workspace_bytes.restype = u64
+    L.h2r_keygen_fixed_columns.argtypes = [vp, ctypes.POINTER(H2RLookupConfig), ctypes.POINTER(H2RAdviceLayout), vp, u64, u32, u32, u32, vp, u64, vp, vp, vp]
+    L.h2r_keygen_sigma_workspace_bytes.argtypes = [u32, u32, u64]
+    L.h2r_keygen_sigma_workspace_bytes.restype = u64
+    L.h2r_keygen_sigma_columns.argtypes = [vp, ctypes.POINTER(H2RPermutationConfig), vp, u64, u32, u32, u32, vp, u64, vp, vp, ctypes.POINTER(H2RKeygenSigmaInfo), vp]
+    L.h2r_keygen_vk_repr.argtypes = [vp, pvs, u32, ctypes.c_char_p, pu64]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.h2r_dist_destroy.argtypes = [vp]

@@ -373,7 +373,7 @@ class BigIntChip:
         """BigIntChip::new (big_integer/chip.rs:1174-1185); raises where the reference asserts.
         columns / montgomery / col_stride: the representation of the advice images and of every field element that crosses the
         boundary (h2r_advice_repr): planar column vectors instead of 160-byte rows, x * R mod p instead of canonical integers."""
-        self.limb_width, self.bits_len, self.device = limb_width, bits_len, device
+        self.limb_width, self.bits_len, self.device, self.field = limb_width, bits_len, device, field
         self.columns, self.montgomery, self.col_stride = bool(columns), bool(montgomery), int(col_stride)
         self._ctx = ctypes.c_void_p()
         p = H2RParams(limb_width, bits_len, _lib.FIELDS[field], device)

@@ -34,6 +34,7 @@
 #include "h2r_random.hpp"
 #include "h2r_verify.hpp"
 #include "h2r_pairing.hpp"
+#include "h2r_keygen.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4369,7 +4370,8 @@ static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_O
               H2R_KERNEL_CURVE_NTT_TWIDDLE == H2R_KERNEL_MSM_FOLD + 1 && H2R_KERNEL_CURVE_NTT_STORE == H2R_KERNEL_CURVE_NTT_TWIDDLE + 3 &&
               H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_RANDOM == H2R_KERNEL_TRANSCRIPT + 1 && H2R_KERNEL_PROOF_DECODE == H2R_KERNEL_RANDOM + 1 &&
               H2R_KERNEL_VERIFY_SCALARS == H2R_KERNEL_PROOF_DECODE + 1 && H2R_KERNEL_MSM_TERMS == H2R_KERNEL_VERIFY_SCALARS + 1 &&
-              H2R_KERNEL_PAIRING == H2R_KERNEL_MSM_TERMS + 1 && H2R_KERNEL_COUNT == H2R_KERNEL_PAIRING + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_PAIRING == H2R_KERNEL_MSM_TERMS + 1 && H2R_KERNEL_KEYGEN_FIXED == H2R_KERNEL_PAIRING + 1 &&
+              H2R_KERNEL_KEYGEN_WRITE == H2R_KERNEL_KEYGEN_FIXED + 4 && H2R_KERNEL_COUNT == H2R_KERNEL_KEYGEN_WRITE + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -5274,6 +5276,220 @@ int32_t h2r_pairing_eval(const h2r_ctx *ctx, uint32_t op, const uint8_t *in, uin
         for (u32 i = 0; i < in[0]; ++i) t.each(0, [&](u32 k) { return fq12_frob_coeff(t.s, 1, k, c); });
     } else pr_final_exp(t, c);
     put(out);
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- key generation: fixed columns, sigma columns, vk_repr (h2r_keygen.hpp, h2r_tu_keygen.hip) ----------------------
+namespace {
+static_assert(H2R_KEYGEN_NUM_FIXED == KG_NUM_FIXED && H2R_PERM_MAX_COLUMNS == KG_MAX_COLUMNS && sizeof(h2r_copy) == 16 && sizeof(KgKind) == 448 &&
+              sizeof(h2r_keygen_sigma_info) == 16, "h2r.h and the kernels' argument structs");
+constexpr u32 kKeygenMaxRounds = 1u << 16;   // hook rounds (every changing round lowers a label: far fewer in practice)
+bool keygen_lookup_cfg_valid(const h2r_lookup_config *cfg) {
+    if (cfg->n_rows == 0 || cfg->n_rows > (u32)LOOKUP_MAX_ROWS || cfg->n_lens > H2R_LOOKUP_MAX_LENS) return false;
+    for (u32 i = 0; i < cfg->n_lens; ++i)
+        if (cfg->bit_len[i] > 10 || (u64)cfg->row_off[i] + (1ull << cfg->bit_len[i]) > cfg->n_rows) return false;
+    return true;
+}
+bool keygen_rows_valid(u32 log_n, u32 usable_rows) { return log_n >= 1 && log_n <= KG_MAX_LOG_N && usable_rows >= 1 && usable_rows < (1ull << log_n); }
+// the sigma workspace's arrays behind its 256-byte aligned base, all u32: ctrl, label, touched, tile_count, keys x 2, vals x 2, hist
+struct KeygenSigmaPlan { u64 cells, tiles, cap, sort_tiles, off_label, off_touched, off_tile, off_keys[2], off_vals[2], off_hist, total; };
+KeygenSigmaPlan keygen_sigma_plan(u32 log_n, u32 m, u64 n_copies) {
+    KeygenSigmaPlan p;
+    p.cells = (u64)m << log_n; p.tiles = (p.cells + KG_TILE - 1) / KG_TILE;
+    p.cap = std::min<u64>(p.cells, 2 * n_copies); p.sort_tiles = (p.cap + KG_TILE - 1) / KG_TILE;
+    u64 off = round_up(4ull * KG_CTRL_WORDS, 256);
+    auto take = [&](u64 words) { const u64 at = off; off += round_up(4 * words, 256); return at; };
+    p.off_label = take(p.cells); p.off_touched = take(p.cells); p.off_tile = take(p.tiles);
+    for (int s = 0; s < 2; ++s) { p.off_keys[s] = take(p.cap); p.off_vals[s] = take(p.cap); }
+    p.off_hist = take(256 * p.sort_tiles);
+    p.total = off + 256;
+    return p;
+}
+}  // namespace
+
+uint64_t h2r_keygen_fixed_workspace_bytes(const h2r_lookup_config *cfg) try {
+    if (!cfg || !keygen_lookup_cfg_valid(cfg)) return 0;
+    return 256 * sizeof(KgKind) + round_up((u64)cfg->n_rows * sizeof(KgTableRow), 256) + 256;
+} H2R_CATCH_ZERO
+
+int32_t h2r_keygen_fixed_columns(const h2r_ctx *ctx, const h2r_lookup_config *cfg, const h2r_advice_layout *layout, const uint8_t *kinds_dev, uint64_t rows,
+                                 uint32_t first_row, uint32_t log_n, uint32_t usable_rows, void *fixed_out, uint64_t col_stride, uint8_t *status,
+                                 void *workspace, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !fixed_out || !status || !workspace || (rows && !kinds_dev)) return H2R_E_NULL;
+    h2r_advice_layout ident;
+    if (!layout) { h2r_advice_layout_default(&ident); layout = &ident; }
+    else if (const int32_t rc = layout_valid(layout)) return rc;
+    if (!keygen_rows_valid(log_n, usable_rows) || !keygen_lookup_cfg_valid(cfg)) return H2R_E_SHAPE;
+    if ((u64)first_row + rows > usable_rows || cfg->n_rows > usable_rows) return H2R_E_SHAPE;
+    if (misaligned(fixed_out, col_stride) || col_stride < (32ull << log_n)) return H2R_E_SHAPE;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    const bool mont = ctx_mont(ctx);
+    // the table of every kind the array can name, and the lookup table's rows: built per call, uploaded behind the workspace's base
+    std::vector<KgKind> tab(256);
+    std::memset(static_cast<void *>(tab.data()), 0, tab.size() * sizeof(KgKind));
+    auto small = [&](u32 v) { return mont ? fe_to_mont(fe_small(v), ctx->fc) : fe_small(v); };
+    for (u32 k = 0; k < 256; ++k) {
+        h2r_fixed_row f, g;
+        if (fixed_row_repr(ctx, cfg, k, mont, &f)) continue;
+        u8 col[5];
+        for (int c = 0; c < 5; ++c) col[c] = layout->column_of[k][c];
+        layout_permute_fixed(col, f, &g);
+        const uint64_t (*sel[9])[4] = {&g.sa, &g.sb, &g.sc, &g.sd, &g.se, &g.s_mul_ab, &g.s_mul_cd, &g.se_next, &g.s_const};
+        for (int q = 0; q < 9; ++q) tab[k].v[q] = fe_words(*sel[q]);
+        tab[k].v[9] = small(g.tag_composition); tab[k].v[10] = small(g.tag_composition ? 1 : 0);
+        tab[k].v[11] = small(g.tag_overflow); tab[k].v[12] = small(g.tag_overflow ? 1 : 0);
+        tab[k].valid = 1;
+    }
+    std::vector<KgTableRow> table(cfg->n_rows, KgTableRow{0, 0});
+    for (u32 i = 0; i < cfg->n_lens; ++i)
+        for (u32 v = 0; v < (1u << cfg->bit_len[i]); ++v) table[cfg->row_off[i] + v] = KgTableRow{cfg->tag[i], v};
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    u8 *ws = workspace_256(workspace);
+    KeygenFixedArgs fa;
+    std::memset(static_cast<void *>(&fa), 0, sizeof fa);
+    fa.tab = reinterpret_cast<const KgKind *>(ws); fa.table = reinterpret_cast<const KgTableRow *>(ws + 256 * sizeof(KgKind));
+    HIP_TRY(hipMemcpyAsync(ws, tab.data(), tab.size() * sizeof(KgKind), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(ws + 256 * sizeof(KgKind), table.data(), table.size() * sizeof(KgTableRow), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));               // (the two host tables are this call's own)
+    fa.kinds = kinds_dev; fa.rows = rows; fa.first_row = first_row; fa.log_n = log_n; fa.table_rows = cfg->n_rows; fa.mont = mont ? 1u : 0u;
+    fa.out = static_cast<u8 *>(fixed_out); fa.col_stride = col_stride; fa.status = status; fa.f = ctx->fc;
+    return stage_launch(H2R_KERNEL_KEYGEN_FIXED, st, [&](hipEvent_t a, hipEvent_t b) { return launch_keygen_fixed(fa, st, a, b); });
+} H2R_CATCH_STATUS
+
+uint64_t h2r_keygen_sigma_workspace_bytes(uint32_t log_n, uint32_t num_columns, uint64_t n_copies) try {
+    if (log_n < 1 || log_n > KG_MAX_LOG_N || num_columns < 1 || num_columns > KG_MAX_COLUMNS || n_copies > (1ull << 31)) return 0;
+    return keygen_sigma_plan(log_n, num_columns, n_copies).total;
+} H2R_CATCH_ZERO
+
+int32_t h2r_keygen_sigma_columns(const h2r_ctx *ctx, const h2r_permutation_config *cfg, const h2r_copy *copies_dev, uint64_t n_copies, uint32_t first_row,
+                                 uint32_t log_n, uint32_t usable_rows, void *sigma_out, uint64_t col_stride, uint8_t *status, void *workspace,
+                                 h2r_keygen_sigma_info *info, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !sigma_out || !status || !workspace || (n_copies && !copies_dev)) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_permutation_config) || (info && info->struct_size != sizeof(h2r_keygen_sigma_info))) return H2R_E_UNSUPPORTED;
+    const u32 m = cfg->num_columns;
+    if (m < 1 || m > KG_MAX_COLUMNS || !keygen_rows_valid(log_n, usable_rows) || n_copies > (1ull << 31)) return H2R_E_SHAPE;
+    u32 col_map = 0;   // nibbles 0..4: the physical columns; 5..7: the extra columns (no pair names one: only "each once" is asked of them)
+    for (u32 p = 0; p < 8; ++p) col_map |= KG_ABSENT << (4 * p);
+    for (u32 c = 0; c < m; ++c) {
+        const u32 p = cfg->column_src[c];
+        if (p >= 5 + H2R_PERM_MAX_EXTRA || ((col_map >> (4 * p)) & 15u) != KG_ABSENT) return H2R_E_SHAPE;
+        col_map = (col_map & ~(15u << (4 * p))) | (c << (4 * p));
+    }
+    if (ge_p(cfg->delta, ctx->fc.p) || ge_p(cfg->omega, ctx->fc.p)) return H2R_E_SHAPE;
+    const FieldConsts &f = ctx->fc;
+    const Fe omega = cfg_to_mont(ctx, cfg->omega);
+    if (!is_primitive_root(omega, log_n, f)) return H2R_E_SHAPE;
+    if (misaligned(sigma_out, col_stride) || misaligned(workspace) || misaligned(copies_dev) || col_stride < (32ull << log_n)) return H2R_E_SHAPE;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    const KeygenSigmaPlan plan = keygen_sigma_plan(log_n, m, n_copies);
+    KeygenSigmaArgs sa;
+    std::memset(static_cast<void *>(&sa), 0, sizeof sa);
+    u8 *ws = workspace_256(workspace);
+    auto words = [&](u64 off) { return reinterpret_cast<u32 *>(ws + off); };
+    sa.copies = copies_dev; sa.n_copies = n_copies; sa.first_row = first_row; sa.usable_rows = usable_rows; sa.log_n = log_n; sa.m = m;
+    sa.n_cells = (u32)plan.cells; sa.n_tiles = (u32)plan.tiles; sa.col_map = col_map; sa.mont = ctx_mont(ctx) ? 1u : 0u;
+    sa.ctrl = words(0); sa.label = words(plan.off_label); sa.touched = words(plan.off_touched); sa.tile_count = words(plan.off_tile); sa.hist = words(plan.off_hist);
+    for (int s = 0; s < 2; ++s) { sa.keys[s] = words(plan.off_keys[s]); sa.vals[s] = words(plan.off_vals[s]); }
+    fe_power_table(sa.dpow, KG_MAX_COLUMNS, cfg_to_mont(ctx, cfg->delta), f);
+    fe_squaring_chain(sa.wpow, KG_MAX_LOG_N, omega, f);
+    sa.f = f; sa.sigma = static_cast<u8 *>(sigma_out); sa.col_stride = col_stride; sa.status = status;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    auto run = [&](u32 kernel_class, u32 phase) {
+        return stage_launch(kernel_class, st, [&](hipEvent_t a, hipEvent_t b) { return launch_keygen_sigma(phase, sa, st, a, b); });
+    };
+    auto read_word = [&](u32 index, u32 *out) -> int32_t {   // (stream-ordered, then waited for: keygen runs once per circuit shape)
+        HIP_TRY(hipMemcpyAsync(out, sa.ctrl + index, sizeof(u32), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        return H2R_OK;
+    };
+    u32 rounds = 0, touched = 0, passes = 0;
+    if (const int32_t rc = run(H2R_KERNEL_KEYGEN_WRITE, KG_PHASE_IDENTITY)) return rc;
+    if (n_copies) {
+        // 1. the components: every touched cell gets the smallest id of its class
+        if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPONENTS, KG_PHASE_INIT)) return rc;
+        if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPONENTS, KG_PHASE_MARK)) return rc;
+        for (;;) {
+            if (rounds == kKeygenMaxRounds) return H2R_E_INTERNAL;
+            if (rounds) HIP_TRY(hipMemsetAsync(sa.ctrl, 0, sizeof(u32), st));
+            if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPONENTS, KG_PHASE_HOOK)) return rc;
+            if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPONENTS, KG_PHASE_COMPRESS)) return rc;
+            ++rounds;
+            u32 changed = 0;
+            if (const int32_t rc = read_word(0, &changed)) return rc;
+            if (!changed) break;
+        }
+        // 2. the touched cells in id order, sorted by label (stable): classes side by side, ascending inside
+        if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPACT, KG_PHASE_COUNT)) return rc;
+        if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPACT, KG_PHASE_TILE_SCAN)) return rc;
+        if (const int32_t rc = read_word(1, &touched)) return rc;
+        if (touched > plan.cap) return H2R_E_INTERNAL;   // (two cells per kept pair at most)
+        if (touched) {
+            if (const int32_t rc = run(H2R_KERNEL_KEYGEN_COMPACT, KG_PHASE_COMPACT)) return rc;
+            sa.n_touched = touched; sa.sort_tiles = (touched + KG_TILE - 1) / KG_TILE;
+            u32 bits = 0;
+            while (bits < 32 && ((plan.cells - 1) >> bits)) ++bits;
+            passes = (bits + 7) / 8;
+            for (u32 p = 0; p < passes; ++p) {
+                sa.shift = 8 * p; sa.src = p & 1u;
+                for (u32 phase = KG_PHASE_SORT_HIST; phase <= KG_PHASE_SORT_SCATTER; ++phase)
+                    if (const int32_t rc = run(H2R_KERNEL_KEYGEN_SORT, phase)) return rc;
+            }
+            // 3. every touched cell takes its successor's label
+            sa.src = passes & 1u;
+            if (const int32_t rc = run(H2R_KERNEL_KEYGEN_WRITE, KG_PHASE_SCATTER)) return rc;
+        }
+    }
+    if (info) { info->hook_rounds = rounds; info->touched_cells = touched; info->sort_passes = passes; }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_keygen_vk_repr(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, uint32_t extended_k, const uint8_t *points, uint64_t out[4]) try {
+    if (!ctx || !cfg || !points || !out) return H2R_E_NULL;
+    if (cfg->struct_size != sizeof(h2r_verify_scalars_config)) return H2R_E_UNSUPPORTED;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    const u32 F = cfg->num_fixed, m = cfg->num_columns;
+    if (cfg->log_n < 1 || cfg->log_n > KG_MAX_LOG_N || extended_k < cfg->log_n || extended_k > 27 || F > 16 || m < 1 || m > KG_MAX_COLUMNS) return H2R_E_SHAPE;
+    for (u32 c = 0; c < m; ++c) if (cfg->column_src[c] >= 5) return H2R_E_SHAPE;
+    if (ge_p(cfg->omega, ctx->fc.p) || ge_p(cfg->delta, ctx->fc.p)) return H2R_E_SHAPE;
+    const TrConsts c = transcript_consts(ctx, *cv);
+    std::vector<u8> msg;
+    auto le32 = [&](u32 v) { for (int b = 0; b < 4; ++b) msg.push_back((u8)(v >> (8 * b))); };
+    auto element = [&](const Fe &x) { for (int k = 0; k < 4; ++k) for (int b = 0; b < 8; ++b) msg.push_back((u8)(x.v[k] >> (8 * b))); };
+    le32(ctx->params.field); le32(cfg->log_n); le32(cfg->blinding_factors); le32(F); le32(m); le32(cfg->chunk_len); le32(cfg->lookup_mask);
+    for (u32 i = 0; i < KG_MAX_COLUMNS; ++i) msg.push_back(i < m ? cfg->column_src[i] : 0);
+    msg.insert(msg.end(), cfg->gate_fixed, cfg->gate_fixed + 9);
+    msg.insert(msg.end(), cfg->lookup_advice, cfg->lookup_advice + H2R_LOOKUP_ARGS);
+    msg.insert(msg.end(), cfg->lookup_tag, cfg->lookup_tag + H2R_LOOKUP_ARGS);
+    msg.insert(msg.end(), cfg->lookup_enable, cfg->lookup_enable + H2R_LOOKUP_ARGS);
+    msg.push_back(cfg->table_tag); msg.push_back(cfg->table_value);
+    element(c.mont ? fe_from_mont(fe_words(cfg->omega), c.fr) : fe_words(cfg->omega));
+    element(c.mont ? fe_from_mont(fe_words(cfg->delta), c.fr) : fe_words(cfg->delta));
+    le32(extended_k);
+    for (u32 i = 0; i < 2 * (F + m + 1); ++i) {          // coordinates: x, y of every point
+        Fe x; std::memcpy(x.v, points + 32ull * i, 32);
+        if (ge_p(x.v, c.fq.p)) return H2R_E_SHAPE;
+        element(c.mont ? fe_from_mont(x, c.fq) : x);
+    }
+    // the transcript's BLAKE2b under this digest's own personalisation
+    TrHash s;
+    tr_init(s);
+    s.h[6] = 0x1f83d9abfb41bd6bull ^ 0x697265562d523248ull;   // "H2R-Veri"
+    s.h[7] = 0x5be0cd19137e2179ull ^ 0x31762d79654b7966ull;   // "fyKey-v1"
+    u64 block[16] = {0};
+    const TrBlock blk{block, 1};
+    for (size_t off = 0; off < msg.size(); off += 8) {
+        const u32 n = (u32)std::min<size_t>(8, msg.size() - off);
+        u64 v = 0;
+        for (u32 b = 0; b < n; ++b) v |= (u64)msg[off + b] << (8 * b);
+        tr_absorb(s, blk, v, n);
+    }
+    u64 d[8];
+    tr_digest(s, blk, d);
+    const Fe r = tr_to_repr(tr_reduce_wide(d, c), c);
+    for (int k = 0; k < 4; ++k) out[k] = r.v[k];
     return H2R_OK;
 } H2R_CATCH_STATUS
 

@@ -18,6 +18,7 @@
 //   h2r_tu_random.hip  the prover's blinding values: a counter-based generator over the transcript's BLAKE2b (h2r_random.hpp)
 //   h2r_tu_verify.hip  the verifier up to the pairing: proof decoder, the accumulators' scalars, the sum of terms over per-circuit bases (h2r_verify.hpp)
 //   h2r_tu_pairing.hip the verifier's verdict: Miller values and final exponentiations of pairing products against prepared G2 tables (h2r_pairing.hpp)
+//   h2r_tu_keygen.hip  key generation: the fixed columns of an image's row kinds, the sigma columns of its copy pairs (h2r_keygen.hpp)
 //   h2r_tu_witness.hip   the witness kernels outside the mul_mod records: assert_in_field / encoded message (aux), the Fresh ops, SHA-256, the
 //                      in-place audit (check, link), range decompose, key expand, mul / refresh / is_equal_muled (h2r_muled.hpp), and the
 //                      arena's fill / restore kernels and the queue probe
@@ -173,6 +174,12 @@ hipError_t launch_msm_terms(const MsmTermsArgs &a, u32 num_elems, hipStream_t st
 // h2r_tu_pairing.hip (argument struct: h2r_pairing.hpp).  The workgroups [a.block0, a.block0 + num_blocks) of 8 circuits.
 struct PairingArgs;
 hipError_t launch_pairing(const PairingArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_keygen.hip (argument structs: h2r_keygen.hpp).  The fixed columns: one launch over every (row, column).  Sigma: phase = KG_PHASE_*,
+// the grid follows from the arguments (pairs, tiles of ids, tiles of sorted entries).
+struct KeygenFixedArgs;
+struct KeygenSigmaArgs;
+hipError_t launch_keygen_fixed(const KeygenFixedArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_keygen_sigma(u32 phase, const KeygenSigmaArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 // h2r_tu_witness.hip (argument structs: h2r_kernels.hpp, h2r_muled.hpp).  w = the limb width (64 | 32).  The aux kernel is the keyed build when
 // aa.key_idx is set; `lds` / `stage` = the dynamic LDS request.
 struct RefreshArgs;

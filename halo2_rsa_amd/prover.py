@@ -584,7 +584,7 @@ class ProvingKey:
     the Lagrange CommitKey, the fixed and sigma columns in Lagrange, coefficient and extended form, vanishing_columns, the row kinds, the
     lookup, permutation and quotient configurations, first_row, the image's rows, the number of h pieces and the caller's vk_repr.
     fixed: uint8 [F, 2^k, 32], sigma: uint8 [m, 2^k, 32], Lagrange form, the chip's representation; kinds: the image's row kinds; delta and
-    vk_repr: integers in the chip's representation (this library derives neither sigma nor vk_repr).  commit_key: the monomial key, at
+    vk_repr: integers in the chip's representation (keygen() below builds all four from the circuit).  commit_key: the monomial key, at
     least 2^k bases; lagrange_key: dom.lagrange_key(commit_key) when None."""
 
     def __init__(self, chip, dom: EvaluationDomain, commit_key: CommitKey, la: LookupArgument, fixed: torch.Tensor, sigma: torch.Tensor, kinds,
@@ -796,16 +796,140 @@ class VerifyingKey:
         self.vk = challenges([vk_repr], dev)
 
 
+def _key_commitments(lk: CommitKey, fixed: torch.Tensor, sigma: torch.Tensor):
+    """The commitments of the fixed and the sigma columns with the Lagrange key: int64 [1, F, 2, 4] and [1, m, 2, 4]."""
+    return lk.commit([fixed[i] for i in range(fixed.shape[0])]), lk.commit([sigma[c] for c in range(sigma.shape[0])])
+
+
 def _verifying_key(self: ProvingKey) -> VerifyingKey:
-    """The verifying half of this key: the commitments of the fixed and sigma columns, formed once with the Lagrange key."""
-    fixed = self.lk.commit([self.fixed_lag[i] for i in range(self.fixed_lag.shape[0])])
-    sigma = self.lk.commit([self.sigma_lag[c] for c in range(self.sigma_lag.shape[0])])
+    """The verifying half of this key: the commitments of the fixed and sigma columns, formed once with the Lagrange key (a key that
+    keygen() made keeps the ones it formed)."""
+    if getattr(self, "commitments", None) is None:
+        self.commitments = _key_commitments(self.lk, self.fixed_lag, self.sigma_lag)
+    fixed, sigma = self.commitments
     return VerifyingKey(self.chip, self.dom, fixed, sigma, self.ck.bases[0],self.blinding_factors, self.delta, self.gate_fixed, self.column_src, self.chunk_len,
                         self.lookup["lookup_advice"], self.lookup["lookup_tag"], self.lookup["lookup_enable"], self.lookup["table_tag"],
                         self.lookup["table_value"], from_words(self.vk[0].tolist()), lookup_mask=self.lookup["lookup_mask"], h_pieces=self.h_pieces)
 
 
 ProvingKey.verifying_key = _verifying_key
+
+
+# ---- key generation (DESIGN.md section 2p) --------------------------------------------------------------------------------------------------
+# The constraint system of an advice image: fixed columns 0..8 the gate selectors in h2r_fixed_row's order, then the table's tag and value,
+# the composition arguments' tag / enable, the overflow argument's tag / enable (h2r_keygen_fixed_columns' order).
+NUM_FIXED = _lib.H2R_KEYGEN_NUM_FIXED
+GATE_FIXED = tuple(range(9))
+F_TABLE_TAG, F_TABLE_VALUE, F_COMP_TAG, F_COMP_ENABLE, F_OVER_TAG, F_OVER_ENABLE = 9, 10, 11, 12, 13, 14
+LOOKUP_ADVICE = (0, 1, 2, 3, 0)                      # composition_a..d read columns a..d, overflow_a column a
+LOOKUP_TAG = (F_COMP_TAG,) * 4 + (F_OVER_TAG,)
+LOOKUP_ENABLE = (F_COMP_ENABLE,) * 4 + (F_OVER_ENABLE,)
+
+
+def field_delta(chip) -> int:
+    """delta of the chip's field (halo2's: a generator of the odd-order subgroup), in the chip's representation."""
+    d = _lib.FIELD_DELTA[chip.field]
+    if not chip.montgomery:
+        return d
+    wa, wb, out = ((ctypes.c_uint64 * 4)(*words(v)) for v in (d, 0, 0))
+    check(lib().h2r_field_eval(chip._ctx, _lib.FIELD_TO_MONTGOMERY, wa, wb, out), "h2r_field_eval")
+    return from_words(out)
+
+
+def copy_pairs_tensor(pairs, dev) -> torch.Tensor:
+    """int32 [n, 4] on the device: h2r_copy entries (row, col, src_row, src_col) from the ctypes array chip.pow_copy_map returns, from
+    anything numpy takes as [n, 4] unsigned integers, or a device tensor as it is."""
+    if isinstance(pairs, torch.Tensor):
+        assert pairs.is_cuda and pairs.dtype == torch.int32 and pairs.dim() == 2 and pairs.shape[1] == 4 and pairs.is_contiguous()
+        return pairs
+    if isinstance(pairs, ctypes.Array):
+        host = np.frombuffer(pairs, dtype=np.uint32).reshape(-1, 4).copy() if len(pairs) else np.zeros((0, 4), dtype=np.uint32)
+    else:
+        host = np.ascontiguousarray(pairs, dtype=np.uint32).reshape(-1, 4)
+    return torch.from_numpy(host.view(np.int32)).to(dev)
+
+
+def keygen_fixed_columns(chip, la: LookupArgument, kinds, k: int, blinding_factors: int, first_row: int = 0, layout=None, out=None):
+    """(fixed, status): the NUM_FIXED fixed columns of an image's row kinds (h2r_keygen_fixed_columns), uint8 [15, 2^k, 32] in Lagrange form
+    in the chip's representation: the image's rows from first_row on, the table's from row 0 on, 0 elsewhere.  kinds: uint8 row kinds
+    (numpy or device tensor).  status: uint8 [1] on the device, H2R_E_SHAPE where a kind has no fixed row.  out: (fixed, status)."""
+    dev = "cuda:%d" % chip.device
+    n = 1 << int(k)
+    kd = kinds_tensor(kinds, dev)
+    fixed, status = outputs(out, dev, (torch.empty, torch.uint8, (NUM_FIXED, n, 32)), status=1)
+    if not is_columns(fixed, rows=n, dims=(3,)) or fixed.shape[0] != NUM_FIXED:
+        check(_lib.H2R_E_SHAPE, "keygen_fixed_columns")
+    ws = workspace(lib().h2r_keygen_fixed_workspace_bytes(ctypes.byref(la.cfg)), dev)
+    check(lib().h2r_keygen_fixed_columns(chip._ctx, ctypes.byref(la.cfg), ref(layout), kd.data_ptr(), kd.numel(), first_row, k, n - blinding_factors - 1,
+                                         fixed.data_ptr(), fixed.stride(0), status.data_ptr(), ws.data_ptr(), chip._stream()), "h2r_keygen_fixed_columns")
+    hold(chip, "keygen_fixed_columns", kd, ws, fixed, status)
+    return fixed, status
+
+
+def keygen_sigma_columns(chip, pairs, k: int, blinding_factors: int, delta: int, omega: int, column_src: Sequence[int] = (0, 1, 2, 3, 4),
+                         first_row: int = 0, out=None):
+    """(sigma, status, info): the sigma columns of a set of copy pairs (h2r_keygen_sigma_columns), uint8 [m, 2^k, 32] in the chip's
+    representation: every class of cells ordered by (permutation column, row), sigma sends a cell to the label of its cyclic successor.
+    pairs: see copy_pairs_tensor (rows counted from the image's first row; sources outside the image are dropped); delta, omega:
+    integers in the chip's representation.  status: uint8 [1] on the device, H2R_E_SHAPE where a pair names a row >= 2^k -
+    blinding_factors - 1 or a column that column_src does not hold.  info: hook_rounds, touched_cells, sort_passes.  out: (sigma, status)."""
+    dev = "cuda:%d" % chip.device
+    n, m = 1 << int(k), len(column_src)
+    if not 0 < m <= _lib.H2R_PERM_MAX_COLUMNS:
+        check(_lib.H2R_E_SHAPE, "keygen_sigma_columns")
+    cd = copy_pairs_tensor(pairs, dev)
+    cfg = _lib.H2RPermutationConfig(struct_size=ctypes.sizeof(_lib.H2RPermutationConfig), chunk_len=1)
+    _permutation_columns(cfg, column_src)
+    set_words(cfg.delta, delta)
+    set_words(cfg.omega, omega)
+    sigma, status = outputs(out, dev, (torch.empty, torch.uint8, (m, n, 32)), status=1)
+    if not is_columns(sigma, rows=n, dims=(3,)) or sigma.shape[0] != m:
+        check(_lib.H2R_E_SHAPE, "keygen_sigma_columns")
+    ws = workspace(lib().h2r_keygen_sigma_workspace_bytes(k, m, cd.shape[0]), dev)
+    info = _lib.H2RKeygenSigmaInfo(struct_size=ctypes.sizeof(_lib.H2RKeygenSigmaInfo))
+    check(lib().h2r_keygen_sigma_columns(chip._ctx, ctypes.byref(cfg), cd.data_ptr() if cd.shape[0] else None, cd.shape[0], first_row, k,
+                                         n - blinding_factors - 1, sigma.data_ptr(), sigma.stride(0), status.data_ptr(), ws.data_ptr(),
+                                         ctypes.byref(info), chip._stream()), "h2r_keygen_sigma_columns")
+    hold(chip, "keygen_sigma_columns", cd, ws, sigma, status)
+    return sigma, status, info
+
+
+def derive_vk_repr(vk: VerifyingKey, points: bytes) -> int:
+    """This library's vk_repr of a verifying key (h2r_keygen_vk_repr): BLAKE2b-512, personalisation
+    "H2R-VerifyKey-v1", over the configuration and the F + m + 1 key points (fixed, sigma, G: 64 bytes each, the chip's representation),
+    reduced modulo r, in the chip's representation."""
+    out = (ctypes.c_uint64 * 4)()
+    check(lib().h2r_keygen_vk_repr(vk.chip._ctx, ctypes.byref(vk.cfg), vk.dom.extended_k, bytes(points), out), "h2r_keygen_vk_repr")
+    return from_words(out)
+
+
+def keygen(chip, dom: EvaluationDomain, commit_key: CommitKey, la: LookupArgument, kinds, pairs, blinding_factors: int,
+           column_src: Sequence[int] = (0, 1, 2, 3, 4), chunk_len: int = 2, first_row: int = 0, vk_repr: Optional[int] = None,
+           lagrange_key: Optional[CommitKey] = None, layout=None) -> ProvingKey:
+    """The ProvingKey of a circuit shape from what the library hands out (halo2's keygen_vk / keygen_pk): the row
+    kinds (h2r_pow_row_kinds, fresh_op_row_kinds, ...), the copy pairs (chip.pow_copy_map; rows counted from the image's first row), the
+    lookup configuration and a commit key.  The fixed and the sigma columns are built on the device, committed with the Lagrange key, and
+    the F + m + 1 key points read back -- the call's one host trip besides the builders' own --; vk_repr is derived from them
+    (derive_vk_repr) unless one is given (an integer in the chip's representation).  The constraint system is the one of an advice image:
+    GATE_FIXED, LOOKUP_ADVICE / _TAG / _ENABLE, F_TABLE_TAG / _VALUE above, delta = field_delta(chip).  key.verifying_key() reuses the
+    commitments formed here.  Raises H2RError(H2R_E_SHAPE) where a kind has no fixed row or a pair is refused."""
+    k, n = dom.k, 1 << dom.k
+    delta = field_delta(chip)
+    fixed, st_fixed = keygen_fixed_columns(chip, la, kinds, k, blinding_factors, first_row=first_row, layout=layout)
+    sigma, st_sigma, info = keygen_sigma_columns(chip, pairs, k, blinding_factors, delta, dom.omega, column_src, first_row=first_row)
+    ck = commit_key if commit_key.n == n else CommitKey(chip, commit_key.bases[:n])
+    lk = lagrange_key if lagrange_key is not None else dom.lagrange_key(ck)
+    commitments = _key_commitments(lk, fixed, sigma)
+    g = ck.bases[0].contiguous().view(torch.uint8).reshape(64)
+    host = torch.cat([commitments[0].view(torch.uint8).reshape(-1), commitments[1].view(torch.uint8).reshape(-1), g, st_fixed, st_sigma]).cpu().numpy()
+    for code in host[-2:]:
+        check(int(code), "keygen")
+    cfg = (blinding_factors, delta, GATE_FIXED, column_src, chunk_len, LOOKUP_ADVICE, LOOKUP_TAG, LOOKUP_ENABLE, F_TABLE_TAG, F_TABLE_VALUE)
+    if vk_repr is None:
+        vk_repr = derive_vk_repr(VerifyingKey(chip, dom, commitments[0], commitments[1], ck.bases[0], *cfg, 0), bytes(host[:-2]))
+    key = ProvingKey(chip, dom, ck, la, fixed, sigma, kinds, *cfg, vk_repr, first_row=first_row, lagrange_key=lk)
+    key.commitments, key.sigma_info = commitments, info
+    return key
 
 
 def msm_terms(chip, scalars: torch.Tensor, bases: torch.Tensor, num_terms: int, batch: int, scalars_stride: int, bases_stride: int, out: torch.Tensor,

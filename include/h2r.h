@@ -1332,6 +1332,58 @@ int32_t h2r_pairing_prepare(const h2r_ctx *ctx, const uint8_t *g2, uint8_t *tabl
 int32_t h2r_pairing_products(const h2r_ctx *ctx, const h2r_pairing_config *cfg, const void *tables, const void *points, uint64_t points_elem_stride,
                              uint64_t batch, void *gt, uint8_t *accept, uint8_t *status, h2r_stream_t stream);
 int32_t h2r_pairing_eval(const h2r_ctx *ctx, uint32_t op, const uint8_t *in, uint64_t in_len, uint8_t *out, uint64_t out_len);
+/* ---- key generation: the fixed columns, the sigma columns and vk_repr of one circuit shape ------------
+ * DESIGN.md section 2p.  What halo2's keygen_vk / keygen_pk derive from a circuit, from what this library hands out: the row kinds
+ * (h2r_pow_row_kinds, h2r_fresh_op_row_kinds, ...), the copy pairs (h2r_pow_copy_map), the lookup configuration.  n = 2^log_n rows,
+ * usable_rows = n - blinding_factors - 1 as h2r_quotient_columns defines it; everything in the ctx's representation.  Keygen runs once
+ * per circuit shape: unlike the prover's stages these two calls SYNCHRONISE `stream` (the upload of a table; one read of a word per
+ * round of the components and one of the touched cells' count).
+ * h2r_keygen_fixed_columns: the H2R_KEYGEN_NUM_FIXED = 15 fixed columns in Lagrange form, column c at fixed_out + c * col_stride, n rows
+ *    of 32 bytes each: the nine gate selectors in h2r_fixed_row's order (h2r_advice_fixed_row_ex of every row's kind under `layout`,
+ *    NULL = the default), then the table's tag and value (h2r_lookup_table_image), the composition arguments' tag and enable, the
+ *    overflow argument's tag and enable (enable = 1 where the tag is nonzero).  The image's `rows` rows start at first_row, the table's
+ *    at row 0, every other row is 0.  kinds_dev: the row kinds ON THE DEVICE; a kind without a fixed row under `cfg` sets *status (one
+ *    byte on the device, never cleared) to H2R_E_SHAPE and leaves zeros in its row.  workspace: h2r_keygen_fixed_workspace_bytes(cfg)
+ *    bytes on the device (the table of 256 kinds x 13 values and the lookup table's rows, uploaded per call).  One launch, one lane per
+ *    (row, column).  H2R_E_SHAPE for log_n = 0 or > 24, usable_rows = 0 or >= n, first_row + rows > usable_rows, a table of more than
+ *    usable_rows rows, col_stride < 32 n, a pointer or stride that is not 16-byte aligned.
+ * h2r_keygen_sigma_columns: sigma_out column c (c < cfg->num_columns, at + c * col_stride, n rows): sigma_c[r] = the label
+ *    delta^c' omega^r' of the NEXT cell of (c, r)'s copy class, the cell's own label where no pair names it.  copies_dev: n_copies
+ *    h2r_copy pairs ON THE DEVICE as h2r_advice_check takes them (rows counted from the image's first row: first_row is added; PHYSICAL
+ *    columns); a pair whose src_row is H2R_COPY_SRC_A / _B / _N is dropped; a physical column p is permutation column c where
+ *    cfg->column_src[c] = p (each entry once; an entry 5 + j is an extra column, which no pair can name: it keeps its labels;
+ *    chunk_len and n_extra are not read).  A class is ordered by (permutation column,
+ *    row) ascending and sigma sends a cell to its cyclic successor: the result is a function of the SET of pairs alone, whatever their
+ *    order, the launch geometry or the order in which atomics arrive.  A pair of a cell with itself and duplicate pairs are legal;
+ *    n_copies = 0 gives the labels.  *status (one byte on the device, never cleared): H2R_E_SHAPE for a pair whose row or src_row (after
+ *    first_row) is >= usable_rows or which names a physical column >= 5 or absent from column_src; sigma is unspecified then, nothing
+ *    outside sigma_out and the workspace is written.  workspace: h2r_keygen_sigma_workspace_bytes(log_n, num_columns, n_copies) bytes,
+ *    16-byte aligned.  info (nullable, host): the hook rounds run (the last one changed nothing), the touched cells, the sort passes.
+ *    H2R_E_SHAPE for log_n = 0 or > 24, usable_rows = 0 or >= n, num_columns = 0 or > 8, a column_src entry >= 8 or repeated,
+ *    delta or omega >= p, omega no primitive n-th root, n_copies > 2^31, col_stride < 32 n, misaligned pointers or strides.
+ * h2r_keygen_vk_repr (host only; works on a host-only ctx): THIS LIBRARY'S OWN definition of the verifying key's transcript scalar
+ *    (upstream hashes the Debug text of its pinned key; no parity with that is claimed): BLAKE2b-512, personalisation
+ *    "H2R-VerifyKey-v1", over  le32(field) | le32(log_n) | le32(blinding_factors) | le32(num_fixed) | le32(num_columns) | le32(chunk_len) |
+ *    le32(lookup_mask) | column_src[8] (entries from num_columns on as 0) | gate_fixed[9] | lookup_advice[5] | lookup_tag[5] |
+ *    lookup_enable[5] | table_tag | table_value | omega[32] | delta[32] | le32(extended_k) | the num_fixed fixed commitments, the
+ *    num_columns sigma commitments and G as x[32] | y[32]  -- every field element as its CANONICAL little-endian integer --, the digest
+ *    reduced as a little-endian 512-bit integer modulo r (the transcript's wide reduction), out[4] in the ctx's representation.  The two
+ *    plans of cfg are derived and not hashed.  points: num_fixed + num_columns + 1 affine points of 64 bytes in the ctx's representation
+ *    (CommitKey's commitments as they come).  A canonical and a Montgomery ctx give the same integer.  H2R_E_UNSUPPORTED for another
+ *    struct_size or a field without a curve; H2R_E_SHAPE for log_n = 0 or > 24, extended_k < log_n or > 27, num_fixed > 16, num_columns = 0
+ *    or > 8, a column_src entry >= 5, omega or delta >= r, a coordinate >= q. */
+#define H2R_KEYGEN_NUM_FIXED 15u
+struct h2r_copy;
+typedef struct h2r_keygen_sigma_info { uint32_t struct_size, hook_rounds, touched_cells, sort_passes; } h2r_keygen_sigma_info;
+uint64_t h2r_keygen_fixed_workspace_bytes(const struct h2r_lookup_config *cfg);
+int32_t h2r_keygen_fixed_columns(const h2r_ctx *ctx, const struct h2r_lookup_config *cfg, const struct h2r_advice_layout *layout, const uint8_t *kinds_dev,
+                                 uint64_t rows, uint32_t first_row, uint32_t log_n, uint32_t usable_rows, void *fixed_out, uint64_t col_stride,
+                                 uint8_t *status, void *workspace, h2r_stream_t stream);
+uint64_t h2r_keygen_sigma_workspace_bytes(uint32_t log_n, uint32_t num_columns, uint64_t n_copies);
+int32_t h2r_keygen_sigma_columns(const h2r_ctx *ctx, const h2r_permutation_config *cfg, const struct h2r_copy *copies_dev, uint64_t n_copies,
+                                 uint32_t first_row, uint32_t log_n, uint32_t usable_rows, void *sigma_out, uint64_t col_stride, uint8_t *status,
+                                 void *workspace, h2r_keygen_sigma_info *info, h2r_stream_t stream);
+int32_t h2r_keygen_vk_repr(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, uint32_t extended_k, const uint8_t *points, uint64_t out[4]);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1638,7 +1690,12 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_PROOF_DECODE = 31 /* proof_decode_kernel: two launches per call */, H2R_KERNEL_VERIFY_SCALARS = 32 /* verify_scalars_kernel */,
        H2R_KERNEL_MSM_TERMS = 33 /* msm_terms_kernel */,
        H2R_KERNEL_PAIRING = 34 /* pairing_kernel */,
-       H2R_KERNEL_COUNT = 35 };
+       H2R_KERNEL_KEYGEN_FIXED = 35 /* keygen_fixed_kernel */,
+       H2R_KERNEL_KEYGEN_COMPONENTS = 36 /* keygen_sigma's init, mark, and per round hook and compress kernels */,
+       H2R_KERNEL_KEYGEN_COMPACT = 37 /* its count, tile scan and compact kernels */,
+       H2R_KERNEL_KEYGEN_SORT = 38 /* per radix pass: histogram, scan, scatter */,
+       H2R_KERNEL_KEYGEN_WRITE = 39 /* the identity labels and the successors' scatter */,
+       H2R_KERNEL_COUNT = 40 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
