@@ -1,6 +1,6 @@
 """Builds halo2_rsa_amd/lib/libh2r.so (hand-written HIP for gfx950) in-tree with hipcc.
 
-The library is twenty-two translation units (csrc/h2r_internal.hpp lists them: one per kernel family, each with its launchers, and
+The library is twenty-three translation units (csrc/h2r_internal.hpp lists them: one per kernel family, each with its launchers, and
 h2r_api.hip, which holds host code only) compiled IN PARALLEL plus a one-line unit that carries
 the BUILD ID: the SHA-256 of every file the library is compiled from (csrc/*, include/*).  The shipped .so answers
 `h2r_build_id()` with it, and `stale()` compares that string -- read straight out of the file, nothing is loaded -- with the hash of
@@ -19,7 +19,7 @@ import time
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
-UNITS = ["h2r_api.hip", "h2r_tu_trace.hip", "h2r_tu_chain.hip", "h2r_tu_step.hip", "h2r_tu_cells.hip", "h2r_tu_chain_keyed.hip", "h2r_tu_step_keyed.hip", "h2r_tu_lookup_product.hip", "h2r_tu_permutation_product.hip", "h2r_tu_ntt.hip", "h2r_tu_quotient.hip", "h2r_tu_open.hip", "h2r_tu_msm.hip", "h2r_tu_curve_ntt.hip", "h2r_tu_transcript.hip", "h2r_tu_random.hip", "h2r_tu_verify.hip", "h2r_tu_pairing.hip", "h2r_tu_keygen.hip", "h2r_tu_witness.hip", "h2r_tu_advice.hip", "h2r_tu_lookup.hip"]
+UNITS = ["h2r_api.hip", "h2r_tu_trace.hip", "h2r_tu_chain.hip", "h2r_tu_step.hip", "h2r_tu_cells.hip", "h2r_tu_chain_keyed.hip", "h2r_tu_step_keyed.hip", "h2r_tu_lookup_product.hip", "h2r_tu_permutation_product.hip", "h2r_tu_ntt.hip", "h2r_tu_quotient.hip", "h2r_tu_open.hip", "h2r_tu_msm.hip", "h2r_tu_curve_ntt.hip", "h2r_tu_transcript.hip", "h2r_tu_random.hip", "h2r_tu_verify.hip", "h2r_tu_pairing.hip", "h2r_tu_keygen.hip", "h2r_tu_setup.hip", "h2r_tu_witness.hip", "h2r_tu_advice.hip", "h2r_tu_lookup.hip"]
 ID_UNIT = "h2r_tu_id.cpp"
 LIB = os.path.join(PKG, "lib", "libh2r.so")
 OBJ = os.path.join(PKG, "lib", "obj")

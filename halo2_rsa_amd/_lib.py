@@ -22,6 +22,11 @@ FIELD_DELTA = {"bn254_fr": 0x0ba49465f79ce3ca21f1ec72be9f9a263f544c14cc40ac6ba14
                "bn254_fq": 0x9,
                "pasta_fp": 0x0a757d0f0006ab6cbd455b7112a5049df5e4f3f13eee56366a6ccd20dd7b9ba2,
                "pasta_fq": 0x2237d5442372416606f0a88e7f7949f8e3ac3376541d11408494392472d1683c}
+# (S, g^t) for p - 1 = 2^S * t with t odd and the same g: halo2's root of unity of order 2^S, canonical, for the fields with a curve
+# (prover.setup squares it down to the 2^k domain; tests/test_setup_host.py compares with tests/permutation_ref.py::domain)
+FIELD_ROOT_OF_UNITY = {"bn254_fr": (28, 0x2a3c09f0a58a7e8500e0a7eb8ef62abc402d111e41112ed49bd61b6e725b19f0)}
+# (q, (x, y)): the coordinate field's modulus and the generator of the curve of a field that has one (bn256 G1 over Fq, of order r)
+CURVE_GENERATOR = {"bn254_fr": (21888242871839275222246405745257275088696311157297823662689037894645226208583, (1, 2))}
 H2R_F_SHARED_MODULUS = 1
 H2R_F_KEYED_MODULI = 2   # `n` points to a host H2RKeyedModuli: a per-element index into a key table (h2r_key_table_build)
 
@@ -238,6 +243,11 @@ class H2RPairingConfig(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("num_pairs", ctypes.c_uint32), ("negate_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
+class H2RSetupConfig(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("log_n", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+                ("n", ctypes.c_uint64), ("tau", ctypes.c_uint64 * 4), ("omega", ctypes.c_uint64 * 4)]
+
+
 class H2RKeygenSigmaInfo(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("hook_rounds", ctypes.c_uint32), ("touched_cells", ctypes.c_uint32), ("sort_passes", ctypes.c_uint32)]
 
@@ -298,6 +308,7 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_proof_decode", "h2r_verify_bases", "h2r_verify_scalars", "h2r_msm_terms", "h2r_verify_eval",
            "h2r_pairing_prepare", "h2r_pairing_products", "h2r_pairing_eval",
            "h2r_keygen_fixed_workspace_bytes", "h2r_keygen_fixed_columns", "h2r_keygen_sigma_workspace_bytes", "h2r_keygen_sigma_columns", "h2r_keygen_vk_repr",
+           "h2r_fixed_base_table", "h2r_fixed_base_mul", "h2r_fixed_base_eval", "h2r_kzg_setup_scalars", "h2r_g2_mul", "h2r_g2_generator",
            "h2r_dist_unique_id", "h2r_dist_init", "h2r_dist_destroy", "h2r_dist_rank", "h2r_dist_world", "h2r_dist_version", "h2r_dist_shard_range",
            "h2r_dist_bcast", "h2r_dist_gather_results", "h2r_dist_allreduce_max_f64",
            "h2r_profile_enable", "h2r_profile_read", "h2r_status_str",
@@ -317,7 +328,10 @@ KERNEL_RANDOM = 30
 KERNEL_PROOF_DECODE, KERNEL_VERIFY_SCALARS, KERNEL_MSM_TERMS = 31, 32, 33
 KERNEL_PAIRING = 34
 KERNEL_KEYGEN_FIXED, KERNEL_KEYGEN_COMPONENTS, KERNEL_KEYGEN_COMPACT, KERNEL_KEYGEN_SORT, KERNEL_KEYGEN_WRITE = 35, 36, 37, 38, 39
+KERNEL_FIXED_BASE_TABLE, KERNEL_FIXED_BASE_MUL, KERNEL_SETUP_SCALARS = 40, 41, 42
 H2R_KEYGEN_NUM_FIXED = 15
+H2R_FIXED_BASE_TABLE_BYTES, H2R_FIXED_BASE_MAX_POINTS = 524288, 1 << 24
+H2R_SETUP_POWERS, H2R_SETUP_LAGRANGE = 0, 1
 H2R_PAIRING_STEPS, H2R_PAIRING_TABLE_BYTES, H2R_PAIRING_MAX_PAIRS = 102, 13056, 4
 FIELD_MUL, FIELD_TO_MONTGOMERY, FIELD_FROM_MONTGOMERY = 2, 6, 7   # h2r_field_eval's operations a * b, a * R and a * R^-1 mod p (include/h2r.h)
 H2R_HASHED_MSG_STREAM_BYTES = 288
@@ -568,6 +582,12 @@ def lib():
     L.h2r_keygen_sigma_workspace_bytes.restype = u64
     L.h2r_keygen_sigma_columns.argtypes = [vp, ctypes.POINTER(H2RPermutationConfig), vp, u64, u32, u32, u32, vp, u64, vp, vp, ctypes.POINTER(H2RKeygenSigmaInfo), vp]
     L.h2r_keygen_vk_repr.argtypes = [vp, pvs, u32, ctypes.c_char_p, pu64]
+    L.h2r_fixed_base_table.argtypes = [vp, ctypes.c_char_p, vp, vp]
+    L.h2r_fixed_base_mul.argtypes = [vp, vp, vp, u64, vp, vp]
+    L.h2r_fixed_base_eval.argtypes = [vp, u32, pu64, pu64, pu64]
+    L.h2r_kzg_setup_scalars.argtypes = [vp, ctypes.POINTER(H2RSetupConfig), vp, vp]
+    L.h2r_g2_mul.argtypes = [vp, ctypes.c_char_p, pu64, vp]
+    L.h2r_g2_generator.argtypes = [vp, vp]
     L.h2r_dist_unique_id.argtypes = [vp]
     L.h2r_dist_init.argtypes = [vp, vp, u32, u32, ctypes.POINTER(vp)]
     L.h2r_dist_destroy.argtypes = [vp]

@@ -18,7 +18,7 @@ import torch
 from . import _lib
 from ._lib import H2RLayout, H2RParams, H2RPowLayout, check, lib
 from ._marshal import hold, image_stride, kinds_tensor, ptr, ref
-from .prover import CommitKey, EvaluationDomain, LookupArgument, PermutationArgument, Transcript  # noqa: F401  (re-exported: they lived here once)
+from .prover import CommitKey, EvaluationDomain, LookupArgument, Params, PermutationArgument, Transcript, fixed_base_mul, fixed_base_table, setup, setup_scalars  # noqa: F401  (re-exported: they lived here once)
 
 
 def _e_bytes(e: int) -> bytes:

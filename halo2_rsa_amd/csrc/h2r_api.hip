@@ -35,6 +35,7 @@
 #include "h2r_verify.hpp"
 #include "h2r_pairing.hpp"
 #include "h2r_keygen.hpp"
+#include "h2r_setup.hpp"
 #include "h2r_muled.hpp"
 #include "h2r_rowprog.hpp"
 #include "h2r_sha256.hpp"
@@ -4371,7 +4372,9 @@ static_assert(H2R_KERNEL_OPEN_CARRY == H2R_KERNEL_OPEN_TILES + 1 && H2R_KERNEL_O
               H2R_KERNEL_TRANSCRIPT == H2R_KERNEL_CURVE_NTT_STORE + 1 && H2R_KERNEL_RANDOM == H2R_KERNEL_TRANSCRIPT + 1 && H2R_KERNEL_PROOF_DECODE == H2R_KERNEL_RANDOM + 1 &&
               H2R_KERNEL_VERIFY_SCALARS == H2R_KERNEL_PROOF_DECODE + 1 && H2R_KERNEL_MSM_TERMS == H2R_KERNEL_VERIFY_SCALARS + 1 &&
               H2R_KERNEL_PAIRING == H2R_KERNEL_MSM_TERMS + 1 && H2R_KERNEL_KEYGEN_FIXED == H2R_KERNEL_PAIRING + 1 &&
-              H2R_KERNEL_KEYGEN_WRITE == H2R_KERNEL_KEYGEN_FIXED + 4 && H2R_KERNEL_COUNT == H2R_KERNEL_KEYGEN_WRITE + 1, "h2r.h: the launch classes");
+              H2R_KERNEL_KEYGEN_WRITE == H2R_KERNEL_KEYGEN_FIXED + 4 && H2R_KERNEL_FIXED_BASE_TABLE == H2R_KERNEL_KEYGEN_WRITE + 1 &&
+              H2R_KERNEL_FIXED_BASE_MUL == H2R_KERNEL_FIXED_BASE_TABLE + 1 && H2R_KERNEL_SETUP_SCALARS == H2R_KERNEL_FIXED_BASE_MUL + 1 &&
+              H2R_KERNEL_COUNT == H2R_KERNEL_SETUP_SCALARS + 1, "h2r.h: the launch classes");
 static_assert(H2R_OPEN_MAX_COLUMNS == OPEN_MAX_COLUMNS && H2R_OPEN_MAX_POINTS == OPEN_MAX_POINTS, "h2r.h and the kernels' argument struct");
 // what the host helpers answer 0 for: the configuration and the masks, which need no ctx and no pointer
 int32_t open_cfg_status(const h2r_open_config *cfg, const h2r_open_column *cols) {
@@ -5276,6 +5279,135 @@ int32_t h2r_pairing_eval(const h2r_ctx *ctx, uint32_t op, const uint8_t *in, uin
         for (u32 i = 0; i < in[0]; ++i) t.each(0, [&](u32 k) { return fq12_frob_coeff(t.s, 1, k, c); });
     } else pr_final_exp(t, c);
     put(out);
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// ---- KZG parameters from a known tau: fixed-base multiplication over G1, the scalars tau^i and l_i(tau), [k]Q on the twist (h2r_setup.hpp, h2r_tu_setup.hip) ----
+static_assert(H2R_FIXED_BASE_TABLE_BYTES == FB_TABLE_BYTES && H2R_FIXED_BASE_MAX_POINTS == FB_MAX_POINTS && H2R_SETUP_POWERS == SETUP_POWERS &&
+              H2R_SETUP_LAGRANGE == SETUP_LAGRANGE && sizeof(h2r_setup_config) == 88, "h2r.h and the kernels' constants");
+namespace {
+// an affine point of 8 words in `mont`'s representation -> Montgomery form: H2R_E_SHAPE for a coordinate >= q, H2R_E_ASSERTION off the curve
+int32_t fixed_base_point(const uint64_t *w, bool mont, const CurveConsts &cv, PtAff &p) {
+    const Fe x = fe_words(w), y = fe_words(w + 4);
+    if (ge_p(x.v, cv.fq.p) || ge_p(y.v, cv.fq.p)) return H2R_E_SHAPE;
+    p.x = mont ? x : fe_to_mont(x, cv.fq); p.y = mont ? y : fe_to_mont(y, cv.fq);
+    return pt_aff_on_curve(p, cv) ? H2R_OK : H2R_E_ASSERTION;
+}
+// what needs no ctx and no pointer
+int32_t setup_cfg_status(const h2r_setup_config *cfg) {
+    if (cfg->struct_size != sizeof(h2r_setup_config) || cfg->mode > H2R_SETUP_LAGRANGE) return H2R_E_UNSUPPORTED;
+    if (cfg->reserved) return H2R_E_SHAPE;
+    if (cfg->mode == H2R_SETUP_POWERS) return cfg->log_n == 0 && cfg->n >= 1 && cfg->n <= FB_MAX_POINTS ? H2R_OK : H2R_E_SHAPE;
+    return cfg->n == 0 && cfg->log_n >= 1 && cfg->log_n <= SETUP_MAX_LOG ? H2R_OK : H2R_E_SHAPE;
+}
+}  // namespace
+
+int32_t h2r_fixed_base_table(const h2r_ctx *ctx, const uint8_t *base, void *table, h2r_stream_t stream) try {
+    if (!ctx || !base || !table) return H2R_E_NULL;
+    if (misaligned(table)) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    uint64_t w[8];
+    std::memcpy(w, base, sizeof w);
+    PtAff b;
+    if (const int32_t rc = fixed_base_point(w, ctx_mont(ctx), *cv, b)) return rc;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    FixedBaseTableArgs ta;
+    std::memset(static_cast<void *>(&ta), 0, sizeof ta);
+    fb_window_bases(b, ta.wb, *cv);
+    ta.table = static_cast<u8 *>(table); ta.cv = *cv;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return for_each_slice(FB_WINDOWS, slice_items(1, FB_WINDOWS), [&](u64 b0, u64 nb) {
+        ta.block0 = (u32)b0;
+        return stage_launch(H2R_KERNEL_FIXED_BASE_TABLE, st, [&](hipEvent_t a, hipEvent_t e) { return launch_fixed_base_table(ta, (u32)nb, st, a, e); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_fixed_base_mul(const h2r_ctx *ctx, const void *table, const void *scalars, uint64_t n, void *out, h2r_stream_t stream) try {
+    if (!ctx || !table || !scalars || !out) return H2R_E_NULL;
+    if (n == 0 || n > FB_MAX_POINTS) return H2R_E_SHAPE;
+    if (misaligned(table) || misaligned(scalars) || misaligned(out)) return H2R_E_SHAPE;
+    // a lane stores its point while other lanes still read their scalars and the table
+    if (overlaps(out, (u128)64 * n, scalars, (u128)32 * n) || overlaps(out, (u128)64 * n, table, (u128)FB_TABLE_BYTES)) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    FixedBaseMulArgs ma;
+    std::memset(static_cast<void *>(&ma), 0, sizeof ma);
+    ma.table = static_cast<const u8 *>(table); ma.scalars = static_cast<const u8 *>(scalars); ma.out = static_cast<u8 *>(out);
+    ma.n = (u32)n; ma.mont = ctx_mont(ctx); ma.fr = ctx->fc; ma.cv = *cv;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const u64 blocks = (n + kBlockThreads - 1) / kBlockThreads;
+    return for_each_slice(blocks, slice_items(1, blocks), [&](u64 b0, u64 nb) {
+        ma.block0 = (u32)b0;
+        return stage_launch(H2R_KERNEL_FIXED_BASE_MUL, st, [&](hipEvent_t a, hipEvent_t e) { return launch_fixed_base_mul(ma, (u32)nb, st, a, e); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_fixed_base_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *base, const uint64_t *arg, uint64_t *out) try {
+    if (!ctx || !base || !arg || !out) return H2R_E_NULL;
+    if (op > 1 || (op == 0 && (arg[0] >= FB_WINDOWS || arg[1] >= FB_DIGITS))) return H2R_E_SHAPE;
+    const CurveConsts *cv = curve_of_field(ctx->params.field);
+    if (!cv) return H2R_E_UNSUPPORTED;
+    PtAff b;
+    if (const int32_t rc = fixed_base_point(base, false, *cv, b)) return rc;
+    PtAff wb[FB_WINDOWS];
+    fb_window_bases(b, wb, *cv);
+    PtAff r;
+    if (op == 0) r = fb_table_entry(wb[arg[0]], (u32)arg[1], *cv);
+    else r = pt_to_affine(fb_walk(fe_words(arg), [&](u32 w, u32 d) { return fb_table_entry(wb[w], d, *cv); }, *cv), *cv);
+    const Fe x = fe_from_mont(r.x, cv->fq), y = fe_from_mont(r.y, cv->fq);
+    for (int k = 0; k < 4; ++k) { out[k] = x.v[k]; out[4 + k] = y.v[k]; }
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_kzg_setup_scalars(const h2r_ctx *ctx, const h2r_setup_config *cfg, void *out, h2r_stream_t stream) try {
+    if (!ctx || !cfg || !out) return H2R_E_NULL;
+    if (const int32_t rc = setup_cfg_status(cfg)) return rc;
+    const FieldConsts &f = ctx->fc;
+    if (ge_p(cfg->tau, f.p) || ge_p(cfg->omega, f.p)) return H2R_E_SHAPE;
+    const bool lagrange = cfg->mode == H2R_SETUP_LAGRANGE;
+    const u64 n = lagrange ? 1ull << cfg->log_n : cfg->n;
+    const Fe tau = cfg_to_mont(ctx, cfg->tau), omega = cfg_to_mont(ctx, cfg->omega), one = fe_one(f);   // Montgomery form from here on
+    SetupScalarsArgs sa;
+    std::memset(static_cast<void *>(&sa), 0, sizeof sa);
+    if (lagrange) {
+        if (!is_primitive_root(omega, cfg->log_n, f)) return H2R_E_SHAPE;
+        const Fe tn = fe_pow2k(tau, cfg->log_n, f);
+        if (fe_eq(tn, one)) return H2R_E_SHAPE;               // tau lies in the domain: l_i(tau) is 0 / 0 by this formula
+        const Fe ninv = fe_to_mont(fe_inv(fe_small(n), f), f);
+        sa.tau = tau; sa.c = fe_mont_mul(fe_sub(tn, one, f.p), ninv, f);
+    }
+    if (misaligned(out)) return H2R_E_SHAPE;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    fe_squaring_chain(sa.pw, SETUP_MAX_LOG, lagrange ? omega : tau, f);
+    sa.out = static_cast<u8 *>(out); sa.n = (u32)n; sa.mode = cfg->mode; sa.mont = ctx_mont(ctx); sa.fr = f;
+    H2R_ON_DEVICE(ctx->params.device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const u64 blocks = (n + kBlockThreads - 1) / kBlockThreads;
+    return for_each_slice(blocks, slice_items(1, blocks), [&](u64 b0, u64 nb) {
+        sa.block0 = (u32)b0;
+        return stage_launch(H2R_KERNEL_SETUP_SCALARS, st, [&](hipEvent_t a, hipEvent_t e) { return launch_setup_scalars(sa, (u32)nb, st, a, e); });
+    });
+} H2R_CATCH_STATUS
+
+int32_t h2r_g2_mul(const h2r_ctx *ctx, const uint8_t *g2, const uint64_t *k, uint8_t *out) try {
+    if (!ctx || !g2 || !k || !out) return H2R_E_NULL;
+    const PairingConsts *pc = pairing_consts_of(ctx->params.field, ctx_mont(ctx));
+    if (!pc) return H2R_E_UNSUPPORTED;
+    G2Aff q;
+    if (const u32 bad = g2_load(g2, &q, *pc)) return (int32_t)bad;
+    g2_store(out, g2_mul(q, k, pc->fq), *pc);
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+int32_t h2r_g2_generator(const h2r_ctx *ctx, uint8_t *out) try {
+    if (!ctx || !out) return H2R_E_NULL;
+    const PairingConsts *pc = pairing_consts_of(ctx->params.field, ctx_mont(ctx));
+    if (!pc) return H2R_E_UNSUPPORTED;
+    g2_generator(out, *pc);
     return H2R_OK;
 } H2R_CATCH_STATUS
 

@@ -19,6 +19,7 @@
 //   h2r_tu_verify.hip  the verifier up to the pairing: proof decoder, the accumulators' scalars, the sum of terms over per-circuit bases (h2r_verify.hpp)
 //   h2r_tu_pairing.hip the verifier's verdict: Miller values and final exponentiations of pairing products against prepared G2 tables (h2r_pairing.hpp)
 //   h2r_tu_keygen.hip  key generation: the fixed columns of an image's row kinds, the sigma columns of its copy pairs (h2r_keygen.hpp)
+//   h2r_tu_setup.hip   KZG parameters from a known tau: the fixed-base table and multiplication over G1, the scalars tau^i and l_i(tau) (h2r_setup.hpp)
 //   h2r_tu_witness.hip   the witness kernels outside the mul_mod records: assert_in_field / encoded message (aux), the Fresh ops, SHA-256, the
 //                      in-place audit (check, link), range decompose, key expand, mul / refresh / is_equal_muled (h2r_muled.hpp), and the
 //                      arena's fill / restore kernels and the queue probe
@@ -180,6 +181,14 @@ struct KeygenFixedArgs;
 struct KeygenSigmaArgs;
 hipError_t launch_keygen_fixed(const KeygenFixedArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 hipError_t launch_keygen_sigma(u32 phase, const KeygenSigmaArgs &a, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+// h2r_tu_setup.hip (argument structs: h2r_setup.hpp).  The table: the windows [a.block0, a.block0 + num_blocks), one workgroup each.  The
+// multiplication and the scalars: the workgroups [a.block0, a.block0 + num_blocks) of 256 scalars.
+struct FixedBaseTableArgs;
+struct FixedBaseMulArgs;
+struct SetupScalarsArgs;
+hipError_t launch_fixed_base_table(const FixedBaseTableArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_fixed_base_mul(const FixedBaseMulArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
+hipError_t launch_setup_scalars(const SetupScalarsArgs &a, u32 num_blocks, hipStream_t st, hipEvent_t ea, hipEvent_t eb);
 // h2r_tu_witness.hip (argument structs: h2r_kernels.hpp, h2r_muled.hpp).  w = the limb width (64 | 32).  The aux kernel is the keyed build when
 // aa.key_idx is set; `lds` / `stage` = the dynamic LDS request.
 struct RefreshArgs;

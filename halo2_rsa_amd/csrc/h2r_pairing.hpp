@@ -35,6 +35,11 @@ constexpr uint32_t PR_TEAM = 8, PR_LANES = 64, PR_TEAMS = PR_LANES / PR_TEAM;   
 constexpr uint32_t PR_TEAM_FQ2 = PR_SLOTS * 6 + PR_MAX_PAIRS;                     // a team's store: the slots, then the G1 operands (x, y) of its circuit
 constexpr uint64_t PR_U = 4965661367192848881ull;         // bn256's u: q = 36 u^4 + 36 u^3 + 24 u^2 + 6 u + 1 (63 bits, 28 set)
 constexpr uint64_t PR_LOOP_LO = 11347224129447541672ull;  // 6 u + 2 = 2^64 + this: the 64 bits below the top bit (36 set)
+// the generator of G2 (EIP-197's; tests/pairing_ref.G2): x.re, x.im, y.re, y.im as canonical integers, four little-endian words each
+constexpr uint64_t PR_G2_GENERATOR[4][4] = {{0x46debd5cd992f6edull, 0x674322d4f75edaddull, 0x426a00665e5c4479ull, 0x1800deef121f1e76ull},
+                                            {0x97e485b7aef312c2ull, 0xf1aa493335a9e712ull, 0x7260bfb731fb5d25ull, 0x198e9393920d483aull},
+                                            {0x4ce6cc0166fa7daaull, 0xe3d1e7690c43d37bull, 0x4aab71808dcb408full, 0x12c85ea5db8c6debull},
+                                            {0x55acdadcd122975bull, 0xbc4b313370b38ef3ull, 0xec9e99ad690c3395ull, 0x090689d0585ff075ull}};
 
 struct Fq2 { Fe re, im; };
 

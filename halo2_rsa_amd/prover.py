@@ -1,5 +1,5 @@
 """The prover stages on the device: halo2's lookup and permutation arguments, the evaluation domain (transforms, quotient, openings) and
-the commitment key, the Fiat-Shamir transcript that joins them, the generator of the blinding values, create_proof, which runs them in halo2's order, and verify_proof, the verifier up to the pairing.  None of them has a counterpart in the reference's `big_integer`
+the commitment key, the Fiat-Shamir transcript that joins them, the generator of the blinding values, create_proof, which runs them in halo2's order, verify_proof and verify, the verifier to its verdict, keygen, and setup, the KZG parameters of a known tau.  None of them has a counterpart in the reference's `big_integer`
 module; `big_integer` re-exports the five classes.
 All arithmetic happens in libh2r.so; every method marshals its arguments with `_marshal` and makes the call.
 A chip is whatever has `_ctx`, `_stream()`, `device` and `montgomery` (big_integer.BigIntChip)."""
@@ -1097,3 +1097,152 @@ def verify(vk: VerifyingKey, pkey: PairingKey, proofs: torch.Tensor, instances: 
     left, right, _ = verify_proof(vk, proofs, instances, out=acc)
     pairing_check(pkey, torch.stack((left, right), dim=1), 0b10, status, out=(accept, None))
     return accept, status
+
+
+# ---- KZG parameters from a known tau ---------------------------------------------------------------------------------
+TAG_SETUP = 7 * 256                        # the generator's tag of setup's tau: kind 7, circuit 0, row 0
+
+
+def _field(chip, op: int, a: int, b: int = 0) -> int:
+    wa, wb, out = ((ctypes.c_uint64 * 4)(*words(v)) for v in (a, b, 0))
+    check(lib().h2r_field_eval(chip._ctx, op, wa, wb, out), "h2r_field_eval")
+    return from_words(out)
+
+
+def field_omega(chip, k: int) -> int:
+    """halo2's primitive 2^k-th root of unity of the chip's field (_lib.FIELD_ROOT_OF_UNITY squared down), in the chip's representation."""
+    if chip.field not in _lib.FIELD_ROOT_OF_UNITY or not 0 < k <= _lib.FIELD_ROOT_OF_UNITY[chip.field][0]:
+        check(_lib.H2R_E_SHAPE, "field_omega")
+    s, w = _lib.FIELD_ROOT_OF_UNITY[chip.field]
+    for _ in range(s - k):
+        w = _field(chip, _lib.FIELD_MUL, w, w)
+    return _field(chip, _lib.FIELD_TO_MONTGOMERY, w) if chip.montgomery else w
+
+
+def curve_generator(chip) -> bytes:
+    """The generator of the curve of the chip's field as a base: 64 bytes, x then y in the chip's representation."""
+    if chip.field not in _lib.CURVE_GENERATOR:
+        check(_lib.H2R_E_UNSUPPORTED, "curve_generator")
+    q, xy = _lib.CURVE_GENERATOR[chip.field]
+    return b"".join(((v << 256) % q if chip.montgomery else v).to_bytes(32, "little") for v in xy)
+
+
+def fixed_base_table(chip, base: Optional[bytes] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [H2R_FIXED_BASE_TABLE_BYTES] on the device: T[w][d] = [d 256^w]B (h2r_fixed_base_table).  base: 64 host
+    bytes, an affine point in the chip's representation ((0, 0): a table of identities); None: the curve's generator."""
+    base = curve_generator(chip) if base is None else bytes(base)
+    if len(base) != 64:
+        check(_lib.H2R_E_SHAPE, "fixed_base_table")
+    out = outputs(out, "cuda:%d" % chip.device, (torch.empty, torch.uint8, (_lib.H2R_FIXED_BASE_TABLE_BYTES,)))
+    assert out.is_contiguous() and out.is_cuda and out.dtype == torch.uint8 and out.numel() == _lib.H2R_FIXED_BASE_TABLE_BYTES
+    check(lib().h2r_fixed_base_table(chip._ctx, base, out.data_ptr(), chip._stream()), "h2r_fixed_base_table")
+    return out
+
+
+def fixed_base_mul(chip, table: torch.Tensor, scalars: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [n, 64]: out[i] = [scalars[i]]B for the base of `table` (h2r_fixed_base_mul): affine points in the chip's representation,
+    (0, 0) the identity.  scalars: uint8 [n, 32] on the device, the chip's representation; out: the tensor to write into (it must overlap
+    neither the scalars nor the table).  Never synchronises."""
+    if not isinstance(scalars, torch.Tensor) or not scalars.is_cuda or not is_columns(scalars, dims=(2,), strides=False) or scalars.shape[0] == 0:
+        check(_lib.H2R_E_SHAPE, "fixed_base_mul")
+    assert is_columns(scalars) and table.is_cuda and table.is_contiguous() and table.numel() * table.element_size() == _lib.H2R_FIXED_BASE_TABLE_BYTES
+    n = int(scalars.shape[0])
+    out = outputs(out, scalars.device, (torch.empty, torch.uint8, (n, 64)))
+    assert out.is_contiguous() and out.is_cuda and out.numel() * out.element_size() == 64 * n
+    check(lib().h2r_fixed_base_mul(chip._ctx, table.data_ptr(), scalars.data_ptr(), n, out.data_ptr(), chip._stream()), "h2r_fixed_base_mul")
+    hold(chip, "fixed_base_mul", table, scalars, out)
+    return out
+
+
+def setup_scalars(chip, mode: int, size: int, tau: int, omega: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [n, 32] on the device, the chip's representation (h2r_kzg_setup_scalars).  mode _lib.H2R_SETUP_POWERS: size = n, out[i] =
+    tau^i; _lib.H2R_SETUP_LAGRANGE: size = k, n = 2^k, out[i] = l_i(tau) over the domain of omega (refused for a tau inside the domain).
+    tau, omega: integers in the chip's representation."""
+    lagrange, size = mode == _lib.H2R_SETUP_LAGRANGE, int(size)
+    if mode not in (_lib.H2R_SETUP_POWERS, _lib.H2R_SETUP_LAGRANGE) or not 1 <= size <= (24 if lagrange else _lib.H2R_FIXED_BASE_MAX_POINTS):
+        check(_lib.H2R_E_SHAPE, "setup_scalars")
+    cfg =_lib.H2RSetupConfig(struct_size=ctypes.sizeof(_lib.H2RSetupConfig), mode=mode, log_n=size if lagrange else 0, reserved=0, n=0 if lagrange else size)
+    set_words(cfg.tau, tau)
+    set_words(cfg.omega, omega)
+    n = (1 << size) if lagrange else size
+    out = outputs(out, "cuda:%d" % chip.device, (torch.empty, torch.uint8, (n, 32)))
+    assert out.is_contiguous() and out.is_cuda and out.numel() * out.element_size() == 32 * n
+    check(lib().h2r_kzg_setup_scalars(chip._ctx, ctypes.byref(cfg), out.data_ptr(), chip._stream()), "h2r_kzg_setup_scalars")
+    return out
+
+
+def g2_generator(chip) -> bytes:
+    """The generator of G2, 128 bytes in the chip's representation (h2r_g2_generator)."""
+    out = (ctypes.c_uint8 * 128)()
+    check(lib().h2r_g2_generator(chip._ctx, out), "h2r_g2_generator")
+    return bytes(out)
+
+
+def g2_mul(chip, g2: bytes, k: int) -> bytes:
+    """[k]Q on the twist, on the host (h2r_g2_mul): g2 and the result are 128 bytes in the chip's representation, zeros the identity; k any
+    integer below 2^256."""
+    out = (ctypes.c_uint8 * 128)()
+    check(lib().h2r_g2_mul(chip._ctx, bytes(g2), (ctypes.c_uint64 * 4)(*words(k)), out), "h2r_g2_mul")
+    return bytes(out)
+
+
+class Params:
+    """halo2's ParamsKZG of a KNOWN tau (setup() below): k, n = 2^k, g = CommitKey over [tau^i]G, g_lagrange = CommitKey over [l_i(tau)]G,
+    g2 and s_g2 = [tau]G2 as 128 host bytes.  keygen / ProvingKey take commit_key=params.g, lagrange_key=params.g_lagrange; verify takes
+    params.pairing_key()."""
+
+    def __init__(self, chip, k: int, omega: int, g: CommitKey, g_lagrange: CommitKey, g2: bytes, s_g2: bytes):
+        self.chip, self.k, self.n, self.omega, self.g, self.g_lagrange, self.g2, self.s_g2 = chip, int(k), 1 << int(k), int(omega), g, g_lagrange, g2, s_g2
+
+    def pairing_key(self) -> "PairingKey":
+        """PairingKey(chip, [s_g2, g2]): what verify checks e(left, [tau]G2) e(-right, G2) = 1 against."""
+        return PairingKey(self.chip, [self.s_g2, self.g2])
+
+    def downsize(self, k2: int) -> "Params":
+        """The parameters of the smaller domain 2^k2: the first 2^k2 points of g, g_lagrange by the curve transform over them
+        (EvaluationDomain.lagrange_key) -- the powers of tau nest, the Lagrange basis does not."""
+        if not 0 < k2 <= self.k:
+            check(_lib.H2R_E_SHAPE, "Params.downsize")
+        w = _field(self.chip, _lib.FIELD_FROM_MONTGOMERY, self.omega) if self.chip.montgomery else self.omega
+        for _ in range(self.k - k2):
+            w = _field(self.chip, _lib.FIELD_MUL, w, w)
+        w = _field(self.chip, _lib.FIELD_TO_MONTGOMERY, w) if self.chip.montgomery else w
+        g = CommitKey(self.chip, self.g.bases[:1 << k2])
+        one = _field(self.chip, _lib.FIELD_TO_MONTGOMERY, 1) if self.chip.montgomery else 1
+        return Params(self.chip, k2, w, g, EvaluationDomain(self.chip, k2, k2, w, one).lagrange_key(g), self.g2, self.s_g2)
+
+
+def setup(chip, k: int, tau: Optional[int] = None, seed: Optional[bytes] = None, omega: Optional[int] = None) -> Params:
+    """halo2's ParamsKZG::setup(k, rng) on the device (DESIGN.md section 2q): one fixed-base table of G, then the powers tau^i and the
+    Lagrange values l_i(tau), each through h2r_fixed_base_mul, and [tau]G2 on the host.  No point array is copied to or from the host and
+    nothing synchronises.
+    A KNOWN TAU IS TOXIC WASTE: whoever holds it can open any commitment to any value.  This is for tests, benches and development keys, as
+    the reference's setup is.  tau is not kept: the two scalar columns are zeroed on the stream once the multiplications have read them and
+    the result references neither them nor the table; tau was in this process's host memory all the same.
+    tau: an integer in the chip's representation; None: the generator's element (seed, circuit 0, TAG_SETUP, row 0) (h2r_random_eval),
+    seed 32 bytes, os.urandom(32) when None.  A tau inside the domain (tau^n = 1) is refused (H2R_E_SHAPE).  omega: the primitive 2^k-th
+    root of unity of the Lagrange basis (an EvaluationDomain's `omega`), in the chip's representation; None: field_omega(chip, k)."""
+    k = int(k)
+    if not 0 < k <= 24:
+        check(_lib.H2R_E_SHAPE, "setup")
+    if tau is None:
+        seed = os.urandom(32) if seed is None else bytes(seed)
+        if len(seed) != 32:
+            check(_lib.H2R_E_SHAPE, "setup")
+        out = (ctypes.c_uint64 * 4)()
+        check(lib().h2r_random_eval(chip._ctx, seed, 0, TAG_SETUP, 0, out), "h2r_random_eval")
+        tau = from_words(out)
+    omega = field_omega(chip, k) if omega is None else int(omega)
+    n = 1 << k
+    lag = setup_scalars(chip, _lib.H2R_SETUP_LAGRANGE, k, tau, omega)     # (first: it refuses a tau inside the domain before anything is built)
+    table = fixed_base_table(chip)
+    pw = setup_scalars(chip, _lib.H2R_SETUP_POWERS, n, tau)
+    g = CommitKey(chip, fixed_base_mul(chip, table, pw))
+    g_lagrange = CommitKey(chip, fixed_base_mul(chip, table, lag))
+    g2 = g2_generator(chip)
+    s_g2 = g2_mul(chip, g2, _field(chip, _lib.FIELD_FROM_MONTGOMERY, tau) if chip.montgomery else tau)
+    # the scalar columns are the toxic waste on the device (pw[1] is tau): cleared in stream order behind the multiplications that read
+    # them, then released -- the launches run on torch's current stream, whose allocator reuses a block only behind them
+    pw.zero_()
+    lag.zero_()
+    return Params(chip, k, omega, g, g_lagrange, g2, s_g2)

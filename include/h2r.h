@@ -1384,6 +1384,52 @@ int32_t h2r_keygen_sigma_columns(const h2r_ctx *ctx, const h2r_permutation_confi
                                  uint32_t first_row, uint32_t log_n, uint32_t usable_rows, void *sigma_out, uint64_t col_stride, uint8_t *status,
                                  void *workspace, h2r_keygen_sigma_info *info, h2r_stream_t stream);
 int32_t h2r_keygen_vk_repr(const h2r_ctx *ctx, const h2r_verify_scalars_config *cfg, uint32_t extended_k, const uint8_t *points, uint64_t out[4]);
+/* ---- KZG parameters from a KNOWN tau: fixed-base multiplication over G1, the scalars of setup, [k]Q on the twist ------------
+ * DESIGN.md section 2q.  halo2's ParamsKZG::setup(k, rng) restated: g[i] = [tau^i]G, g_lagrange[i] = [l_i(tau)]G, s_g2 = [tau]G2.  A KNOWN
+ * TAU IS TOXIC WASTE: whoever holds it forges openings.  These calls are for tests, benches and development keys, as the reference's own
+ * setup is; production keys come from a ceremony.  Held to the Python models (tests/setup_ref.py, msm_ref.py, pairing_ref.py); byte
+ * parity with upstream's ParamsKZG is not claimed.  Only a ctx whose field has a curve (h2r_kzg_setup_scalars: any field).
+ * h2r_fixed_base_table: table (device, H2R_FIXED_BASE_TABLE_BYTES) = T[w][d] = [d 256^w]B for w < 32, d < 256, entry (w, d) at
+ *    (256 w + d) * 64: affine x then y in the MONTGOMERY form of Fq whatever the ctx's representation is (the form the multiplication
+ *    adds without converting), (0, 0) for d = 0.  base: the affine point B on the HOST, 64 bytes in the ctx's representation, section 2i's
+ *    encoding; (0, 0) is legal and gives a table of identities.  The host forms the 32 window bases [256^w]B, which travel in the kernel
+ *    arguments; one launch, one lane per (w, d).  The table is a function of (field, B) alone.  Never synchronises.
+ *    H2R_E_NULL; H2R_E_SHAPE for a table pointer off 16 bytes; H2R_E_UNSUPPORTED for a field without a curve; H2R_E_SHAPE for a coordinate
+ *    >= q, H2R_E_ASSERTION for a point off the curve; H2R_E_UNSUPPORTED for a host-only ctx (after every other check).
+ * h2r_fixed_base_mul: out[i] = [s_i]B for the n scalars of a device column (32 bytes each, the ctx's representation; scalar semantics as
+ *    h2r_msm_columns': the 32 windows cover all 256 bits, so a canonical value >= r multiplies like its residue; a Montgomery ctx converts
+ *    once per scalar).  out: n affine points of 64 bytes in the ctx's representation, canonical representatives, (0, 0) the identity: the
+ *    bytes do not depend on the order of operations.  One lane per scalar: at most 32 mixed additions of gathered entries, one
+ *    inversion; Z = 0 never reaches it.  No workgroup waits for another, no atomics, no status, never synchronises, every loop has a fixed
+ *    trip count: a table of garbage gives unspecified bytes, never a fault.  In this order: H2R_E_NULL; H2R_E_SHAPE for n = 0 or >
+ *    H2R_FIXED_BASE_MAX_POINTS, a pointer off 16 bytes, out overlapping the scalars or the table; H2R_E_UNSUPPORTED for a field without
+ *    a curve, then for a host-only ctx.
+ * h2r_fixed_base_eval (host only; works on a host-only ctx) runs the very functions the kernels inline, canonical operands and results
+ *    like h2r_curve_eval: base = affine x[4] | y[4]; op 0: arg = {w, d} (two words), out[8] = table entry (w, d); op 1: arg = k[4], any
+ *    256-bit integer, out[8] = [k]B by the kernel's walk over the bytes of k.  H2R_E_SHAPE for another op, w >= 32, d >= 256, a coordinate
+ *    >= q; H2R_E_ASSERTION off the curve.
+ * h2r_kzg_setup_scalars: out (device, n x 32 bytes, the ctx's representation), one lane per element, never synchronises.
+ *    mode H2R_SETUP_POWERS: out[i] = tau^i for i < cfg->n, 1 <= n <= 2^24 (log_n must be 0; omega is not read beyond its range check);
+ *    tau = 0 gives 1, 0, 0, ...  mode H2R_SETUP_LAGRANGE: n = 2^log_n, 1 <= log_n <= 24 (cfg->n must be 0), out[i] = l_i(tau) =
+ *    omega^i (tau^n - 1) / (n (tau - omega^i)); omega as in h2r_curve_ntt (a primitive n-th root, checked as omega^(n/2) = -1).  tau and
+ *    omega are integers in the ctx's representation.  H2R_E_UNSUPPORTED for another struct_size or mode; H2R_E_SHAPE for a nonzero
+ *    `reserved`, n or log_n out of range, tau or omega >= r, omega not primitive, tau^n = 1 (tau lies in the domain, the formula divides
+ *    by zero there), out off 16 bytes; H2R_E_UNSUPPORTED for a host-only ctx last.
+ * h2r_g2_mul (host only; works on a host-only ctx): out = [k]Q on the twist of section 2o, in its encoding (128 bytes, the ctx's
+ *    representation); k[4] any 256-bit integer; the identity is 128 zero bytes, legal as an input.  H2R_E_SHAPE for a coordinate >= q,
+ *    H2R_E_ASSERTION for a point off E'.  h2r_g2_generator writes the generator (EIP-197's) in the same encoding.  G2 arithmetic stays
+ *    off the device. */
+#define H2R_FIXED_BASE_TABLE_BYTES 524288u
+#define H2R_FIXED_BASE_MAX_POINTS  (1u << 24)
+#define H2R_SETUP_POWERS   0u
+#define H2R_SETUP_LAGRANGE 1u
+typedef struct h2r_setup_config { uint32_t struct_size, mode, log_n, reserved; uint64_t n; uint64_t tau[4], omega[4]; } h2r_setup_config;
+int32_t h2r_fixed_base_table(const h2r_ctx *ctx, const uint8_t *base, void *table, h2r_stream_t stream);
+int32_t h2r_fixed_base_mul(const h2r_ctx *ctx, const void *table, const void *scalars, uint64_t n, void *out, h2r_stream_t stream);
+int32_t h2r_fixed_base_eval(const h2r_ctx *ctx, uint32_t op, const uint64_t *base, const uint64_t *arg, uint64_t *out);
+int32_t h2r_kzg_setup_scalars(const h2r_ctx *ctx, const h2r_setup_config *cfg, void *out, h2r_stream_t stream);
+int32_t h2r_g2_mul(const h2r_ctx *ctx, const uint8_t *g2, const uint64_t *k, uint8_t *out);
+int32_t h2r_g2_generator(const h2r_ctx *ctx, uint8_t *out);
 /* Arithmetic of the ctx's field on canonical elements (host): op 0 = a + b, 1 = a - b, 2 = a * b, 3 = a^-1 (b ignored; a != 0;
  * binary extended Euclid), 4 = a^(p-2) (Fermat: the cross-check of 3), 5 = a^-1 as the kernels compute main_gate.is_zero's witness
  * (classical Euclid on (p, s) when a = +-s with s < 2^64 -- the only differences this path produces --, op 3 otherwise),
@@ -1695,7 +1741,9 @@ enum { H2R_KERNEL_CHAIN = 0, H2R_KERNEL_TRACE = 1, H2R_KERNEL_HIST = 2, H2R_KERN
        H2R_KERNEL_KEYGEN_COMPACT = 37 /* its count, tile scan and compact kernels */,
        H2R_KERNEL_KEYGEN_SORT = 38 /* per radix pass: histogram, scan, scatter */,
        H2R_KERNEL_KEYGEN_WRITE = 39 /* the identity labels and the successors' scatter */,
-       H2R_KERNEL_COUNT = 40 };
+       H2R_KERNEL_FIXED_BASE_TABLE = 40 /* fixed_base_table_kernel */, H2R_KERNEL_FIXED_BASE_MUL = 41 /* fixed_base_mul_kernel */,
+       H2R_KERNEL_SETUP_SCALARS = 42 /* setup_scalars_kernel */,
+       H2R_KERNEL_COUNT = 43 };
 int32_t h2r_profile_enable(uint32_t capacity);
 int32_t h2r_profile_read(uint32_t kernel, float *ms_out, uint32_t max_count, uint32_t *count);
 
