@@ -289,7 +289,8 @@ EXPORTS = ["h2r_ctx_create", "h2r_ctx_create_ex", "h2r_ctx_advice_repr", "h2r_ab
            "h2r_pow_trace_flatten_ex", "h2r_trace_emit_stream", "h2r_pow_trace_emit_stream", "h2r_mul_mod_trace_check", "h2r_pow_trace_check",
            "h2r_modpow_public_key_advice_rows", "h2r_modpow_public_key_emit_advice",
            "h2r_advice_copy_map", "h2r_pow_operand_sources", "h2r_advice_layout_default", "h2r_advice_layout_custom", "h2r_advice_fixed_row_ex",
-           "h2r_advice_apply_layout", "h2r_advice_check", "h2r_pow_copy_map", "h2r_lookup_hist_advice",
+           "h2r_advice_apply_layout", "h2r_advice_check", "h2r_pow_copy_map", "h2r_fresh_op_copy_map", "h2r_verify_circuit_rows", "h2r_verify_circuit_row_kinds",
+           "h2r_verify_circuit_emit_frame", "h2r_verify_circuit_copy_map", "h2r_lookup_hist_advice",
            "h2r_advice_rows", "h2r_mul_mod_emit_advice", "h2r_pow_trace_emit_advice", "h2r_pow_advice_rows", "h2r_pow_row_kinds", "h2r_advice_row_kinds",
            "h2r_advice_fixed_row", "h2r_fresh_op_advice_rows", "h2r_fresh_op_row_kinds", "h2r_fresh_op_emit_advice",
            "h2r_verify_advice_rows", "h2r_verify_row_kinds", "h2r_verify_emit_advice", "h2r_verify_layout_compact", "h2r_pipeline_verify_pkcs1v15_advice", "h2r_pow_layout_compact", "h2r_pipeline_modpow_public_key_var_advice", "h2r_pipeline_verify_pkcs1v15_var_advice", "h2r_verify_layout_var", "h2r_verify_pkcs1v15_var_batch", "h2r_pipeline_verify_pkcs1v15_var",
@@ -502,6 +503,14 @@ def lib():
     L.h2r_advice_check.argtypes = [vp, vp, vp, vp, u64, vp, u64, u64, vp, vp, u64, vp, vp, vp, u32, vp, vp, vp]
     L.h2r_pow_copy_map.argtypes = [vp, ctypes.POINTER(H2RPowLayout), ctypes.c_char_p, ctypes.c_size_t, u64, vp, u64]
     L.h2r_pow_copy_map.restype = u64
+    L.h2r_fresh_op_copy_map.argtypes = [vp, u32, u32, u64, vp, u64]
+    L.h2r_fresh_op_copy_map.restype = u64
+    L.h2r_verify_circuit_rows.argtypes = [vp, ctypes.POINTER(H2RVerifyLayout), vp]
+    L.h2r_verify_circuit_rows.restype = u64
+    L.h2r_verify_circuit_row_kinds.argtypes = [vp, ctypes.POINTER(H2RVerifyLayout), vp]
+    L.h2r_verify_circuit_emit_frame.argtypes = [vp, ctypes.POINTER(H2RVerifyLayout), vp, vp, vp, vp, u32, u64, vp, vp, u64, vp]
+    L.h2r_verify_circuit_copy_map.argtypes = [vp, ctypes.POINTER(H2RVerifyLayout), ctypes.c_char_p, ctypes.c_size_t, vp, u64]
+    L.h2r_verify_circuit_copy_map.restype = u64
     L.h2r_modpow_public_key_advice_rows.argtypes = [vp, ctypes.POINTER(H2RPowLayout), vp]
     L.h2r_modpow_public_key_advice_rows.restype = u64
     L.h2r_modpow_public_key_emit_advice.argtypes = [vp, ctypes.POINTER(H2RPowLayout), vp, vp, u32, vp, vp, vp, u64, vp, vp, u64, vp]

@@ -432,6 +432,41 @@ class BigIntChip:
         assert int(lib().h2r_pow_copy_map(self._ctx, ctypes.byref(pl), eb, len(eb), row_offset, arr, n)) == n
         return arr
 
+    @staticmethod
+    def _copy_pairs(call, what: str):
+        """cap = 0 asks for the count; 0 pairs = the export refused the shape."""
+        n = int(call(None, 0))
+        if n == 0:
+            check(_lib.H2R_E_UNSUPPORTED, what)
+        arr = (_lib.H2RCopy * n)()
+        assert int(call(arr, n)) == n
+        return arr
+
+    def fresh_op_copy_map(self, op: int, assert_one: bool = False, row_offset: int = 0):
+        """h2r_fresh_op_copy_map: the copy pairs of one Fresh-integer op's rows (operands: H2R_COPY_SRC_A / _B / _N) as H2RCopy."""
+        flags = _lib.H2R_ADVICE_ASSERT_ONE if assert_one else 0
+        return self._copy_pairs(lambda out, cap: lib().h2r_fresh_op_copy_map(self._ctx, op, flags, row_offset, out, cap), "h2r_fresh_op_copy_map")
+
+    def verify_circuit_rows(self, vl):
+        """h2r_verify_circuit_rows: (rows, [P, E, 1]) of the closed verify_pkcs1v15_signature circuit of a Fix layout."""
+        sec = (ctypes.c_uint64 * 3)()
+        rows = int(lib().h2r_verify_circuit_rows(self._ctx, ctypes.byref(vl), sec))
+        if rows == 0:
+            check(_lib.H2R_E_UNSUPPORTED, "h2r_verify_circuit_rows")
+        return rows, [int(v) for v in sec]
+
+    def verify_circuit_row_kinds(self, vl) -> np.ndarray:
+        """h2r_verify_circuit_row_kinds: uint8 kinds of the circuit's rows (frame prefix, element, assert_one)."""
+        kinds = np.zeros(self.verify_circuit_rows(vl)[0], dtype=np.uint8)
+        check(lib().h2r_verify_circuit_row_kinds(self._ctx, ctypes.byref(vl), kinds.ctypes.data), "h2r_verify_circuit_row_kinds")
+        return kinds
+
+    def verify_circuit_copy_map(self, vl, e: int):
+        """h2r_verify_circuit_copy_map: the closed map over circuit rows as H2RCopy -- no H2R_COPY_SRC_* entry is left."""
+        eb = _e_bytes(e)
+        return self._copy_pairs(lambda out, cap: lib().h2r_verify_circuit_copy_map(self._ctx, ctypes.byref(vl), eb, len(eb), out, cap),
+                                "h2r_verify_circuit_copy_map")
+
     def image_bytes(self, rows: int) -> int:
         """Bytes of one element's advice image of `rows` rows in the chip's representation: rows * 160 (row-major, or planar with
         the five columns packed), 5 * col_stride for planar columns of a fixed stride."""

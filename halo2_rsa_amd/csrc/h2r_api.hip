@@ -189,7 +189,7 @@ struct h2r_ctx {
     mutable hipStream_t side_stream = nullptr;
     mutable hipEvent_t side_fork = nullptr, side_join = nullptr;
     // row programs of the Fresh-op advice images (h2r_rowprog.hpp), built on first use; key = op | assert_one << 8
-    struct RowProg { std::vector<RpRow> host; RpRow *dev = nullptr; std::vector<u32> inv_rows; u32 *inv_dev = nullptr; };
+    struct RowProg { std::vector<RpRow> host; RpRow *dev = nullptr; std::vector<u32> inv_rows; u32 *inv_dev = nullptr; std::vector<h2r_copy> copies; };
     mutable std::mutex prog_mu;
     mutable std::map<u32, RowProg> progs;
     // h2r_advice_check: the per-kind table (selectors, lookup bit lengths) of a (lookup configuration, layout) pair, on the device
@@ -612,7 +612,7 @@ int32_t pow_layout(const h2r_ctx *ctx, const Exponent &e, h2r_pow_layout *out) {
 // One RSAChip::verify_pkcs1v15_signature element: the pow element, then the in-field and the encoded-message witness.
 int32_t verify_layout(const h2r_ctx *ctx, const Exponent &e, h2r_verify_layout *out) {
     if (!ctx || !out) return H2R_E_NULL;
-    if (ctx->layout.limb_width != 64 || ctx->L < 9) return H2R_E_SHAPE;  // RSAChip::LIMB_WIDTH, src/chip.rs:203
+    if (ctx->layout.limb_width != 64 || ctx->L < 8) return H2R_E_SHAPE;  // RSAChip::LIMB_WIDTH, src/chip.rs:203
     std::memset(out, 0, sizeof *out);
     int32_t rc = pow_layout(ctx, e, &out->pow);
     if (rc) return rc;
@@ -2227,7 +2227,7 @@ int32_t h2r_signature_verifier_batch(const h2r_ctx *ctx, const uint8_t *msgs, co
                                      uint8_t *is_valid_out, uint8_t *status, void *workspace, h2r_stream_t stream) try {
     if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/true)) return g;
     if (!hashed_out) return H2R_E_NULL;
-    if (ctx && (ctx->layout.limb_width != 64 || ctx->L < 9)) return H2R_E_SHAPE;   // before any launch: RSAChip::LIMB_WIDTH
+    if (ctx && (ctx->layout.limb_width != 64 || ctx->L < 8)) return H2R_E_SHAPE;   // before any launch: RSAChip::LIMB_WIDTH
     const int32_t rc = h2r_sha256_hashed_msg_batch(ctx, msgs, msg_off, fixed_len, batch, digest_out, hashed_out, hm_trace, hm_stride, stream);
     if (rc) return rc;
     return h2r_verify_pkcs1v15_batch(ctx, sig, n, e_le, e_len, hashed_out, batch, flags, trace, powed_out, is_valid_out, status, workspace, stream);
@@ -3230,6 +3230,7 @@ int32_t row_prog(const h2r_ctx *ctx, u32 key, const std::function<bool(RowProgBu
         if (!build(rb)) return H2R_E_UNSUPPORTED;
         h2r_ctx::RowProg rp;
         rp.host = std::move(rb.rows);
+        rp.copies = std::move(rb.copies);
         for (u32 r = 0; r < rp.host.size(); ++r) if (rp.host[r].c[1].type == RP_INV34) rp.inv_rows.push_back(r);
         if (ctx->params.device >= 0) {
             DeviceGuard dg(ctx->params.device);
@@ -3264,7 +3265,7 @@ int32_t launch_row_prog(const h2r_ctx *ctx, const h2r_ctx::RowProg *rp, RowProgA
     const long sr_k = knobs().rowprog_stage_rows;
     const u32 sr_env = (sr_k == 64 || sr_k == 128 || sr_k == 256) ? (u32)sr_k : 0u;
     const u32 sr = sr_env ? sr_env : ((ctx->repr.flags & H2R_ADVICE_MONTGOMERY) ? 64u : 256u);
-    const u64 blocks = ra.batch * ((ra.rows + sr - 1) / sr);
+    const u64 blocks = ra.batch * rowprog_chunks(ra.rows, ra.tail_rows, sr);
     if (blocks == 0) return H2R_OK;
     if (blocks >= (1ull << 31)) return H2R_E_UNSUPPORTED;
     const u32 w = ctx->layout.limb_width;
@@ -3655,7 +3656,7 @@ int32_t h2r_pipeline_modpow_public_key_advice(h2r_pipeline *p, const void *x, co
 // and nothing else -- no record planes.  `pow` keeps its counts (rows, the number of mul_mods); pow.off_records = UINT64_MAX marks the absence.
 int32_t h2r_verify_layout_compact(const h2r_ctx *ctx, const h2r_verify_layout *full, h2r_verify_layout *out) try {
     if (!ctx || !full || !out) return H2R_E_NULL;
-    if (ctx->layout.limb_width != 64 || ctx->L < 9) return H2R_E_SHAPE;
+    if (ctx->layout.limb_width != 64 || ctx->L < 8) return H2R_E_SHAPE;
     const AuxGeom g(ctx->L, 64);
     *out = *full;
     out->off_in_field = 0;
@@ -5659,6 +5660,124 @@ uint64_t h2r_pow_copy_map(const h2r_ctx *ctx, const h2r_pow_layout *pl, const ui
         }
     }
     return n;
+} H2R_CATCH_ZERO
+
+// The copy constraints of one Fresh-integer op's rows (h2r_fresh_op_emit_advice's image): the pairs the symbolic walk recorded next to
+// the rows (RowProgBuilder's origins), rows counted from row_offset; the op's operands stay H2R_COPY_SRC_A / _B / _N.
+uint64_t h2r_fresh_op_copy_map(const h2r_ctx *ctx, uint32_t op, uint32_t flags, uint64_t row_offset, h2r_copy *out, uint64_t cap) try {
+    const h2r_ctx::RowProg *rp = nullptr;
+    if (!ctx || fresh_row_prog(ctx, op, flags, &rp)) return 0;
+    if (row_offset + rp->host.size() >= 0xFFFFFF00ull) return 0;
+    u64 n = 0;
+    for (const h2r_copy &c : rp->copies) {
+        if (out && n < cap) out[n] = h2r_copy{(uint32_t)(row_offset + c.row), c.col, c.src_row >= 0xFFFFFF00u ? c.src_row : (uint32_t)(row_offset + c.src_row), c.src_col};
+        ++n;
+    }
+    return n;
+} H2R_CATCH_ZERO
+
+// ---- the closed verify_pkcs1v15_signature circuit: assignment rows around the element, one copy map over all of it ---------------
+// rows 0 .. P: assign_signature, assign_public_key (n), the four hashed-message limbs (P = 4 L + 8); rows P .. P + E: the element as
+// h2r_verify_emit_advice writes it; row P + E: main_gate.assert_one(is_valid)  (benches/bench.rs:145-221, Fix exponent).
+namespace {
+constexpr u32 kProgFrame = 0x1003;
+struct CircuitRows { const h2r_ctx::RowProg *frame, *pre, *inf, *em; u64 P, sec[4], E; };
+int32_t circuit_rows(const h2r_ctx *ctx, const h2r_verify_layout *vl, CircuitRows *cr) {
+    if (vl->pow.off_e_bits != UINT64_MAX) return H2R_E_UNSUPPORTED;   // a Var element: h2r_pow_copy_map is fixed-exponent too
+    int32_t rc = verify_progs(ctx, &cr->pre, &cr->inf, &cr->em);      // (64-bit limbs, L >= 8)
+    if (!rc) rc = row_prog(ctx, kProgFrame, [](RowProgBuilder &rb) { rb.build_frame(); return true; }, &cr->frame);
+    if (rc) return rc;
+    cr->P = cr->frame->host.size() - 1;
+    cr->E = h2r_verify_advice_rows(ctx, vl, cr->sec);
+    if (cr->E == 0 || cr->P + cr->E + 1 >= 0xFFFFFF00ull) return H2R_E_UNSUPPORTED;
+    return H2R_OK;
+}
+}  // namespace
+
+uint64_t h2r_verify_circuit_rows(const h2r_ctx *ctx, const h2r_verify_layout *vl, uint64_t section_rows[3]) try {
+    CircuitRows cr;
+    if (!ctx || !vl || circuit_rows(ctx, vl, &cr)) return 0;
+    if (section_rows) { section_rows[0] = cr.P; section_rows[1] = cr.E; section_rows[2] = 1; }
+    return cr.P + cr.E + 1;
+} H2R_CATCH_ZERO
+
+int32_t h2r_verify_circuit_row_kinds(const h2r_ctx *ctx, const h2r_verify_layout *vl, uint8_t *kinds_out) try {
+    if (!ctx || !vl || !kinds_out) return H2R_E_NULL;
+    CircuitRows cr;
+    if (const int32_t rc = circuit_rows(ctx, vl, &cr)) return rc;
+    for (u64 r = 0; r < cr.P; ++r) kinds_out[r] = (uint8_t)cr.frame->host[r].kind;
+    if (const int32_t rc = h2r_verify_row_kinds(ctx, vl, kinds_out + cr.P)) return rc;
+    kinds_out[cr.P + cr.E] = (uint8_t)cr.frame->host[cr.P].kind;
+    return H2R_OK;
+} H2R_CATCH_STATUS
+
+// Writes the frame rows only (rows 0 .. P and row P + E of every element's image); the element rows belong to whichever producer the caller
+// points at row P.  One launch of the row-program interpreter: the operands' limbs are range-decomposed in place, the last row is the
+// program's tail.
+int32_t h2r_verify_circuit_emit_frame(const h2r_ctx *ctx, const h2r_verify_layout *vl, const void *sig, const void *n, const uint64_t *hashed,
+                                      const uint8_t *is_valid, uint32_t flags, uint64_t batch, const uint8_t *status, void *advice_out,
+                                      uint64_t out_stride, h2r_stream_t stream) try {
+    if (const int32_t g = moduli_guard(flags, n, /*keyed_export=*/false)) return g;
+    if (!ctx || !vl || !sig || !n || !hashed || !is_valid || !advice_out) return H2R_E_NULL;
+    if (ctx->params.device < 0) return H2R_E_UNSUPPORTED;
+    CircuitRows cr;
+    int32_t rc = circuit_rows(ctx, vl, &cr);
+    if (rc) return rc;
+    AdviceDst dst;
+    if ((rc = advice_dst(ctx, advice_out, out_stride, cr.P + cr.E + 1, batch, &dst))) return rc;
+    if (batch == 0) return H2R_OK;
+    RowProgArgs ra;
+    std::memset(&ra, 0, sizeof ra);
+    ra.a = sig; ra.a_stride = ctx->L;
+    ra.n = n; ra.n_stride = (flags & H2R_F_SHARED_MODULUS) ? 0 : ctx->L;
+    ra.b = hashed; ra.b_stride = 4;
+    ra.trace = is_valid; ra.elem_stride = 1; ra.first_off = 0;   // the tail row's region: the element's is_valid byte
+    ra.status = status; ra.batch = batch; ra.dst = dst;
+    ra.tail_rows = 1; ra.tail_skip = cr.E;
+    H2R_ON_DEVICE(ctx->params.device);
+    return launch_row_prog(ctx, cr.frame, ra, static_cast<hipStream_t>(stream));
+} H2R_CATCH_STATUS
+
+// The closed map over circuit rows: every section's own pairs, and every operand tie resolved to the cell that holds the operand.
+uint64_t h2r_verify_circuit_copy_map(const h2r_ctx *ctx, const h2r_verify_layout *vl, const uint8_t *e_le_bytes, size_t e_len,
+                                     h2r_copy *out, uint64_t cap) try {
+    CircuitRows cr;
+    if (!ctx || !vl || circuit_rows(ctx, vl, &cr)) return 0;
+    const u32 L = ctx->L;
+    const u64 r_pre = cr.P, r_inf = r_pre + cr.sec[0], r_pow = r_inf + cr.sec[1], r_em = r_pow + cr.sec[2], r_last = cr.P + cr.E;
+    const u64 n_pow = h2r_pow_copy_map(ctx, &vl->pow, e_le_bytes, e_len, r_pow, nullptr, 0);
+    if (n_pow == 0) return 0;   // (an exponent that is not the layout's)
+    std::vector<h2r_copy> pw(n_pow);
+    if (h2r_pow_copy_map(ctx, &vl->pow, e_le_bytes, e_len, r_pow, pw.data(), n_pow) != n_pow) return 0;
+    // limb j of the assigned integers: column e of the first row of the limb's RangeChip::assign
+    auto sig_cell = [&](u32 j) { return (u64)2 * j; };
+    auto mod_cell = [&](u32 j) { return (u64)2 * L + 2 * j; };
+    auto hashed_cell = [&](u32 j) { return (u64)4 * L + 2 * j; };
+    const u64 r_powed = r_pow + 2 + (u64)(vl->pow.num_mul_mods - 1) * h2r_advice_rows(ctx) + 2 * L;   // r limb j of the LAST record: + 2 j
+    u64 cnt = 0;
+    auto push = [&](u64 row, u32 col, u64 src_row, u32 src_col) {
+        if (out && cnt < cap) out[cnt] = h2r_copy{(uint32_t)row, col, (uint32_t)src_row, src_col};
+        ++cnt;
+    };
+    // one section's program pairs, its operands A / B resolved by `a_cell` / `b_cell`
+    auto section = [&](const h2r_ctx::RowProg *rp, u64 base, const std::function<u64(u32)> &a_cell, const std::function<u64(u32)> &b_cell) {
+        for (const h2r_copy &c : rp->copies) {
+            if (c.src_row == H2R_COPY_SRC_A) push(base + c.row, c.col, a_cell(c.src_col), 4);
+            else if (c.src_row == H2R_COPY_SRC_B) push(base + c.row, c.col, b_cell(c.src_col), 4);
+            else if (c.src_row == RP_ORIGIN_SEED) push(base + c.row, c.col, r_pre, 0);            // the first and's is_eq: the element's CONST1 row
+            else if (c.src_row == RP_ORIGIN_VALID) push(r_last, c.col, r_last - 1, 2);             // assert_one [is_valid]: the last running AND
+            else push(base + c.row, c.col, base + c.src_row, c.src_col);
+        }
+    };
+    section(cr.frame, 0, sig_cell, hashed_cell);                                                   // (the frame's one pair)
+    section(cr.inf, r_inf, sig_cell, mod_cell);                                                    // assert_in_field(sig, n)
+    for (const h2r_copy &c : pw) {                                                                 // pow_mod_fixed_exp(sig, e, n)
+        if (c.src_row == H2R_COPY_SRC_A) push(c.row, c.col, sig_cell(c.src_col), 4);
+        else if (c.src_row == H2R_COPY_SRC_N) push(c.row, c.col, mod_cell(c.src_col), 4);
+        else push(c.row, c.col, c.src_row, c.src_col);
+    }
+    section(cr.em, r_em, [&](u32 j) { return r_powed + 2 * j; }, hashed_cell);                      // encoded-message check (powed, hashed)
+    return cnt;
 } H2R_CATCH_ZERO
 
 // ---- in-place audit ----------------------------------------------------------------------------------------

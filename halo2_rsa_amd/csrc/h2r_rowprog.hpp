@@ -13,6 +13,7 @@
 #include <utility>
 #include <vector>
 
+#include "h2r.h"
 #include "h2r_kernels.hpp"
 #include "h2r_field.hpp"
 
@@ -53,11 +54,20 @@ struct RpRow { RpCell c[5]; u32 kind, pad; };   // 48 bytes
 static_assert(sizeof(RpRow) == 48, "three 16-byte loads per row");
 
 // ---- host: the symbolic walk ---------------------------------------------------------------------------------------
+//
+// Origins.  Every value the walk hands on also remembers the cell where the reference FIRST assigned it: a row of this program and a
+// column, limb j of an operand (H2R_COPY_SRC_A / _B / _N, as in copy_map_record), or nothing (an unassigned zero).  A row that takes a
+// value with an origin as one of its visible cells records the copy pair (this row, that column) <- origin; the cells an op assigns
+// fresh -- results, bits, inverses, range sub-limbs, constants -- become origins.  Same walk, so the pairs cannot drift from the rows.
+constexpr u32 RP_NO_ORIGIN = 0xFFFFFFFFu;
+constexpr u32 RP_ORIGIN_SEED = 0xFFFFFF04u;    // build_em: the preamble's assign_constant(1) (the whole element's CONST1 row)
+constexpr u32 RP_ORIGIN_VALID = 0xFFFFFF05u;   // build_frame: the is_valid the encoded-message check returns (its last running AND)
 struct RowProgBuilder {
     const AuxGeom g;
     std::vector<RpRow> rows;
+    std::vector<h2r_copy> copies;   // (row, col) <- (src_row, src_col); rows of this program
     u64 off = 0;   // section cursor inside the element's region, as fresh_sections / the kernels advance it
-    using V = RpCell;
+    struct V : RpCell { u32 orow = RP_NO_ORIGIN, ocol = 0; };   // host only: the interpreter sees the RpCell
     using Int = std::vector<V>;
 
     explicit RowProgBuilder(const AuxGeom &g_) : g(g_) {}
@@ -66,45 +76,64 @@ struct RowProgBuilder {
     static V one() { return mk(RP_ONE); }
     V st(u64 o, u32 width) const { return mk(RP_STREAM, (u32)o, (u8)width); }
     static V hidden(V v) { v.type |= RP_HIDDEN; return v; }
-    static Int operand(u8 type, u32 n) { Int r; for (u32 i = 0; i < n; ++i) r.push_back(mk(type, i)); return r; }
+    static V at(V v, u32 orow, u32 ocol) { v.orow = orow; v.ocol = ocol; return v; }   // v, first assigned at (orow, ocol)
+    static Int operand(u8 type, u32 n) {
+        Int r;
+        for (u32 i = 0; i < n; ++i) r.push_back(at(mk(type, i), type == RP_IN_A ? H2R_COPY_SRC_A : type == RP_IN_B ? H2R_COPY_SRC_B : H2R_COPY_SRC_N, i));
+        return r;
+    }
 
-    void row(u32 kind, V c0 = zero(), V c1 = zero(), V c2 = zero(), V c3 = zero(), V c4 = zero()) {
-        RpRow r; r.c[0] = c0; r.c[1] = c1; r.c[2] = c2; r.c[3] = c3; r.c[4] = c4; r.kind = kind; r.pad = 0;
+    u32 row(u32 kind, V c0 = zero(), V c1 = zero(), V c2 = zero(), V c3 = zero(), V c4 = zero()) {   // returns the row's index
+        const V *c[5] = {&c0, &c1, &c2, &c3, &c4};
+        const u32 idx = (u32)rows.size();
+        RpRow r; r.kind = kind; r.pad = 0;
+        for (u32 q = 0; q < 5; ++q) {
+            r.c[q] = *c[q];
+            if (!(c[q]->type & RP_HIDDEN) && c[q]->orow != RP_NO_ORIGIN) copies.push_back(h2r_copy{idx, q, c[q]->orow, c[q]->ocol});
+        }
         rows.push_back(r);
+        return idx;
     }
-    void range_limb(u64 ra_off) {   // RangeChip::assign(limb, w/8, w): value at ra_off, its eight sub-limb bytes behind it
-        row(ROWK_RANGE_LIMB + 0, st(ra_off, g.LB));
-        row(ROWK_RANGE_LIMB + 1, st(ra_off, g.LB));
+    V const_row(u32 kind, V v = zero()) { const u32 r = row(kind, v); return at(v, r, 0); }   // main_gate.assign_constant: the cell later rows copy
+    V range_rows(u32 kind, V src, V value) {   // RangeChip::assign: two rows; the assigned value is column e of the first
+        const u32 r = row(kind + 0, src);
+        row(kind + 1, src);
+        return at(value, r, 4);
     }
-    void is_zero_rows(V x, V y, V flag) {   // main_gate.is_zero(d = x - y): assign_bit(r), [d, d', r], [r, d]
-        row(ROWK_BIT, flag, flag, flag);
-        row(ROWK_ISZERO_INV, mk(RP_DIFF34), mk(RP_INV34), flag, hidden(x), hidden(y));
-        row(ROWK_ISZERO_RA, flag, mk(RP_DIFF34), zero(), hidden(x), hidden(y));
+    V range_limb(u64 ra_off) {   // RangeChip::assign(limb, w/8, w): value at ra_off, its eight sub-limb bytes behind it
+        return range_rows(ROWK_RANGE_LIMB, st(ra_off, g.LB), st(ra_off, g.LB));
     }
-    void is_equal(V x, V y, V flag) {       // main_gate.is_equal = sub + is_zero
-        row(ROWK_SUB, x, y, mk(RP_DIFF01));
-        is_zero_rows(x, y, flag);
+    // main_gate.is_zero(d = x - y): assign_bit(r), [d, d', r], [r, d]; d was first assigned where `d_at` says.  Returns r.
+    V is_zero_rows(V x, V y, V flag, V d_at) {
+        const V f = at(flag, row(ROWK_BIT, flag, flag, flag), 0);
+        const V d = at(mk(RP_DIFF34), d_at.orow, d_at.ocol);
+        row(ROWK_ISZERO_INV, d, mk(RP_INV34), f, hidden(x), hidden(y));
+        row(ROWK_ISZERO_RA, f, d, zero(), hidden(x), hidden(y));
+        return f;
+    }
+    V is_equal(V x, V y, V flag) {          // main_gate.is_equal = sub + is_zero
+        const u32 r = row(ROWK_SUB, x, y, mk(RP_DIFF01));
+        return is_zero_rows(x, y, flag, at(zero(), r, 2));
     }
 
     Int add(const Int &a, const Int &b) {   // chip.rs:245-297; section layout of aux_add
         const u32 n = (u32)std::max(a.size(), b.size());
         const u64 sec = off;
         off += g.add_sz(n);
-        row(ROWK_CONST0);                   // zero_value :254
-        row(ROWK_CONST_B, mk(RP_B));        // limb_max_val :267
+        const V zv = const_row(ROWK_CONST0);              // zero_value :254: pads the shorter operand, and is carrys[0]
+        const V lmax = const_row(ROWK_CONST_B, mk(RP_B)); // limb_max_val :267
         Int out;
-        V carry = zero();
+        V carry = zv;
         for (u32 i = 0; i < n; ++i) {
             const u64 q = sec + (u64)i * g.STEP;
-            const V ai = i < a.size() ? a[i] : zero(), bi = i < b.size() ? b[i] : zero();
-            const V a_b = st(q, g.SB), sum = st(q + g.SB, g.SB), c = st(q + 2 * g.SB, g.LB), cy = st(q + 2 * g.SB + g.RA, g.LB),
-                    cac = st(q + 2 * g.SB + 2 * g.RA, g.SB);
-            row(ROWK_ADD, ai, bi, a_b);                 // :272
-            row(ROWK_ADD, a_b, carry, sum);             // :273
-            range_limb(q + 2 * g.SB);                   // c :279-280
-            range_limb(q + 2 * g.SB + g.RA);            // carry :281-282
-            row(ROWK_MUL_ADD, cy, mk(RP_B), c, cac);    // :283
-            row(ROWK_ASSERT_EQ, sum, cac);              // :285
+            const V ai = i < a.size() ? a[i] : zv, bi = i < b.size() ? b[i] : zv;
+            V a_b = st(q, g.SB), sum = st(q + g.SB, g.SB), cac = st(q + 2 * g.SB + 2 * g.RA, g.SB);
+            a_b = at(a_b, row(ROWK_ADD, ai, bi, a_b), 2);            // :272
+            sum = at(sum, row(ROWK_ADD, a_b, carry, sum), 2);        // :273
+            const V c = range_limb(q + 2 * g.SB);                    // c :279-280
+            const V cy = range_limb(q + 2 * g.SB + g.RA);            // carry :281-282
+            cac = at(cac, row(ROWK_MUL_ADD, cy, lmax, c, cac), 3);   // :283
+            row(ROWK_ASSERT_EQ, sum, cac);                           // :285
             out.push_back(c);
             carry = cy;
         }
@@ -117,28 +146,24 @@ struct RowProgBuilder {
         const u32 n = larger ? n1 : n2;
         const u64 sec = off;
         off += g.eq_sz(n);
-        row(ROWK_BIT, one(), one(), one());
-        V eq = one();
+        V eq = at(one(), row(ROWK_BIT, one(), one(), one()), 0);
         for (u32 i = 0; i < n; ++i) {
             V flag = st(sec + 2ull * i, 1), run = st(sec + 2ull * i + 1, 1);
-            if (larger && i >= n2) is_zero_rows(a[i], zero(), flag);
-            else if (!larger && i >= n1) is_zero_rows(b[i], zero(), flag);
-            else is_equal(a[i], b[i], flag);
-            row(ROWK_MUL, eq, flag, run);               // and
-            eq = run;
+            if (larger && i >= n2) flag = is_zero_rows(a[i], zero(), flag, a[i]);
+            else if (!larger && i >= n1) flag = is_zero_rows(b[i], zero(), flag, b[i]);
+            else flag = is_equal(a[i], b[i], flag);
+            eq = at(run, row(ROWK_MUL, eq, flag, run), 2);   // and
         }
         return eq;
     }
     V is_zero(const Int &a) {                        // chip.rs:754-767 (the kernel writes it as aux_eq against zero)
         const u64 sec = off;
         off += g.eq_sz((u32)a.size());
-        row(ROWK_BIT, one(), one(), one());
-        V bit = one();
+        V bit = at(one(), row(ROWK_BIT, one(), one(), one()), 0);
         for (u32 i = 0; i < a.size(); ++i) {
             V flag = st(sec + 2ull * i, 1), run = st(sec + 2ull * i + 1, 1);
-            is_zero_rows(a[i], zero(), flag);
-            row(ROWK_MUL, bit, flag, run);
-            bit = run;
+            flag = is_zero_rows(a[i], zero(), flag, a[i]);
+            bit = at(run, row(ROWK_MUL, bit, flag, run), 2);
         }
         return bit;
     }
@@ -147,7 +172,7 @@ struct RowProgBuilder {
         const u64 sec = off;
         off += g.cl_sz(n1);
         Int c;
-        for (u32 i = 0; i < n1; ++i) { range_limb(sec + (u64)i * g.RA); c.push_back(st(sec + (u64)i * g.RA, g.LB)); }
+        for (u32 i = 0; i < n1; ++i) c.push_back(range_limb(sec + (u64)i * g.RA));
         const Int added = add(b, c);
         const V ok = is_equal_fresh(a, added);
         row(ROWK_ASSERT_ONE, ok);                       // assert_equal_fresh -> assert_one
@@ -156,29 +181,26 @@ struct RowProgBuilder {
     std::pair<Int, V> sub(const Int &a, const Int &b) {   // chip.rs:310-373; aux_sub
         const u32 nA = (u32)a.size(), n2 = (u32)b.size(), m = std::max(nA, n2), n1 = m + 1;
         Int max_int;
-        for (u32 i = 0; i < n2; ++i) { row(ROWK_CONST_BM1, mk(RP_BM1)); max_int.push_back(mk(RP_BM1)); }   // max_value :138-154
+        for (u32 i = 0; i < n2; ++i) max_int.push_back(const_row(ROWK_CONST_BM1, mk(RP_BM1)));   // max_value :138-154
         const Int inflated_a = add(a, max_int);
         const Int is_ = sub_unchecked(inflated_a, b);
-        const V not_ov = st(off, 1), ov = st(off + 1, 1);
+        V not_ov = st(off, 1), ov = st(off + 1, 1);
         off += 16;
-        row(ROWK_BIT, one(), one(), one());             // one :326
-        is_equal(is_[n2], one(), not_ov);               // :330
-        row(ROWK_NOT, not_ov, ov);                      // :331
-        row(ROWK_CONST0);                               // zero_value :343
+        const V one_bit = at(one(), row(ROWK_BIT, one(), one(), one()), 0);   // one :326
+        not_ov = is_equal(is_[n2], one_bit, not_ov);    // :330
+        ov = at(ov, row(ROWK_NOT, not_ov, ov), 1);      // :331
+        const V zv = const_row(ROWK_CONST0);            // zero_value :343
         Int sel_l, sel_r;
         const u64 sl = off, sr = off + AuxGeom::a16((u64)n1 * g.LB);
         off = sr + AuxGeom::a16((u64)m * g.LB);
-        for (u32 i = 0; i < n1; ++i) {                  // :345-357
-            const V v = st(sl + (u64)i * g.LB, g.LB);
-            row(ROWK_SELECT, not_ov, is_[i], not_ov, i >= n2 ? zero() : b[i], v);
-            sel_l.push_back(v);
-        }
+        auto select = [&](V x, V y, V v) { return at(v, row(ROWK_SELECT, not_ov, x, not_ov, y, v), 4); };
+        for (u32 i = 0; i < n1; ++i)                    // :345-357
+            sel_l.push_back(select(is_[i], i >= n2 ? zv : b[i], st(sl + (u64)i * g.LB, g.LB)));
         for (u32 i = 0; i < m; ++i) {                   // :358-367
             const V v = st(sr + (u64)i * g.LB, g.LB);
-            if (i >= nA) row(ROWK_SELECT, not_ov, max_int[i], not_ov, zero(), v);
-            else if (i >= n2) row(ROWK_SELECT, not_ov, zero(), not_ov, a[i], v);
-            else row(ROWK_SELECT, not_ov, max_int[i], not_ov, a[i], v);
-            sel_r.push_back(v);
+            if (i >= nA) sel_r.push_back(select(max_int[i], zv, v));
+            else if (i >= n2) sel_r.push_back(select(zv, a[i], v));
+            else sel_r.push_back(select(max_int[i], a[i], v));
         }
         Int real = sub_unchecked(sel_l, sel_r);
         return {real, ov};
@@ -186,60 +208,71 @@ struct RowProgBuilder {
     V is_less_than(const Int &a, const Int &b) {     // chip.rs:908-919; aux_less_than
         const V ov = sub(a, b).second;
         const V is_eq = is_equal_fresh(a, b);
-        const V is_not_eq = st(off, 1), lt = st(off + 1, 1);
+        V is_not_eq = st(off, 1), lt = st(off + 1, 1);
         off += 16;
-        row(ROWK_NOT, is_eq, is_not_eq);                // :917
-        row(ROWK_MUL, ov, is_not_eq, lt);               // :918
-        return lt;
+        is_not_eq = at(is_not_eq, row(ROWK_NOT, is_eq, is_not_eq), 1);   // :917
+        return at(lt, row(ROWK_MUL, ov, is_not_eq, lt), 2);              // :918
     }
     void select_mod(const Int &x, const Int &y, V cond, u32 n_limbs) {   // tail of add_mod :466-478 / sub_mod :512-525
-        row(ROWK_CONST0);
+        const V zv = const_row(ROWK_CONST0);
         const u32 num = (u32)std::max(x.size(), y.size());
-        for (u32 i = 0; i < num; ++i)
-            row(ROWK_SELECT, cond, i < x.size() ? x[i] : zero(), cond, i < y.size() ? y[i] : zero(), st(off + (u64)i * g.LB, g.LB));
-        for (u32 i = n_limbs; i < num; ++i) row(ROWK_ASSERT_ZERO, st(off + (u64)i * g.LB, g.LB));
+        Int out;
+        for (u32 i = 0; i < num; ++i) {
+            const V v = st(off + (u64)i * g.LB, g.LB);
+            out.push_back(at(v, row(ROWK_SELECT, cond, i < x.size() ? x[i] : zv, cond, i < y.size() ? y[i] : zv, v), 4));
+        }
+        for (u32 i = n_limbs; i < num; ++i) row(ROWK_ASSERT_ZERO, out[i]);
     }
 
-    void range_u32(u64 ra_off) { row(ROWK_RANGE_U32 + 0, st(ra_off, 4)); row(ROWK_RANGE_U32 + 1, st(ra_off, 4)); }
+    V range_u32(u64 ra_off) { return range_rows(ROWK_RANGE_U32, st(ra_off, 4), st(ra_off, 4)); }
     // RSAChip::verify_pkcs1v15_signature after the modpow (src/chip.rs:138-198; 64-bit limbs): operand A = powed, B = hashed (4 limbs);
     // region = the encoded-message region the aux role wrote (flags, the two 32-bit range assigns, the recomposed limb)
     void build_em() {
         const u32 L = g.L;
         const Int A = operand(RP_IN_A, L), H = operand(RP_IN_B, 4);
-        auto K = [&](u32 j) { return mk(RP_CONST64, j); };
-        V is_eq = one();                                    // the cell of the preamble's assign_constant(1), :137
-        auto and_ = [&](V flag, V run) { row(ROWK_MUL, is_eq, flag, run); is_eq = run; };
-        for (u32 i = 0; i < 4; ++i) { is_equal(A[i], H[i], st(2 * i, 1)); and_(st(2 * i, 1), st(2 * i + 1, 1)); }   // :141-144
-        row(ROWK_CONST_EM + 0, K(0)); row(ROWK_CONST_EM + 1, K(1));                                                  // :149-152
-        is_equal(A[4], K(0), st(8, 1)); is_equal(A[5], K(1), st(9, 1));                                              // :153-154
-        and_(st(8, 1), st(10, 1)); and_(st(9, 1), st(11, 1));                                                        // :155-156
-        range_u32(12); range_u32(24);                                                                                // :170-171
-        const V low = st(12, 4), high = st(24, 4), concat = st(36, 8);
-        row(ROWK_CONST_EM + 2, K(2));                                                                                // :172
-        row(ROWK_MUL_ADD, high, K(2), low, concat);                                                                  // :173
+        auto K = [&](u32 j) { return const_row(ROWK_CONST_EM + j, mk(RP_CONST64, j)); };
+        V is_eq = at(one(), RP_ORIGIN_SEED, 0);             // the cell of the preamble's assign_constant(1), :137
+        // is_eq = and(is_eq, is_equal(x, y)): the flag byte at `fo`, the running AND at `ro`
+        auto eq_and = [&](V x, V y, u64 fo, u64 ro) { const V flag = is_equal(x, y, st(fo, 1)); is_eq = at(st(ro, 1), row(ROWK_MUL, is_eq, flag, st(ro, 1)), 2); };
+        for (u32 i = 0; i < 4; ++i) eq_and(A[i], H[i], 2 * i, 2 * i + 1);                                            // :141-144
+        const V k0 = K(0), k1 = K(1);                                                                                // :149-152
+        const V f4 = is_equal(A[4], k0, st(8, 1)), f5 = is_equal(A[5], k1, st(9, 1));                                // :153-154
+        is_eq = at(st(10, 1), row(ROWK_MUL, is_eq, f4, st(10, 1)), 2);                                               // :155
+        is_eq = at(st(11, 1), row(ROWK_MUL, is_eq, f5, st(11, 1)), 2);                                               // :156
+        const V low = range_u32(12), high = range_u32(24);                                                           // :170-171
+        const V k2 = K(2);                                                                                           // :172
+        const V concat = at(st(36, 8), row(ROWK_MUL_ADD, high, k2, low, st(36, 8)), 3);                              // :173
         row(ROWK_ASSERT_EQ, A[6], concat);                                                                           // :174
-        row(ROWK_CONST_EM + 3, K(3)); is_equal(low, K(3), st(44, 1)); and_(st(44, 1), st(45, 1));                    // :175-177
-        row(ROWK_CONST_EM + 4, K(4)); is_equal(high, K(4), st(46, 1)); and_(st(46, 1), st(47, 1));                   // :180-182
-        row(ROWK_CONST_BM1, mk(RP_BM1));                                                                             // ff_64 :183-184
-        for (u32 i = 7; i + 1 < L; ++i) { const u64 f = 48 + 2ull * (i - 7); is_equal(A[i], mk(RP_BM1), st(f, 1)); and_(st(f, 1), st(f + 1, 1)); }   // :185-188
+        const V k3 = K(3); eq_and(low, k3, 44, 45);                                                                  // :175-177
+        const V k4 = K(4); eq_and(high, k4, 46, 47);                                                                 // :180-182
+        const V ff = const_row(ROWK_CONST_BM1, mk(RP_BM1));                                                          // ff_64 :183-184
+        for (u32 i = 7; i + 1 < L; ++i) { const u64 f = 48 + 2ull * (i - 7); eq_and(A[i], ff, f, f + 1); }           // :185-188
         const u64 f = 48 + 2ull * (L - 8);
-        row(ROWK_CONST_EM + 5, K(5)); is_equal(A[L - 1], K(5), st(f, 1)); and_(st(f, 1), st(f + 1, 1));              // :190-197
+        const V k5 = K(5); eq_and(A[L - 1], k5, f, f + 1);                                                           // :190-197
     }
     // RSASignatureVerifier::verify_pkcs1v15_signature, src/lib.rs:225-239: the four hashed-message limbs composed from the 32
     // reversed digest bytes; region = [32 byte cells][32 running limb values, 8 bytes each] (sha256_kernel, h2r_sha256.hpp)
     void build_hashed_msg() {
         for (u32 i = 0; i < 4; ++i) {
-            row(ROWK_CONST0);                                                        // limb_val = assign_constant(0) :226
-            V limb = zero();
+            V limb = const_row(ROWK_CONST0);                                         // limb_val = assign_constant(0) :226
             for (u32 j = 0; j < 8; ++j) {
-                const V coeff = mk(RP_POW2, 8 * j), nv = st(32 + 8ull * (8 * i + j), 8);
-                row(ROWK_CONST_COEFF8 + j, coeff);                                   // :228-229
-                row(ROWK_MUL_ADD, coeff, st(8 * i + j, 1), limb, nv);                // :230-235
-                limb = nv;
+                const V coeff = const_row(ROWK_CONST_COEFF8 + j, mk(RP_POW2, 8 * j)), nv = st(32 + 8ull * (8 * i + j), 8);   // :228-229
+                limb = at(nv, row(ROWK_MUL_ADD, coeff, st(8 * i + j, 1), limb, nv), 3);   // :230-235 (the byte cells are the SHA-256 chip's)
             }
         }
     }
     void build_verify_preamble() { row(ROWK_CONST1, one()); }   // is_eq = assign_constant(1), src/chip.rs:137 (before the modpow)
+    // What stands around the element in the reference's signature circuit (benches/bench.rs:145-221): assign_signature, assign_public_key
+    // (Fix exponent: n only), the four hashed-message limbs -- RangeChip::assign per limb, operand A = signature, N = modulus, B = hashed --
+    // and, behind the element, main_gate.assert_one(is_valid): region = the caller's is_valid byte.  The last row is the program's tail.
+    void build_frame() {
+        const u32 L = g.L;
+        auto assign_integer = [&](u8 type, u32 n) { for (u32 j = 0; j < n; ++j) range_rows(ROWK_RANGE_LIMB, mk(type, j), mk(type, j)); };
+        assign_integer(RP_IN_A, L);
+        assign_integer(RP_IN_N, L);
+        assign_integer(RP_IN_B, 4);
+        row(ROWK_ASSERT_ONE, at(st(0, 1), RP_ORIGIN_VALID, 0));
+    }
 
     // returns false for an unknown op
     bool build(u32 op, bool assert_one) {
@@ -260,8 +293,8 @@ struct RowProgBuilder {
             case FRESH_IS_EQUAL_FRESH: bit = is_equal_fresh(A, B); break;
             case FRESH_IS_LESS_THAN: case FRESH_IS_IN_FIELD: bit = is_less_than(A, B); break;
             case FRESH_IS_LESS_THAN_OR_EQUAL: bit = sub(A, B).second; break;
-            case FRESH_IS_GREATER_THAN: { const V le = sub(A, B).second; bit = st(off, 1); row(ROWK_NOT, le, bit); break; }              // :954-963
-            case FRESH_IS_GREATER_THAN_OR_EQUAL: { const V lt = is_less_than(A, B); bit = st(off, 1); row(ROWK_NOT, lt, bit); break; }   // :976-985
+            case FRESH_IS_GREATER_THAN: { const V le = sub(A, B).second; bit = st(off, 1); bit = at(bit, row(ROWK_NOT, le, bit), 1); break; }              // :954-963
+            case FRESH_IS_GREATER_THAN_OR_EQUAL: { const V lt = is_less_than(A, B); bit = st(off, 1); bit = at(bit, row(ROWK_NOT, lt, bit), 1); break; }   // :976-985
             default: return false;
         }
         if (assert_one) { if (!has_bit) return false; row(ROWK_ASSERT_ONE, bit); }
@@ -278,7 +311,10 @@ struct RowProgArgs {
     AdviceDst dst; const MontK *mk;     // the program's first row = row 0 of dst
     FieldConsts f;
     const u32 *inv_rows; u32 n_inv;     // the rows with an RP_INV34 cell (rowprog_inv_kernel fills those cells)
+    u32 tail_rows; u64 tail_skip;       // the program's last tail_rows rows land tail_skip rows further down (the frame's assert_one behind the element)
 };
+// workgroups per element of a program whose rows are staged sr at a time: the head and the tail never share a stage
+__host__ __device__ inline u32 rowprog_chunks(u32 rows, u32 tail_rows, u32 sr) { return (rows - tail_rows + sr - 1) / sr + (tail_rows + sr - 1) / sr; }
 
 // the value a cell descriptor names, for element `elem` whose region starts at `reg`
 template <int LW>
@@ -317,13 +353,15 @@ __global__ __launch_bounds__(SR) void rowprog_kernel(RowProgArgs a) {
     using limb_t = typename LimbT<LW>::type;
     __shared__ uint4 stage[SR * (ADVICE_ROW_BYTES / 16)];
     const u32 tid = threadIdx.x;
-    const u32 nchunks = (a.rows + SR - 1) / SR;
+    const u32 head = a.rows - a.tail_rows, hchunks = (head + SR - 1) / SR, nchunks = rowprog_chunks(a.rows, a.tail_rows, SR);
     const u32 item = xcd_contiguous_block(blockIdx.x, gridDim.x);
-    const u32 elem = item / nchunks, r0 = (item - elem * nchunks) * SR;
+    const u32 elem = item / nchunks, ci = item - elem * nchunks;
+    const bool tail = ci >= hchunks;
+    const u32 r0 = tail ? head + (ci - hchunks) * SR : ci * SR, r_end = tail ? a.rows : head;
     if (a.status && a.status[elem]) return;
     const u8 *reg = a.trace + (u64)elem * a.elem_stride + a.first_off;
     const u32 r = r0 + tid;
-    if (r < a.rows) {
+    if (r < r_end) {
         const uint4 *pr = reinterpret_cast<const uint4 *>(a.prog + r);
         union { uint4 q[3]; RpRow row; } u;
         u.q[0] = pr[0]; u.q[1] = pr[1]; u.q[2] = pr[2];
@@ -334,9 +372,17 @@ __global__ __launch_bounds__(SR) void rowprog_kernel(RowProgArgs a) {
         if ((rw.kind >= ROWK_RANGE_LIMB && rw.kind < ROWK_RANGE_LIMB + 2) || u32r) {
             // main_gate.decompose of a limb (eight w/8-bit sub-limbs) or of a 32-bit half (eight 4-bit ones): four sub-limb
             // bytes per row (the last row reversed), column e = what remains
-            const u8 *p = reg + rw.c[0].off;
-            const u32 *ps = reinterpret_cast<const u32 *>(p + (u32r ? 4 : LW / 8));
-            const u64 subs = ((u64)ps[1] << 32) | ps[0];
+            // bytes behind the value in the stream -- or, for a limb of an operand (assign_integer), the limb's own w/8-bit digits
+            u64 subs;
+            if (rw.c[0].type == RP_STREAM) {
+                const u8 *p = reg + rw.c[0].off;
+                const u32 *ps = reinterpret_cast<const u32 *>(p + (u32r ? 4 : LW / 8));
+                subs = ((u64)ps[1] << 32) | ps[0];
+            } else {
+                const u64 limb = fetch(rw.c[0]).v[0];
+                subs = limb;
+                if (LW != 64) { subs = 0; for (u32 k = 0; k < 8; ++k) subs |= ((limb >> (4 * k)) & 0xf) << (8 * k); }
+            }
             const u32 sb = u32r ? 4 : LW / 8;
             u64 rem = 0;
             const u32 k0 = (rw.kind & 1) ? 4u : 0u;
@@ -375,8 +421,8 @@ __global__ __launch_bounds__(SR) void rowprog_kernel(RowProgArgs a) {
         }
     }
     __syncthreads();
-    const u32 n_rows = a.rows - r0 < SR ? a.rows - r0 : SR;
-    advice_flush<SR>(a.dst, a.mk, a.dst.elem(elem), r0, n_rows, stage, tid);
+    const u32 n_rows = r_end - r0 < SR ? r_end - r0 : SR;
+    advice_flush<SR>(a.dst, a.mk, a.dst.elem(elem), r0 + (tail ? a.tail_skip : 0), n_rows, stage, tid);
 }
 
 

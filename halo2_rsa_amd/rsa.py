@@ -303,6 +303,30 @@ class VerifyResult:
                                            self.chip._stream()), "h2r_verify_emit_advice")
         return out
 
+    def emit_verify_circuit(self, direct: bool = False, out: "torch.Tensor" = None) -> "torch.Tensor":
+        """The closed circuit of the reference's bench (benches/bench.rs:145-221, Fix exponent): the assignment rows of the signature,
+        the modulus and the hashed message, the element, assert_one(is_valid) -- uint8 [batch, image_bytes(chip.verify_circuit_rows)].
+        The frame emitter (h2r_verify_circuit_emit_frame) writes rows 0 .. P and the last row, the element emitter
+        (h2r_verify_emit_advice) rows P .. P + E.  Its kinds: chip.verify_circuit_row_kinds(layout); its pairs:
+        chip.verify_circuit_copy_map(layout, e).  out: a caller's buffer (only the circuit's rows are written)."""
+        sig, n, hashed = self.inputs
+        n = _plain_moduli(n)
+        batch, chip = sig.batch, self.chip
+        rows, (P, _, _) = chip.verify_circuit_rows(self.layout)
+        if chip.columns and not chip.col_stride:
+            raise ValueError("emit_verify_circuit: two calls write one image -- planar columns need a fixed col_stride")
+        if out is None:
+            out = torch.empty((batch, chip.image_bytes(rows)), dtype=torch.uint8, device=self.trace.device)
+        flags = chip._flags(n, batch)
+        check(lib().h2r_verify_circuit_emit_frame(chip._ctx, ctypes.byref(self.layout), sig.data_ptr(), n.data_ptr(), hashed.data_ptr(),
+                                                  self.is_valid.data_ptr(), flags, batch, self.status.data_ptr(), out.data_ptr(), out.shape[1],
+                                                  chip._stream()), "h2r_verify_circuit_emit_frame")
+        check(lib().h2r_verify_emit_advice(chip._ctx, ctypes.byref(self.layout), sig.data_ptr(), n.data_ptr(), hashed.data_ptr(),
+                                           self.powed.data_ptr(), flags | (H2R_ADVICE_DIRECT if direct else 0), self.trace.data_ptr(),
+                                           self.workspace.data_ptr(), batch, self.status.data_ptr(), out.data_ptr() + P * (32 if chip.columns else 160),
+                                           out.shape[1], chip._stream()), "h2r_verify_emit_advice")
+        return out
+
     def flatten(self, elem: int) -> "np.ndarray":
         s = self.layout.elem_stride
         host = np.ascontiguousarray(self.trace[elem * s:(elem + 1) * s].cpu().numpy())

@@ -1628,6 +1628,42 @@ int32_t h2r_advice_check(const h2r_ctx *ctx, const struct h2r_lookup_config *cfg
                          uint32_t flags, uint32_t *bad_out, uint64_t *first_bad_out, h2r_stream_t stream);
 uint64_t h2r_pow_copy_map(const h2r_ctx *ctx, const h2r_pow_layout *pl, const uint8_t *e_le_bytes, size_t e_len, uint64_t row_offset,
                           h2r_copy *out, uint64_t cap);
+/* h2r_fresh_op_copy_map: the pairs of one Fresh-integer op's rows (the image of h2r_fresh_op_emit_advice with the same op and flags), rows
+ * counted from row_offset.  The row programs are a symbolic walk of the reference's control flow; every value of that walk remembers
+ * the cell where the reference first assigned it (results, bits, inverses, range-assigned values: column e of the assign's first row;
+ * assign_constant cells count), and every row that takes such a value as an input gives one pair.  The op's operands come out as
+ * H2R_COPY_SRC_A / _B / _N, limb src_col, as in h2r_advice_copy_map; an unassigned zero gives no pair.  Host-only; returns the number
+ * of pairs (out NULL / cap 0 to ask), 0 for an op / flags pair h2r_fresh_op_emit_advice refuses. */
+uint64_t h2r_fresh_op_copy_map(const h2r_ctx *ctx, uint32_t op, uint32_t flags, uint64_t row_offset, h2r_copy *out, uint64_t cap);
+
+/* ---- the closed verify_pkcs1v15_signature circuit (benches/bench.rs:145-221, sha2 disabled; RSAPubE::Fix) -------------------------
+ * The element of h2r_verify_emit_advice between the assignment rows the reference's circuit puts around it.  L = num_limbs (64-bit limbs),
+ * P = 4 L + 8, E = h2r_verify_advice_rows:
+ *     rows 0 .. 2L        assign_signature: RangeChip::assign per limb (kinds H2R_ROW_RANGE_LIMB + 0, + 1); limb j = column e of row 2j
+ *     rows 2L .. 4L       assign_public_key: the modulus, likewise (a fixed exponent assigns nothing)
+ *     rows 4L .. P        the four hashed-message limbs, likewise
+ *     rows P .. P + E     the element, exactly as h2r_verify_emit_advice writes it
+ *     row  P + E          main_gate.assert_one(is_valid): H2R_ROW_ASSERT_ONE [is_valid]
+ * h2r_verify_circuit_rows returns P + E + 1 and the three section sizes {P, E, 1}; h2r_verify_circuit_row_kinds the kinds of all rows.
+ * h2r_verify_circuit_emit_frame writes ONLY the frame (rows 0 .. P and row P + E) of every element image at advice_out (out_stride
+ * bytes apart, the ctx's representation; planar columns: a fixed col_stride, since the element's producer writes into the same
+ * columns) in one launch: sig, n, hashed as h2r_verify_emit_advice takes them (flags: H2R_F_SHARED_MODULUS), is_valid = the call's
+ * is_valid bytes; elements with a nonzero status byte (nullable) are skipped.  The element rows are the caller's to fill, with any
+ * producer (record-based, H2R_ADVICE_DIRECT, pipelined) pointed at row P.
+ * h2r_verify_circuit_copy_map: the copy pairs of the whole circuit, rows counted from row 0 -- the pairs of assert_in_field
+ * (h2r_fresh_op_copy_map), of the pow rows (h2r_pow_copy_map) and of the encoded-message check, with every operand tie resolved to a
+ * cell: in-field a and pow x = the signature cells, in-field b and pow n = the modulus cells, the encoded-message check's powed = the
+ * r limbs of the LAST record (h2r_pow_operand_sources), its hashed = the hashed cells, its first `and` = the element's CONST1 row,
+ * and the last row's cell = the last running AND.  No entry has src_row >= 0xFFFFFF00: a key made from these pairs ties the three
+ * sections to one signature, one modulus and one digest.  Host-only; returns the number of pairs (out NULL / cap 0 to ask).
+ * All four: 64-bit limbs, L >= 8; a Var layout is refused (0 rows / 0 pairs / H2R_E_UNSUPPORTED). */
+uint64_t h2r_verify_circuit_rows(const h2r_ctx *ctx, const h2r_verify_layout *vl, uint64_t section_rows[3]);
+int32_t h2r_verify_circuit_row_kinds(const h2r_ctx *ctx, const h2r_verify_layout *vl, uint8_t *kinds_out);
+int32_t h2r_verify_circuit_emit_frame(const h2r_ctx *ctx, const h2r_verify_layout *vl, const void *sig, const void *n, const uint64_t *hashed,
+                                      const uint8_t *is_valid, uint32_t flags, uint64_t batch, const uint8_t *status, void *advice_out,
+                                      uint64_t out_stride, h2r_stream_t stream);
+uint64_t h2r_verify_circuit_copy_map(const h2r_ctx *ctx, const h2r_verify_layout *vl, const uint8_t *e_le_bytes, size_t e_len,
+                                     h2r_copy *out, uint64_t cap);
 
 /* One RSAChip::modpow_public_key element (src/chip.rs:99-114) as advice rows, in the reference's op order: [assert_in_field(x, n) :106:
  * the rows of h2r_fresh_op_emit_advice(H2R_OP_IS_IN_FIELD, H2R_ADVICE_ASSERT_ONE)] [pow_mod_fixed_exp / pow_mod :108-111: the rows of
